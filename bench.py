@@ -5,7 +5,14 @@ One step = one block of B frames pushed through every channel chain of the progr
 (LOAD_GAIN -> 16 biquads -> 4096-tap FIR -> SAT0DB -> STORE for the north-star workload) by
 dspRuntimeBlockDevice(); inputs and outputs are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload north|cfg2|cfg3|cfg4|cfg5] [--block B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload north|cfg2|cfg3|cfg4|cfg5] [--block B] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, ms_per_step = milliseconds of one
+timed step ...).  --full adds everything else it measures or checks: the check against the reference's pins before timing, the CPU
+baseline, the per-kernel and roofline figures (untimed steps of their own) and, for N > 1, the block-boundary collectives.  Both
+time the same steps the same way, so their headline figures compare.  --dump-outputs DIR writes the output block of the last timed
+step to DIR/output.npy (DIR/output_rank<r>.npy per rank for N > 1; see dump_outputs()); the filter state is put back to the
+program's initial state after the time-based settle phase, so the same arguments give the same inputs and the same outputs.
 
 N > 1 runs one rank per GPU, whoever starts it:
   * under a launcher (the driver's  python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...):
@@ -14,7 +21,7 @@ N > 1 runs one rank per GPU, whoever starts it:
   * bare (python bench.py --gpus N, WORLD_SIZE unset): this process -- which has not touched the GPU and never will --
     times the CPU baseline, then starts that very launcher command as a CHILD process (N fresh rank processes; nothing
     is exec'ed over a process that has initialised HIP), hands the CPU figure to rank 0 through a temporary file
-    (AVDSP_BENCH_CPU_JSON), lets rank 0's JSON line through on stdout and leaves with the children's exit code.
+    (AVDSP_BENCH_CPU_JSON; --full only), lets rank 0's JSON line through on stdout and leaves with the children's exit code.
 The experiment is the one BASELINE.json names: a FIXED program (north: 4096 channels;
 cfg5: 16384) at 1, 2, 4 and 8 GPUs = STRONG scaling.  Every rank loads the same unsharded program and
 calls dspRuntimeSetShard(rank, world): the library cuts the lowered chain list into contiguous balanced
@@ -22,7 +29,7 @@ ranges, the rank feeds its column slice of the [B][C] block and gets its slice o
 are independent, so there is NO data-path collective; torch.distributed (RCCL) is used for the barriers
 and the max-over-ranks time.
 
-Rank 0 prints ONE JSON line with, besides the contract fields:
+Rank 0 prints ONE JSON line; with --full it carries, besides the contract fields:
   roofline     -- for the dominant kernel (the FIR on v_mfma_f64_16x16x4_f64 when the workload has
                   one, else the biquad cascade): algorithmic work per launch / average launch time
                   from the dispatches' own start / end stamps (hipExtLaunchKernel events on the launch
@@ -255,6 +262,24 @@ def verify_against_reference_pins(args, make_runtime, workload, shard_rank, shar
     return what
 
 
+DUMP_BYTES = 60_000_000                 # what --dump-outputs may write in all (npy headers and channel lists fit in the rest of 64 MB)
+
+
+def dump_outputs(dirname, name, out, out_base, world):
+    """--dump-outputs: the [B][Cl] output block of the last timed step as DIR/<name>.npy -- float32 as it is, the int32 words of the
+    fixed-point formats as float64 (exact).  A block larger than this rank's share of DUMP_BYTES keeps a fixed, seeded sample of its
+    channels, whose global channel numbers go to DIR/<name>_channels.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    a = out if out.dtype == np.float32 else out.astype(np.float64)
+    cap = DUMP_BYTES // world
+    if a.nbytes > cap:
+        keep = max(1, cap // (a.shape[0] * a.itemsize))
+        cols = np.sort(np.random.default_rng(20260104).choice(a.shape[1], size=keep, replace=False))
+        a = a[:, cols]
+        np.save(os.path.join(dirname, f"{name}_channels.npy"), (cols + out_base).astype(np.float64))
+    np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(args, fmt, S, T, B):
     """python bench.py --gpus N without a launcher: be the launcher.  This process makes no HIP call (counting devices does not
     initialise the GPU on this image); it times the CPU baseline, then runs
@@ -274,7 +299,7 @@ def launch_ranks(args, fmt, S, T, B):
             return 2
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     with tempfile.TemporaryDirectory() as d:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(fmt, S, T, B, budget_s=args.cpu_budget)
             path = os.path.join(d, "cpu_baseline.json")
             with open(path, "w") as f:
@@ -322,10 +347,16 @@ def main():
     ap.add_argument("--dist", action="store_true", help="initialise the process group and run every collective leg even at world 1 (under a launcher with "
                     "--nproc-per-node 1): what tests/ use to execute each RCCL call bench.py makes on a one-GPU box")
     ap.add_argument("--no-verify", action="store_true", help="skip the pre-timing check of this rank's columns against the reference's pins")
-    ap.add_argument("--gather", action="store_true", help="(the default for N > 1) also time an RCCL all_gather of the ranks' [B][C/N] output blocks and an all_reduce of "
+    ap.add_argument("--gather", action="store_true", help="(the default for N > 1 under --full) also time an RCCL all_gather of the ranks' [B][C/N] output blocks and an all_reduce of "
                     "their checksums (SURVEY.md 8e: block-boundary collectives), reported BESIDE value, never inside it")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the block-boundary collectives leg")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the check against the reference's pins, "
+                    "the CPU baseline, the per-kernel and roofline figures and (N > 1) the block-boundary collectives")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the output block of the last timed step to DIR/output.npy "
+                    "(float32, or float64 for the fixed-point formats; a seeded sample of the channels above 60 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
 
     if args.custom:
         WORKLOADS["custom"] = tuple(int(v) for v in args.custom.split(","))
@@ -359,7 +390,7 @@ def main():
     # too (the other ranks wait for it in init_process_group), unless the process that started the ranks has
     # already timed it (AVDSP_BENCH_CPU_JSON, see launch_ranks).
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         handed = os.environ.get("AVDSP_BENCH_CPU_JSON")
         if handed and os.path.exists(handed):
             with open(handed) as f:
@@ -412,11 +443,11 @@ def main():
             rr.set_option("host_pin", args.host_pin)
         return rr
 
-    # What is about to be timed is checked first, on every rank: the same path, the same options, the reference's own bits
+    # --full: what is about to be timed is checked first, on every rank: the same path, the same options, the reference's own bits
     # ... and the ranks of an N > 1 job leave TOGETHER when any of them fails: a rank that exited alone would leave the others in
     # their next barrier until the launcher's timeout
     verified, verify_error = None, None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         try:
             verified = verify_against_reference_pins(args, make_runtime, args.workload, shard_rank, shard_world, torch)
             if os.environ.get("AVDSP_BENCH_FAIL_RANK") == str(rank):          # tests/: what the job does when one rank's check fails
@@ -470,15 +501,25 @@ def main():
 
     # Every timed launch costs the stream an event pair (a few microseconds each).  In the timed region only the
     # kernel the roofline is quoted on carries one; the cascade in front of a FIR is timed over a few extra
-    # untimed steps first (kernels_ms.biquad), back to back with the FIR (overlap off), which also gives the FIR
-    # kernel's duration with the chip to itself (roofline.frac_alone).
+    # untimed steps first (kernels_ms.biquad, --full), back to back with the FIR (overlap off), which also gives the FIR
+    # kernel's duration with the chip to itself (roofline.frac_alone).  A plain run stamps the same launches of the
+    # timed region, so that its headline figure is the one --full measures.
+    state0 = r.state.copy()                                 # the program's initial state (nothing has run yet)
     r.set_option("profile", 0)
     t_settle = time.perf_counter()
     while time.perf_counter() - t_settle < args.settle:
         for _ in range(20):
             step()
         torch.cuda.synchronize()
-    r.set_option("profile", 1)
+    # the settle phase ran as many steps as its time allowed: back to the initial state, so that the steps from here on -- and the
+    # outputs --dump-outputs writes -- do not depend on how fast it went (dspRuntimeUploadState rebuilds the FIR rings from it)
+    r.state[:] = state0
+    r.upload_state()
+    torch.cuda.synchronize()
+    # ... and the clock the settle phase built up, back after the copy's idle gap: a fixed count of untimed steps (the same every run)
+    for _ in range(200):
+        step()
+    r.set_option("profile", 1 if (args.full or not (T and S)) else 2 * (1 << 1))     # (plain, cascade + FIR: the FIR only, as below)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -487,7 +528,7 @@ def main():
     # FIR and 15 % of a 35-us cascade
     dom_ms = warm[1][0] / warm[1][1] if (T and warm[1][1]) else (warm[0][0] / warm[0][1] if warm[0][1] else 0.0)
     bq_side = fir_alone = None
-    if T and S:
+    if args.full and T and S:
         r.set_option("overlap", 0)
         for _ in range(10):
             step()
@@ -530,9 +571,12 @@ def main():
         rank_ms = [float(v.item()) / args.steps * 1e3 for v in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # block-boundary collectives (opt-in, beside the metric): every rank's [B][C/N] output gathered on every rank, checksums summed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", dm.to_host(ys[(turn[0] - 1) % len(ys)]),
+                     out_base, world)
+    # block-boundary collectives (--full or --gather, beside the metric): every rank's [B][C/N] output gathered on every rank, checksums summed
     gather = None
-    if use_dist and not args.no_gather:
+    if use_dist and not args.no_gather and (args.full or args.gather):
         # (shards differ by at most one chain: every rank hands over max(C/N) columns, the last one of a smaller shard unused)
         cmax = -(-C // world)
         ypad = y if Cl == cmax else torch.nn.functional.pad(y, (0, cmax - Cl))
@@ -567,13 +611,15 @@ def main():
     # dispatch's own start and end stamps, what rocprofv3's kernel trace reads, nothing on the stream -- no correction applies.
     # (Kernels launched the plain way are bracketed by two recorded events, which read ~5 us more than the kernel took:
     # kernels_ms.event_pair says how much on this box.)
-    pairs = []
-    for _ in range(60):
-        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(); e1.record()
-        pairs.append((e0, e1))
-    torch.cuda.synchronize()
-    pair_ms = float(np.median([a.elapsed_time(b) for a, b in pairs[10:]]))
+    pair_ms = None
+    if args.full:
+        pairs = []
+        for _ in range(60):
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(); e1.record()
+            pairs.append((e0, e1))
+        torch.cuda.synchronize()
+        pair_ms = float(np.median([a.elapsed_time(b) for a, b in pairs[10:]]))
 
     def timing_label(n, npairs):
         """how the library says it timed the launches it summed: by the dispatch's own stamps, or by an event pair around the launch"""
@@ -632,7 +678,9 @@ def main():
             # --profile-stride beyond the run: no launch of the timed region carried its stamps (the un-sampled step); the roofline is
             # then the kernel alone, from the ten untimed steps in front of the timed region, and says so
             fir_raw, fir_n, fir_pairs = fir_alone[0] / fir_alone[1], fir_alone[1], 0
-        if T and fir_n:
+        if not args.full:
+            roof = None                                          # (the roofline is --full's, beside the per-kernel figures it needs)
+        elif T and fir_n:
             # `frac` from the kernel's own start / end stamps of every timed launch (rocprofv3's kernel average of the same command
             # agrees, profiles/)
             per_launch = fir_raw * 1e-3
@@ -693,11 +741,12 @@ def main():
                                    f"DSP_FORMAT {fmt}; {shard_txt}, no data-path collective",
                        "channels": C, "channels_per_gpu": Cl, "sections": S, "taps": T, "block": B, "format": fmt,
                        "overlap": r.get_option("overlap"), "ready_words": r.get_option("ready_words"), "ready_mode": r.get_option("ready_mode"), "side_by_side": r.get_option("side_by_side"), "streams_remade": r.get_option("streams_remade"), "cu_split": r.get_option("cu_split"), "fir_split": r.get_option("fir_split"), "fir_launch": r.get_option("fir_launch"), "fir_lean": r.get_option("fir_lean"), "ring_wait": r.get_option("ring_wait"), "settle_s": args.settle, "profile_stride": stride},
-            "roofline": roof,
             "hbm_frac_step": step_bytes / step_s / 1e9 / PEAK_HBM_GBS,
-            "kernels_ms": {"biquad": bq_raw, "fir": fir_raw, "event_pair": pair_ms,
-                           "biquad_timing": timing_label(bq_n, bq_pairs) + ("" if bq_side is None else "; ten untimed steps in front of the timed region, overlap off")},
         }
+        if args.full:
+            line["roofline"] = roof
+            line["kernels_ms"] = {"biquad": bq_raw, "fir": fir_raw, "event_pair": pair_ms,
+                                  "biquad_timing": timing_label(bq_n, bq_pairs) + ("" if bq_side is None else "; ten untimed steps in front of the timed region, overlap off")}
         line["verified"] = verified
         line["verified_ranks"] = verified_ranks          # ranks whose own columns matched the reference's pins (every rank checks; any mismatch ends the job)
         if use_dist:

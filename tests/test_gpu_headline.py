@@ -362,7 +362,7 @@ def _bench_ranks(world, extra=(), env_extra=None, workload="cfg3"):
     env = dict(os.environ, AVDSP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-           "--settle", "0.05", "--workload", workload, "--no-cpu-baseline", *extra]
+           "--settle", "0.05", "--workload", workload, "--no-cpu-baseline", "--full", *extra]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
 
 
@@ -447,7 +447,7 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--settle", "0.05",
-                        "--workload", "cfg3", "--cpu-budget", "1.5"], env=_clean_env(AVDSP_DIST_BACKEND="gloo"),
+                        "--workload", "cfg3", "--cpu-budget", "1.5", "--full"], env=_clean_env(AVDSP_DIST_BACKEND="gloo"),
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _bench_line(p)
@@ -471,7 +471,7 @@ def test_every_collective_of_bench_runs_on_rccl_at_world_1():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--dist", "--steps", "4", "--warmup", "1",
-           "--settle", "0.05", "--workload", "cfg3", "--cpu-budget", "1.0"]
+           "--settle", "0.05", "--workload", "cfg3", "--cpu-budget", "1.0", "--full"]
     p = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _bench_line(p)
@@ -490,7 +490,7 @@ def test_bench_block_sizes_push_the_same_pins_through():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for blk in (64, 256, 4096):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--settle", "0.05",
-                            "--workload", "cfg3", "--block", str(blk), "--no-cpu-baseline"], env=_clean_env(),
+                            "--workload", "cfg3", "--block", str(blk), "--no-cpu-baseline", "--full"], env=_clean_env(),
                            capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         line = _bench_line(p)
@@ -499,8 +499,40 @@ def test_bench_block_sizes_push_the_same_pins_through():
     # one-row-tile wave at 256 frames, four chains per two-row-tile workgroup at 512)
     for blk in (256, 512):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--settle", "0.05",
-                            "--workload", "north", "--block", str(blk), "--no-cpu-baseline"], env=_clean_env(),
+                            "--workload", "north", "--block", str(blk), "--no-cpu-baseline", "--full"], env=_clean_env(),
                            capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         line = _bench_line(p)
         assert line["config"]["block"] == blk and "north_f6" in line["verified"] and "SHA-256" in line["verified"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the --full legs, and --dump-outputs writes the output block of its last
+    timed step: the same bits whatever the time-based settle phase ran before the warm-up (the state goes back to the program's initial
+    state after it), and on sampled channels the oracle's bits for the 200 re-settle, warm-up and timed steps of the same block from
+    that state."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 1
+    dumps = []
+    for k, settle in enumerate(("0.3", "0.05")):
+        d = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--settle", settle,
+                            "--workload", "north", "--dump-outputs", str(d)], env=_clean_env(), capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = _bench_line(p)
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Msamples/s"
+        assert line["cpu_baseline"] is None and line["verified"] is None and "roofline" not in line and "kernels_ms" not in line
+        assert sorted(os.listdir(d)) == ["output.npy"]
+        dumps.append(np.load(d / "output.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1024, 4096)
+    assert (words(dumps[0]) == words(dumps[1])).all(), "the dumped outputs depend on the settle phase"
+    fmt, S, T, B = 6, 16, 4096, 1024
+    x = pb.lcg_input(B, 4096, True, seed=12345)
+    for c in (0, 1234, 4095):
+        o = po.OracleProgram(fmt, pb.synth_program(fmt, 1, S, T, channel_base=c))
+        xc = np.ascontiguousarray(x[:, c:c + 1])
+        for _ in range(200 + warmup + steps):
+            want = o.run_block(xc, 1, 1)
+        assert (words(want[:, 0]) == words(dumps[0][:, c])).all(), f"channel {c} differs from the oracle"

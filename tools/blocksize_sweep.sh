@@ -10,7 +10,7 @@ OUT=gpurun_out/${TAG}_blocksize.jsonl
 for W in north cfg3 cfg3i cfg4; do
   for B in 64 128 256 512 1024 4096; do
     STEPS=$(( 40960 / B )); [ $STEPS -lt 40 ] && STEPS=40; [ $STEPS -gt 320 ] && STEPS=320
-    python3 bench.py --workload $W --block $B --steps $STEPS --warmup 10 --no-cpu-baseline "$@" >> "$OUT" 2>> gpurun_out/${TAG}_blocksize.err || echo "{\"failed\": \"$W $B\"}" >> "$OUT"
+    python3 bench.py --full --workload $W --block $B --steps $STEPS --warmup 10 --no-cpu-baseline "$@" >> "$OUT" 2>> "${OUT%.jsonl}.err" || echo "{\"failed\": \"$W $B\"}" >> "$OUT"
     echo "$W B=$B done"
   done
 done

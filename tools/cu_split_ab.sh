@@ -6,7 +6,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-r05}_cu_split_ab.txt; : > "$OUT"
-run() { python3 bench.py --no-cpu-baseline --steps 96 --warmup 10 --profile-stride 1000 "$@" 2>>gpurun_out/cu_split.err | python3 -c "
+run() { python3 bench.py --full --no-cpu-baseline --steps 96 --warmup 10 --profile-stride 1000 "$@" 2>>"${OUT%.txt}.err" | python3 -c "
 import sys, json
 l = json.loads(sys.stdin.read()); c = l['config']
 print('%-46s ch %4d  step %7.2f us  %7.1f Msamples/s   fir alone %.1f us  cascade alone %.1f us  side_by_side %s remade %s' % (' '.join(sys.argv[1:]), c['channels_per_gpu'], l['ms_per_step'] * 1e3, l['value'], (l['roofline'] or {}).get('launch_ms_alone', 0) * 1e3, l['kernels_ms']['biquad'] * 1e3, c['side_by_side'], c['streams_remade']))" "$@" >> "$OUT"; }

@@ -4,7 +4,7 @@
 #   bash tools/fir_boundary_lab.sh > gpurun_out/r04_fir_boundary_lab.txt
 set -uo pipefail
 ROOT="$(pwd)"
-line() { python3 "$ROOT/bench.py" --no-cpu-baseline --steps 48 "$@" 2>/dev/null | grep '^{' | python3 -c "
+line() { python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 48 "$@" 2>/dev/null | grep '^{' | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline'] or {}
 print('ms/step %.4f   FIR launch %.4f   FIR alone %s' % (d['ms_per_step'], r.get('launch_ms',0), ('%.4f' % r['launch_ms_alone']) if r.get('launch_ms_alone') else '-'))"; }

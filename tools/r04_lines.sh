@@ -4,9 +4,9 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 L=gpurun_out/r04_bench_lines.jsonl; : > $L
-run() { python3 bench.py --steps 48 --no-cpu-baseline "$@" 2>/dev/null | grep '^{' >> $L; echo "$* rc=$?"; }
-python3 bench.py --steps 48 2>/dev/null | grep '^{' >> $L
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' >> $L
+run() { python3 bench.py --full --steps 48 --no-cpu-baseline "$@" 2>/dev/null | grep '^{' >> $L; echo "$* rc=$?"; }
+python3 bench.py --full --steps 48 2>/dev/null | grep '^{' >> $L
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' >> $L
 run --profile-stride 1000
 run --shard 0/2; run --shard 0/4; run --shard 0/8
 run --shard 0/2 --profile-stride 1000; run --shard 0/4 --profile-stride 1000; run --shard 0/8 --profile-stride 1000

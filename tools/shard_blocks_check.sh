@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { python3 bench.py --workload north --no-cpu-baseline --steps 120 --warmup 10 --profile-stride 1000 "$@" 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --workload north --no-cpu-baseline --steps 120 --warmup 10 --profile-stride 1000 "$@" 2>/dev/null | python3 -c "
 import sys, json
 l = json.loads(sys.stdin.read()); c = l['config']
 print('%-40s step %8.2f us  verified %s' % (' '.join(sys.argv[1:]), l['ms_per_step'] * 1e3, bool(l['verified'])))" "$@"; }
