@@ -112,11 +112,20 @@ typedef struct avdsp_ctx {
     int             chain_inst_made;                       /* the device holds ninst copies of the mirror; the plans are ninst x the cores' chains, made for ... */
     size_t          chain_inst_in, chain_inst_out;         /* ... these distances between the instances' sample blocks (words) */
     int             chain_inst_win[5];                     /* the windows the cores' IOs were last checked against (format, in base, in stride, out base, out stride); [0] = 0: none */
+    int             opt_frame_server, opt_frame_server_idle_us;      /* "frame_server" (AVDSP_OPT_FRAME_SERVER), "frame_server_idle_us" */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
 static avdsp_ctx g_template = { .opt_lane_hw = 1, .opt_ring_wait = 1, .opt_ready_words = -1, .opt_fir_impl = 1, .opt_biquad_impl = 1, .opt_device = -1, .opt_interp_impl = 1, .opt_strand_split = 1, .opt_strand_lanes = 1, .shard_world = 1,
-                                .mantissa = DSP_MANT, .device_ordinal = -1 };
+                                .mantissa = DSP_MANT, .device_ordinal = -1, .opt_frame_server_idle_us = 1000 };
+
+/* A host written for the reference cannot call dspRuntimeSetOption: AVDSP_FRAME_SERVER=1 in the environment makes "frame_server" 1 the
+ * default (read once, when the library is loaded) */
+__attribute__((constructor)) static void frame_server_from_environment(void)
+{
+    const char *e = getenv("AVDSP_FRAME_SERVER");
+    if (e && !strcmp(e, "1")) g_template.opt_frame_server = 1;
+}
 #define MAX_PROGRAMS 64
 static avdsp_ctx *g_ctx[MAX_PROGRAMS];
 static int        g_nctx;
@@ -317,6 +326,18 @@ static int set_option_here(const char *key, int value)
         G.opt_cu_split = value;
         return 0;
     }
+    if (!strcmp(key, "frame_server")) {                  /* one-frame calls of interpreter cores through a resident server */
+        if (value != 0 && value != 1) return fail(-1, "frame_server: 0 or 1");
+        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER, value)) return hip_fail();
+        G.opt_frame_server = value;
+        return 0;
+    }
+    if (!strcmp(key, "frame_server_idle_us")) {
+        if (value < 50 || value > 20000) return fail(-1, "frame_server_idle_us: 50 .. 20000");
+        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER_IDLE_US, value)) return hip_fail();
+        G.opt_frame_server_idle_us = value;
+        return 0;
+    }
     if (!strcmp(key, "ready_test")) {                    /* tests only (AVDSP_OPT_READY_TEST) */
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_READY_TEST, value)) return hip_fail();
         return 0;
@@ -372,6 +393,11 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "side_by_side")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_SIDE_BY_SIDE) : -1; }
     if (!strcmp(key, "streams_remade")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_STREAMS_REMADE) : 0; }
     if (!strcmp(key, "ready_mode"))  { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_READY_MODE) : 0; }
+    if (!strcmp(key, "frame_server")) return G.opt_frame_server;
+    if (!strcmp(key, "frame_server_idle_us")) return G.opt_frame_server_idle_us;
+    if (!strcmp(key, "frame_server_frames")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_FRAMES) : 0;
+    if (!strcmp(key, "frame_server_launches")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_LAUNCHES) : 0;
+    if (!strcmp(key, "frame_server_fallbacks")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_FALLBACKS) : 0;
     if (!strcmp(key, "fir_rows"))    return G.opt_fir_rows;
     if (!strcmp(key, "host_split"))  return G.opt_host_split;
     if (!strcmp(key, "host_pin"))    return G.opt_host_pin;
@@ -495,6 +521,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -1279,6 +1306,8 @@ static int ensure_device(void)
         avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_SPLIT, G.opt_host_split) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_PIN, G.opt_host_pin) ||
         (G.opt_cu_split && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_CU_SPLIT, G.opt_cu_split)) ||
         (G.opt_group_serial && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_GROUP_FANOUT, 0)) ||
+        (G.opt_frame_server && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER, 1)) ||
+        (G.opt_frame_server_idle_us != 1000 && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER_IDLE_US, G.opt_frame_server_idle_us)) ||
         (G.ninst > 1 && avdsp_hip_set_instances(G.dev, G.ninst))) {
         hip_fail(); drop_device(); return g_err_code;
     }

@@ -3542,6 +3542,115 @@ __global__ void frame_done(unsigned *flag, unsigned seq)
     __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+/* The frame server ("frame_server"): ONE resident wave per program that serves dspRuntime_N calls of the program's
+ * interpreter cores out of LDS, fed through a mailbox in mapped pinned host memory (coherent).  Mailbox words: */
+namespace fsrv {
+constexpr int kReq = 0, kStop = 1;              /* host: request number; stop = the generation of the server to leave (one 8-byte poll) */
+constexpr int kPlan = 2;                        /* host: the requested core, an index into the launch's plan table */
+constexpr int kReply = 32, kExited = 33;        /* server: number of the latest request served; generation of the server that has left */
+constexpr int kSlots = 64;                      /* the frame's IO slots 0 .. span - 1, in and out */
+constexpr int kMaxSpan = 2048;
+constexpr int kWords = kSlots + kMaxSpan;
+constexpr int kMaxPlans = 16;
+constexpr unsigned long long kLifetimeTicks = 20ull * 100000ull;     /* 20 ms of s_memrealtime (100 MHz) */
+constexpr unsigned kMaxPolls = 1u << 22;        /* (a second bound on the wait, should the clock not advance) */
+}
+
+struct ServerArgs {
+    unsigned *mb;                                /* the mailbox (device address of the mapped host words) */
+    const GenericArgs *table; int nplans;        /* the program's interpreter plans the server may be asked for */
+    int *buf; TpdfGlobals *tpdf; unsigned *scratch;
+    int scratch_len, total_words, keep_words;
+    unsigned gen, done;                          /* this launch's generation; the latest request already answered */
+    unsigned long long idle_ticks;
+};
+
+/* system-scope publish of one word behind everything the wave has stored (the fence's own wait is repeated after it: the compiler
+ * may drop it where it believes nothing is outstanding) */
+__device__ __forceinline__ void fsrv_publish(unsigned *word, unsigned v, int lane)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <int FMT, bool STAGED>
+__global__ __launch_bounds__(64) void frame_server(const ServerArgs s)
+{
+#if AVDSP_INTERP_HW_FLUSH
+    if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
+#endif
+    extern __shared__ unsigned lds_words[];
+    __shared__ TpdfGlobals tg;
+    const int lane = threadIdx.x;
+    unsigned *samp;
+    int *prog;
+    if constexpr (STAGED) {                              /* as interp_core<FMT, true>: frame, then the whole mirror */
+        samp = lds_words;
+        prog = (int *)(lds_words + s.scratch_len);
+        for (int k = lane; k < s.total_words; k += 64) prog[k] = s.buf[k];
+        for (int k = lane; k < s.scratch_len; k += 64) samp[k] = s.scratch[k];
+    } else {
+        samp = s.scratch;
+        prog = s.buf;
+    }
+    if (lane == 0) tg = *s.tpdf;
+    __syncthreads();
+    unsigned *mb = s.mb, *slots = s.mb + fsrv::kSlots;
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    unsigned long long last = t0;
+    unsigned done = s.done, polls = 0;
+    for (;;) {
+        /* lane 0 polls the request and stop words: relaxed system-scope loads, s_sleep between them, ONE acquire after */
+        unsigned req = done;
+        if (lane == 0) {
+            for (;;) {
+                const unsigned long long w = __hip_atomic_load(reinterpret_cast<unsigned long long *>(mb + fsrv::kReq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if ((unsigned)(w >> 32) == s.gen) { req = done; break; }
+                if ((unsigned)w != done) { req = (unsigned)w; break; }
+                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+                if (now - last > s.idle_ticks || now - t0 > fsrv::kLifetimeTicks || ++polls > fsrv::kMaxPolls) break;
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        req = __shfl(req, 0);
+        if (req == done) break;                          /* stop, idle or lifetime: leave */
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        const int pi = (int)__hip_atomic_load(mb + fsrv::kPlan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (pi < 0 || pi >= s.nplans) break;             /* (never from the library: leave unanswered, the host runs the call the ordinary way) */
+        const GenericArgs &a = s.table[pi];
+        const int span = a.io.in_stride;
+        for (int k = lane; k < span; k += 64) samp[k] = slots[k];
+        __syncthreads();
+        if (lane == 0) {
+            /* a core that neither owns the TPDF globals nor runs alone leaves them as they were (interp_core writes them back only then) */
+            const bool keep_tpdf = a.tpdf_owner || a.nown < 0;
+            const TpdfGlobals before = tg;
+            interp::run_frame<FMT>(a, prog, samp, &tg, 0);
+            if (!keep_tpdf) tg = before;
+        }
+        __syncthreads();
+        /* the core's slots back into the mailbox (slots it does not store keep the caller's value, which the mailbox holds), and into the
+         * program's scratch frame what interp_core would write back there after this frame */
+        for (int k = lane; k < span; k += 64) {
+            const bool wr = k < 256 && (a.written_io[k >> 5] >> (k & 31) & 1u);
+            const unsigned v = samp[k];
+            if (a.rows_whole || wr) slots[k] = v;
+            if constexpr (STAGED) { if (a.nown < 0 || wr) s.scratch[k] = v; }
+        }
+        fsrv_publish(mb + fsrv::kReply, req, lane);
+        done = req;
+        last = __builtin_amdgcn_s_memrealtime();
+        if (last - t0 > fsrv::kLifetimeTicks) break;
+    }
+    /* leaving: the mirror (the header stays the host's) and the TPDF globals go home, then the generation says so */
+    if constexpr (STAGED) { for (int k = s.keep_words + lane; k < s.total_words; k += 64) s.buf[k] = prog[k]; }
+    __syncthreads();
+    if (lane == 0) *s.tpdf = tg;
+    fsrv_publish(mb + fsrv::kExited, s.gen, lane);
+}
+
 /* ------------------------------------------------------------------------------------------
  * host side of the thin ABI
  * ---------------------------------------------------------------------------------------- */
@@ -3696,6 +3805,15 @@ struct avdsp_hip_prog {
     int host_pin = 0;                    /* pin the caller's buffers in place and remember them: only for a host that keeps them allocated */
     bool ev_fir_set[kAhead] = {false, false, false};
     unsigned long long blk = 0;
+    /* the frame server (frame_server): "frame_server", "frame_server_idle_us" and the counters behind the read-only keys */
+    int fs_on = 0, fs_idle_us = 1000;
+    unsigned *fs_h = nullptr, *fs_d = nullptr;           /* the mailbox: mapped pinned host words (fsrv::kWords) */
+    GenericArgs *fs_table = nullptr;                     /* device copy of the live server's plan table */
+    int fs_plan[fsrv::kMaxPlans] = {}; int fs_nplans = 0, fs_format = 0;
+    bool fs_live = false;                                /* a server was launched on fs_stream and has not been synchronised with yet */
+    hipStream_t fs_stream = nullptr;                     /* ... taken from the library's pool while live */
+    unsigned fs_gen = 0, fs_seq = 0;                     /* generation of the latest launch; number of the latest request */
+    long long fs_frames = 0, fs_launches = 0, fs_fallbacks = 0;
 };
 
 namespace {
@@ -4460,6 +4578,195 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
     return 0;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * the frame server, host side.  A server is one wave on a non-blocking stream of the library's pool; the host
+ * posts a frame into the mailbox and waits for the reply, every wait bounded.  While a server is live the program's state is in
+ * its LDS: every entry point that launches for the program, reads or writes its device state or changes its plans calls
+ * fs_stop first, which has the server write everything back and leave.
+ * ---------------------------------------------------------------------------------------- */
+constexpr int kFsStreams = 3;                            /* servers per process: fewer than the runtime's 4 hardware queues */
+constexpr int kFsReplyUs = 2000;                         /* the host's wait for a reply (as AVDSP_SMALL_FLAG's default) */
+constexpr size_t kFsLdsMax = 144 * 1024;
+struct FsPool { int device; hipStream_t st[kFsStreams]; avdsp_hip_prog *user[kFsStreams]; };
+std::vector<FsPool> g_fs_pool;                           /* per device: its streams are made together, so the runtime deals them different queues */
+std::vector<avdsp_hip_prog *> g_fs_live;                 /* programs whose server is live (stopped at exit) */
+
+unsigned fs_load(const unsigned *w) { return __atomic_load_n(w, __ATOMIC_ACQUIRE); }
+
+int fs_stop(avdsp_hip_prog *prog)
+{
+    if (!prog->fs_live) return 0;
+    __atomic_store_n(&prog->fs_h[fsrv::kStop], prog->fs_gen, __ATOMIC_RELEASE);
+    /* a server that runs sees the stop word within a poll; one that has not started yet leaves as soon as it does (the stream sync) */
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; fs_load(&prog->fs_h[fsrv::kExited]) != prog->fs_gen; spins++)
+        if ((spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(prog->fs_idle_us + kFsReplyUs)) break;
+    prog->fs_live = false;
+    g_fs_live.erase(std::remove(g_fs_live.begin(), g_fs_live.end(), prog), g_fs_live.end());
+    const hipError_t e = hipStreamSynchronize(prog->fs_stream);
+    for (auto &q : g_fs_pool)
+        for (int i = 0; i < kFsStreams; i++) if (q.user[i] == prog) q.user[i] = nullptr;
+    prog->fs_stream = nullptr;
+    if (e != hipSuccess) return set_err("frame server: hipStreamSynchronize: %s", hipGetErrorString(e));
+    return 0;
+}
+#define FS_STOP(prog) do { if (fs_stop(prog)) return -1; } while (0)
+
+void fs_stop_all() { while (!g_fs_live.empty()) (void)fs_stop(g_fs_live.back()); }
+
+/* the plans a server can take: whole interpreter cores of the program itself (no instances, no dither pieces) */
+bool fs_servable(const avdsp_hip_prog *prog, const Plan &pl)
+{
+    return pl.generic && pl.instances <= 1 && pl.ga.tpdf_role == 0 && pl.io_span <= fsrv::kMaxSpan && prog->d_frame && pl.io_span <= prog->frame_words;
+}
+
+GenericArgs fs_args(const Plan &pl)
+{
+    GenericArgs a = pl.ga;
+    a.io = BlockIO{};
+    a.io.in_stride = a.io.out_stride = pl.io_span; a.io.nframes = 1;
+    a.rows_whole = pl.ga.nown < 0 || pl.ga.nrd_slot < 0 || pl.ga.nwr_slot < 0;      /* (needs_whole) */
+    a.done_flag = nullptr;
+    return a;
+}
+
+/* LDS = [frame][mirror][4 words: the interpreter fetches the two words behind every head word, also behind the last one] */
+size_t fs_lds_bytes(const avdsp_hip_prog *prog) { return ((size_t)prog->frame_words + prog->total_words + 4) * 4; }
+bool fs_staged(const avdsp_hip_prog *prog) { return fs_lds_bytes(prog) <= kFsLdsMax; }
+
+int fs_launch(avdsp_hip_prog *prog, unsigned done)
+{
+    ServerArgs s{};
+    s.mb = prog->fs_d; s.table = prog->fs_table; s.nplans = prog->fs_nplans;
+    s.buf = prog->d_buf; s.tpdf = prog->d_tpdf; s.scratch = prog->d_frame;
+    s.scratch_len = prog->frame_words; s.total_words = prog->total_words; s.keep_words = (int)(sizeof(dspHeader_t) / 4);
+    s.gen = ++prog->fs_gen; s.done = done; s.idle_ticks = (unsigned long long)prog->fs_idle_us * 100ull;
+    const bool staged = fs_staged(prog);
+    const size_t lds = staged ? fs_lds_bytes(prog) : 0;
+#define AVDSP_LAUNCH_SERVER(F) \
+    if (staged) hipLaunchKernelGGL((frame_server<F, true>), dim3(1), dim3(64), lds, prog->fs_stream, s); \
+    else        hipLaunchKernelGGL((frame_server<F, false>), dim3(1), dim3(64), 0, prog->fs_stream, s)
+    switch (prog->fs_format) {
+    case 2:  AVDSP_LAUNCH_SERVER(2); break;
+    case 3:  AVDSP_LAUNCH_SERVER(3); break;
+    case 4:  AVDSP_LAUNCH_SERVER(4); break;
+    case 5:  AVDSP_LAUNCH_SERVER(5); break;
+    default: AVDSP_LAUNCH_SERVER(6); break;
+    }
+#undef AVDSP_LAUNCH_SERVER
+    HIP_TRY(hipGetLastError());
+    prog->fs_launches++;
+    return 0;
+}
+
+/* a server for the program, holding `plan` at table index 0: 0 started, 1 none can be (every stream of the pool is taken), < 0 error */
+int fs_start(avdsp_hip_prog *prog, int plan, unsigned done)
+{
+    if (!prog->fs_h) {
+        HIP_TRY(hipHostMalloc((void **)&prog->fs_h, (size_t)fsrv::kWords * 4, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(prog->fs_h, 0, (size_t)fsrv::kWords * 4);
+        HIP_TRY(hipHostGetDevicePointer((void **)&prog->fs_d, prog->fs_h, 0));
+    }
+    if (!prog->fs_table) HIP_TRY(hipMalloc((void **)&prog->fs_table, fsrv::kMaxPlans * sizeof(GenericArgs)));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    FsPool *pool = nullptr;
+    for (auto &q : g_fs_pool) if (q.device == dev) pool = &q;
+    if (!pool) {
+        FsPool q{};
+        q.device = dev;
+        for (auto &st : q.st) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        g_fs_pool.push_back(q);
+        pool = &g_fs_pool.back();
+    }
+    /* servers that have left on their own give their streams back */
+    for (size_t i = 0; i < g_fs_live.size();) {
+        avdsp_hip_prog *o = g_fs_live[i];
+        if (o != prog && fs_load(&o->fs_h[fsrv::kExited]) == o->fs_gen) { if (fs_stop(o)) return -1; } else i++;
+    }
+    int slot = -1;
+    for (int i = 0; i < kFsStreams && slot < 0; i++) if (!pool->user[i]) slot = i;
+    if (slot < 0 || (int)g_fs_live.size() >= kFsStreams) return 1;
+    const Plan &want = prog->plans[plan];
+    GenericArgs tab[fsrv::kMaxPlans];
+    int n = 0;
+    prog->fs_plan[n] = plan; tab[n++] = fs_args(want);
+    for (int i = 0; i < (int)prog->plans.size() && n < fsrv::kMaxPlans; i++)
+        if (i != plan && prog->plans[i].format == want.format && fs_servable(prog, prog->plans[i])) { prog->fs_plan[n] = i; tab[n++] = fs_args(prog->plans[i]); }
+    prog->fs_nplans = n; prog->fs_format = want.format;
+    if (fs_staged(prog)) {
+        static bool lds_set[7] = {};
+        if (!lds_set[want.format]) {
+            const void *fn = want.format == 2 ? (const void *)frame_server<2, true> : want.format == 3 ? (const void *)frame_server<3, true>
+                           : want.format == 4 ? (const void *)frame_server<4, true> : want.format == 5 ? (const void *)frame_server<5, true>
+                                                                                          : (const void *)frame_server<6, true>;
+            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFsLdsMax));
+            lds_set[want.format] = true;
+        }
+    }
+    pool->user[slot] = prog; prog->fs_stream = pool->st[slot];
+    prog->fs_live = true;
+    g_fs_live.push_back(prog);
+    static bool at_exit = false;
+    if (!at_exit) { at_exit = true; std::atexit(fs_stop_all); }
+    /* (stream-ordered in front of the launch; a synchronous copy of a few KB: the table is the stack's) */
+    HIP_TRY(hipMemcpyAsync(prog->fs_table, tab, (size_t)n * sizeof(GenericArgs), hipMemcpyHostToDevice, prog->fs_stream));
+    HIP_TRY(hipStreamSynchronize(prog->fs_stream));
+    return fs_launch(prog, done);
+}
+
+/* one dspRuntime_N call through the server: 0 served, 1 not (the caller takes the ordinary path; the server has been stopped where
+ * the state must come home), < 0 error */
+int fs_frame(avdsp_hip_prog *prog, int plan, const void *h_in, void *h_out)
+{
+    const Plan &pl = prog->plans[plan];
+    if (!prog->fs_on || h_in != h_out || !fs_servable(prog, pl) || prog->overlap || prog->inst_n > 1 || prog->chain_inst > 1) { FS_STOP(prog); return 1; }
+    int ti = -1;
+    if (prog->fs_live) {
+        if (prog->fs_format == pl.format) for (int i = 0; i < prog->fs_nplans; i++) if (prog->fs_plan[i] == plan) ti = i;
+        /* a core the live server does not hold, or a server that has left on its own (idle, lifetime): it is synchronised with, and
+         * a new one is started */
+        if (ti < 0 || fs_load(&prog->fs_h[fsrv::kExited]) == prog->fs_gen) FS_STOP(prog);
+    }
+    if (!prog->fs_live) {
+        const int rc = fs_start(prog, plan, prog->fs_seq);
+        if (rc) return rc;
+        ti = 0;
+    }
+    const size_t bytes = (size_t)pl.io_span * 4;
+    unsigned *mb = prog->fs_h;
+    memcpy(mb + fsrv::kSlots, h_in, bytes);
+    mb[fsrv::kPlan] = (unsigned)ti;
+    const unsigned seq = ++prog->fs_seq;
+    __atomic_store_n(&mb[fsrv::kReq], seq, __ATOMIC_RELEASE);
+    bool served = false, restarted = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; spins++) {
+        if (fs_load(&mb[fsrv::kReply]) == seq) { served = true; break; }
+        if ((spins & 63) != 63) continue;
+        if (fs_load(&mb[fsrv::kExited]) == prog->fs_gen) {
+            /* the server left without this request (idle or lifetime bound, just as it was posted): a new one, stream-ordered behind
+             * the old one's write-back, takes it up -- once */
+            if (fs_load(&mb[fsrv::kReply]) == seq) { served = true; break; }
+            if (restarted) break;
+            restarted = true;
+            if (fs_launch(prog, seq - 1)) return -1;
+            continue;
+        }
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kFsReplyUs)) break;
+    }
+    if (!served) {
+        /* the bound ran out: the server is stopped (it answers the request if it has it already); unanswered, the call goes the
+         * ordinary way -- a request is never run twice and never lost */
+        FS_STOP(prog);
+        served = fs_load(&mb[fsrv::kReply]) == seq;
+        if (!served) { prog->fs_fallbacks++; return 1; }
+    }
+    memcpy(h_out, mb + fsrv::kSlots, bytes);
+    prog->fs_frames++;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4513,6 +4820,7 @@ avdsp_hip_prog *avdsp_hip_prog_create(int total_words)
 void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
 {
     if (!p) return;
+    (void)fs_stop(p);
     (void)hipDeviceSynchronize();
     for (auto &pl : p->plans) free_plan(pl);
     for (auto &sp : p->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
@@ -4541,6 +4849,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
     for (int i = 0; i < avdsp_hip_prog::kAhead; i++) { if (p->ev_bq[i]) (void)hipEventDestroy(p->ev_bq[i]); if (p->ev_fir[i]) (void)hipEventDestroy(p->ev_fir[i]); }
     (void)hipFree(p->d_buf); (void)hipFree(p->d_in); (void)hipFree(p->d_out); (void)hipFree(p->d_tpdf); (void)hipFree(p->d_frame);
     (void)hipHostFree(p->h_small); (void)hipHostFree(p->h_ready_flag);
+    (void)hipHostFree(p->fs_h); (void)hipFree(p->fs_table);
     for (auto e : p->launch_ev) if (e) (void)hipEventDestroy(e);
     (void)hipFree(p->d_tpdf_seq); (void)hipFree(p->d_ready_timeouts); for (auto &x : p->alias) (void)hipFree(x.buf);
     (void)hipFree(p->d_inst_buf); (void)hipFree(p->d_inst_tpdf); (void)hipFree(p->d_inst_frame); (void)hipFree(p->d_inst_seq);
@@ -4549,6 +4858,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
 
 int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
 {
+    FS_STOP(prog);
     if (d->format < 2 || d->format > 6) return set_err("format %d has no device kernels", d->format);
     Plan pl;
     pl.format = d->format; pl.nchains = d->nchains; pl.store_mask = d->store_mask;
@@ -4797,6 +5107,7 @@ static const size_t kGenericLdsMax = 144 * 1024;     /* bytes */
 
 int avdsp_hip_prog_add_generic(avdsp_hip_prog *prog, const avdsp_generic_desc *d)
 {
+    FS_STOP(prog);
     if (d->format < 2 || d->format > 6) return set_err("format %d is not one of 2..6", d->format);
     if (d->core_word < 0 || d->core_word >= d->prog_words || d->prog_words > prog->total_words || d->io_span < 1 ||
         (d->end_word && (d->end_word <= d->core_word || d->end_word > d->prog_words)))
@@ -4904,6 +5215,7 @@ static int plan_add_strands(avdsp_hip_prog *prog, Plan &pl, const avdsp_strand_d
  * runs through the interpreter as if it had never been asked -- and the caller learns why from the return value and the message. */
 int avdsp_hip_plan_add_strands(avdsp_hip_prog *prog, int plan, const avdsp_strand_desc *d)
 {
+    FS_STOP(prog);
     if (plan < 0 || plan >= (int)prog->plans.size() || !prog->plans[plan].generic) return set_err("strand plan: %d is not a generic plan", plan);
     Plan &pl = prog->plans[plan];
     const int rc = plan_add_strands(prog, pl, d);
@@ -5006,6 +5318,7 @@ static bool strands_take(const Plan &pl, const BlockIO &io)
 
 int avdsp_hip_tpdf_reset(avdsp_hip_prog *prog, int seed, int default_dither)
 {
+    FS_STOP(prog);
     if (!prog->d_tpdf) HIP_TRY(hipMalloc((void **)&prog->d_tpdf, sizeof(TpdfGlobals)));
     hipLaunchKernelGGL(tpdf_init_kernel, dim3(1), dim3(1), 0, nullptr, prog->d_tpdf, seed, default_dither);
     HIP_TRY(hipGetLastError());
@@ -5212,6 +5525,7 @@ static int mirror_to_rings(avdsp_hip_prog *p)
 
 int avdsp_hip_prog_clear_plans(avdsp_hip_prog *p)
 {
+    FS_STOP(p);
     HIP_TRY(hipDeviceSynchronize());
     if (rings_to_mirror(p)) return -1;
     HIP_TRY(hipDeviceSynchronize());
@@ -5222,6 +5536,7 @@ int avdsp_hip_prog_clear_plans(avdsp_hip_prog *p)
 
 int avdsp_hip_upload_words(avdsp_hip_prog *p, const int32_t *host_buf, int first, int n)
 {
+    FS_STOP(p);
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
     if (n && copy_from_caller(p->d_buf + first, host_buf + first, (size_t)n * 4)) return -1;
@@ -5230,6 +5545,7 @@ int avdsp_hip_upload_words(avdsp_hip_prog *p, const int32_t *host_buf, int first
 
 int avdsp_hip_download_words(avdsp_hip_prog *p, int32_t *host_buf, int first, int n)
 {
+    FS_STOP(p);
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
     READY_CHECK(p);                                      /* the state the caller asks for would not be the reference's */
@@ -5241,6 +5557,7 @@ int avdsp_hip_download_words(avdsp_hip_prog *p, int32_t *host_buf, int first, in
 
 int avdsp_hip_zero_words(avdsp_hip_prog *p, int first, int n)
 {
+    FS_STOP(p);
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
     if (n) HIP_TRY(hipMemset(p->d_buf + first, 0, (size_t)n * 4));
@@ -5251,6 +5568,7 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
                         void *d_out, int out_stride, int out_io_base, int nframes,
                         int fir_impl, int biquad_impl, void *stream)
 {
+    FS_STOP(prog);
     if (plan < 0 || plan >= (int)prog->plans.size()) return set_err("bad plan id %d", plan);
     Plan &pl = prog->plans[plan];
     if (nframes <= 0) return 0;
@@ -5436,6 +5754,12 @@ int avdsp_hip_run_block_host(avdsp_hip_prog *prog, int plan, const void *h_in, i
 {
     if (plan < 0 || plan >= (int)prog->plans.size()) return set_err("bad plan id %d", plan);
     Plan &pl = prog->plans[plan];
+    if (in_stride == 0 && out_stride == 0 && nframes == 1) {
+        /* dspRuntime_N through the frame server, where it is on and takes the core (otherwise it is stopped here) */
+        READY_CHECK(prog);
+        const int rc = fs_frame(prog, plan, h_in, h_out);
+        if (rc <= 0) return rc;
+    } else FS_STOP(prog);
     if (in_stride == 0 && out_stride == 0) {
         /* single-frame dspRuntime_N(): both windows are the caller's samples[] array, IO 0 .. span */
         in_stride = out_stride = pl.generic ? pl.io_span : std::max(pl.io_in_max, pl.io_out_max) + 1;
@@ -5567,6 +5891,7 @@ int avdsp_hip_wait_block_host(avdsp_hip_prog *prog, int max_in_flight)
 int avdsp_hip_submit_block_host(avdsp_hip_prog *prog, int plan, const void *h_in, int in_stride, int in_io_base,
                                 void *h_out, int out_stride, int out_io_base, int nframes, int fir_impl, int biquad_impl)
 {
+    FS_STOP(prog);
     if (plan < 0 || plan >= (int)prog->plans.size()) return set_err("bad plan id %d", plan);
     Plan &pl = prog->plans[plan];
     if (pl.generic || nframes < 256 || in_stride <= 0 || out_stride <= 0) {
@@ -5631,6 +5956,7 @@ int avdsp_hip_run_levels(avdsp_hip_prog *prog, const int *plans, const int *leve
                          const void *d_in, int in_stride, int in_io_base, void *d_out, int out_stride, int out_io_base,
                          int nframes, int fir_impl, int biquad_impl, void *stream)
 {
+    FS_STOP(prog);
     hipStream_t main = (hipStream_t)stream;
     int at = 0;
     READY_CHECK(prog);
@@ -5753,6 +6079,7 @@ int avdsp_hip_run_levels(avdsp_hip_prog *prog, const int *plans, const int *leve
  * (their rings and records address the old buffer): the host drops them first.  n <= 1: back to the one copy. */
 int avdsp_hip_chain_instances(avdsp_hip_prog *prog, int n)
 {
+    FS_STOP(prog);
     if (n < 0 || n > 65536) return set_err("instances: 1 .. 65536");
     if (!prog->plans.empty()) return set_err("chain instances: the program's plans must be dropped first");
     if (n <= 1 && prog->chain_inst <= 1) { prog->chain_inst = 0; return 0; }
@@ -5774,6 +6101,7 @@ int avdsp_hip_chain_instances(avdsp_hip_prog *prog, int n)
 
 int avdsp_hip_set_instances(avdsp_hip_prog *prog, int n)
 {
+    FS_STOP(prog);
     if (n < 1 || n > 65536) return set_err("instances: 1 .. 65536");
     HIP_TRY(hipDeviceSynchronize());
     prog->inst_n = n; prog->inst_valid = false;
@@ -5824,6 +6152,7 @@ int avdsp_hip_run_levels_instances(avdsp_hip_prog *prog, const int *plans, const
                                    const void *d_in, int in_stride, int in_io_base, size_t in_inst_words,
                                    void *d_out, int out_stride, int out_io_base, size_t out_inst_words, int nframes, void *stream)
 {
+    FS_STOP(prog);
     hipStream_t main = (hipStream_t)stream;
     const int ninst = prog->inst_n;
     if (nframes < 2 || nframes > kFirChunk * 64) return set_err("instances: blocks of 2 .. %d frames", kFirChunk * 64);
@@ -5912,6 +6241,7 @@ int avdsp_hip_run_levels_instances(avdsp_hip_prog *prog, const int *plans, const
 /* the data area (or any word range) of one instance's mirror, for the host */
 int avdsp_hip_download_instance_words(avdsp_hip_prog *p, int inst, int32_t *host_buf, int first, int n)
 {
+    FS_STOP(p);
     if (inst < 0 || inst >= std::max(p->inst_n, p->chain_inst)) return set_err("instance %d of %d", inst, std::max(p->inst_n, p->chain_inst));
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
@@ -5940,6 +6270,7 @@ int avdsp_hip_run_levels_host(avdsp_hip_prog *prog, const int *plans, const int 
                               const void *h_in, int in_stride, int in_io_base, void *h_out, int out_stride, int out_io_base,
                               int nframes, int fir_impl, int biquad_impl)
 {
+    FS_STOP(prog);
     const size_t in_words = (size_t)nframes * in_stride, out_words = (size_t)nframes * out_stride;
     if (prog->in_cap < in_words) {
         (void)hipFree(prog->d_in); prog->d_in = nullptr; prog->in_cap = 0;
@@ -5960,6 +6291,7 @@ int avdsp_hip_run_levels_host(avdsp_hip_prog *prog, const int *plans, const int 
 
 int avdsp_hip_unpack_pcm(avdsp_hip_prog *prog, int pcm, const void *d_src, void *d_dst, size_t nsamples, void *stream)
 {
+    FS_STOP(prog);
     if (pcm != AVDSP_PCM_S24_3LE && pcm != AVDSP_PCM_S16) return set_err("unpack: PCM kind %d needs no conversion or is unknown", pcm);
     if (reinterpret_cast<size_t>(d_dst) & 15) return set_err("unpack: destination must be 16-byte aligned");
     if (!nsamples) return 0;
@@ -5986,6 +6318,7 @@ int avdsp_hip_run_block_pcm_host(avdsp_hip_prog *prog, int plan, int pcm, const 
                                  void *h_out, int out_stride, int out_io_base, int nframes,
                                  int fir_impl, int biquad_impl)
 {
+    FS_STOP(prog);
     if (plan < 0 || plan >= (int)prog->plans.size()) return set_err("bad plan id %d", plan);
     if (pcm == AVDSP_PCM_S32)
         return avdsp_hip_run_block_host(prog, plan, h_src, in_stride, in_io_base, h_out, out_stride, out_io_base, nframes, fir_impl, biquad_impl);
@@ -6022,6 +6355,7 @@ int avdsp_hip_run_levels_pcm_host(avdsp_hip_prog *prog, const int *plans, const 
                                   const void *h_src, int in_stride, int in_io_base, void *h_out, int out_stride, int out_io_base,
                                   int nframes, int fir_impl, int biquad_impl)
 {
+    FS_STOP(prog);
     if (pcm == AVDSP_PCM_S32)
         return avdsp_hip_run_levels_host(prog, plans, level_size, nlevels, h_src, in_stride, in_io_base, h_out, out_stride,
                                          out_io_base, nframes, fir_impl, biquad_impl);
@@ -6059,6 +6393,7 @@ int avdsp_hip_run_levels_pcm_host(avdsp_hip_prog *prog, const int *plans, const 
 
 int avdsp_hip_tag_output(avdsp_hip_prog *prog, void *d_column, int stride, int nframes, int reset, int reset_value, void *stream)
 {
+    FS_STOP(prog);
     if (!prog->d_tag_prev) {
         HIP_TRY(hipMalloc((void **)&prog->d_tag_prev, sizeof(int)));
         HIP_TRY(hipMemset(prog->d_tag_prev, 0, sizeof(int)));
@@ -6074,6 +6409,7 @@ int avdsp_hip_tag_output(avdsp_hip_prog *prog, void *d_column, int stride, int n
 
 int avdsp_hip_tag_column_host(avdsp_hip_prog *prog, int *h_column, int nframes)
 {
+    FS_STOP(prog);
     int *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, (size_t)nframes * sizeof(int)));
     hipError_t e = hipMemcpy(d, h_column, (size_t)nframes * sizeof(int), hipMemcpyHostToDevice);
@@ -6085,6 +6421,7 @@ int avdsp_hip_tag_column_host(avdsp_hip_prog *prog, int *h_column, int nframes)
 
 int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
 {
+    FS_STOP(prog);
     HIP_TRY(hipDeviceSynchronize());                    /* nothing in flight when the launch arrangement changes */
     switch (key) {
     case AVDSP_OPT_OVERLAP:  prog->overlap = value; for (bool &f : prog->ev_fir_set) f = false; return 0;
@@ -6094,6 +6431,8 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
     case AVDSP_OPT_FIR_LEAN: if (value < -1 || value > 1) return set_err("fir_lean: -1 (auto), 0 or 1"); prog->fir_lean = value; return 0;
     case AVDSP_OPT_RING_WAIT: prog->ring_wait_host = value != 0; return 0;
     case AVDSP_OPT_READY_TEST: prog->ready_test = value > 0 ? value : 0; return 0;
+    case AVDSP_OPT_FRAME_SERVER: prog->fs_on = value != 0; return 0;      /* (the server, if any, was stopped above) */
+    case AVDSP_OPT_FRAME_SERVER_IDLE_US: if (value < 50 || value > 20000) return set_err("frame_server_idle_us: 50 .. 20000"); prog->fs_idle_us = value; return 0;
     case AVDSP_OPT_GROUP_FANOUT: prog->group_fanout = value != 0; return 0;
     case AVDSP_OPT_CU_SPLIT:
         if (value < -128 || value > 128 || (value & 7)) return set_err("cu_split: 0 (off) or 8, 16, ... 128 CUs for the cascades' stream (negative: the FIRs stay on the caller's stream, unmasked)");
@@ -6132,6 +6471,11 @@ int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
     case AVDSP_OPT_SIDE_BY_SIDE: return prog->s_bq ? prog->side_by_side : -1;      /* -1: not probed yet (no overlapped launch so far) */
     case AVDSP_OPT_READY_MODE:   return prog->ready_mode_now;
     case AVDSP_OPT_STREAMS_REMADE: return prog->remade;
+    case AVDSP_OPT_FRAME_SERVER: return prog->fs_on;
+    case AVDSP_OPT_FRAME_SERVER_IDLE_US: return prog->fs_idle_us;
+    case AVDSP_OPT_FRAME_SERVER_FRAMES: return (int)std::min(prog->fs_frames, 0x7FFFFFFFll);
+    case AVDSP_OPT_FRAME_SERVER_LAUNCHES: return (int)std::min(prog->fs_launches, 0x7FFFFFFFll);
+    case AVDSP_OPT_FRAME_SERVER_FALLBACKS: return (int)std::min(prog->fs_fallbacks, 0x7FFFFFFFll);
     }
     return -1;
 }
@@ -6139,6 +6483,7 @@ int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
 /* the caller has heard of the time-outs (dspRuntimeReset; dspRuntimeSetOption("ready_timeouts", 0)): count and mark start again */
 int avdsp_hip_ready_clear(avdsp_hip_prog *prog)
 {
+    FS_STOP(prog);
     if (!prog->d_ready_timeouts) return 0;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemset(prog->d_ready_timeouts, 0, 4));
@@ -6150,6 +6495,7 @@ int avdsp_hip_last_error_is_ready_timeout(void) { return g_err_ready ? 1 : 0; }
 
 int avdsp_hip_ready_timeouts(avdsp_hip_prog *prog)
 {
+    FS_STOP(prog);
     unsigned n = 0;
     if (!prog->d_ready_timeouts) return 0;
     HIP_TRY(hipDeviceSynchronize());

@@ -229,7 +229,12 @@ enum { AVDSP_OPT_OVERLAP = 0, AVDSP_OPT_PROFILE_STRIDE = 1, AVDSP_OPT_FIR_ROWS =
        AVDSP_OPT_CU_SPLIT = 16,     /* experiment: the overlap mode's cascades on that many CUs of their own (CU-masked stream), the FIRs on the others */
        AVDSP_OPT_STREAMS_REMADE = 15, /* read-only: how many times the cascades' stream was made anew because it shared a hardware queue with the FIRs' */
        AVDSP_OPT_READY_MODE = 14,   /* read-only: how the latest overlapped launch's FIR found its cascades' block: 0 event, 1 / 2 ready words */
-       AVDSP_OPT_READY_TEST = 12 /* tests only: that many coming "ready_words" 2 launches never get their words set (their FIR waves time out) */ };
+       AVDSP_OPT_READY_TEST = 12, /* tests only: that many coming "ready_words" 2 launches never get their words set (their FIR waves time out) */
+       AVDSP_OPT_FRAME_SERVER = 18, /* 1: one-frame calls of interpreter cores go to a resident server wave; 0 (default): a launch per call */
+       AVDSP_OPT_FRAME_SERVER_IDLE_US = 19,     /* the server leaves after that many microseconds without a request: 50 .. 20000, default 1000 */
+       AVDSP_OPT_FRAME_SERVER_FRAMES = 20,      /* read-only: core calls the servers answered */
+       AVDSP_OPT_FRAME_SERVER_LAUNCHES = 21,    /* read-only: servers started */
+       AVDSP_OPT_FRAME_SERVER_FALLBACKS = 22    /* read-only: calls whose bounded wait for the server ran out and that went the ordinary way */ };
 /* FIR_LEAN: fir_tile's chunk boundary with a third of the vector instructions: -1 by the plan (default), 0 never, 1 always. */
 /* READY_WORDS (under OVERLAP): how a block's FIR finds its cascades' block in the rings: 0 an event between the two queues, 1 per-chain
  * words published by the cascade's waves (write-through stores) and polled by the FIR's, 2 the words set by a kernel behind the
@@ -245,7 +250,7 @@ enum { AVDSP_OPT_OVERLAP = 0, AVDSP_OPT_PROFILE_STRIDE = 1, AVDSP_OPT_FIR_ROWS =
 /* READY_WORDS 1: under OVERLAP the FIR finds its cascades' blocks through per-chain ready words polled inside the kernel instead of
  * an event between the two queues (0, the default: the event -- the words measured slower on every configuration). */
 int avdsp_hip_chain_instances(avdsp_hip_prog *prog, int n);   /* the mirror n times side by side (no plan may exist); <= 1: one copy again */
-int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key);   /* AVDSP_OPT_SIDE_BY_SIDE, AVDSP_OPT_READY_MODE */
+int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key);   /* AVDSP_OPT_SIDE_BY_SIDE, AVDSP_OPT_READY_MODE, AVDSP_OPT_FRAME_SERVER* */
 int avdsp_hip_ready_clear(avdsp_hip_prog *prog);       /* the caller acknowledges the time-outs: count and sticky mark start again */
 int avdsp_hip_last_error_is_ready_timeout(void);       /* 1: the latest failure of this thread was the sticky ready-word time-out (the host maps it to -11) */
 int avdsp_hip_ready_timeouts(avdsp_hip_prog *prog);    /* waves whose bounded wait for a ready word ran out since the program was loaded (0 unless something is broken) */

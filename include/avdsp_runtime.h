@@ -237,6 +237,12 @@ int dspRuntimeStrandInfo(int format, opcode_t *core, int *strands, int *ops_per_
  * stream of your own with it -- CU-masked streams are blocking streams, beside the null stream every launch on them synchronises.
  * "group_fanout" 1 (default) = a chain core's cascades of up to 16 sections run as ONE launch whatever their lengths, longer ones side by
  * side over up to four streams; 0 = one launch per section count, one after the other (as through round 4; results identical).
+ * "frame_server" 1 (opt-in; default 0, or 1 when the environment holds AVDSP_FRAME_SERVER=1 as the library loads) = dspRuntime_N calls
+ * of interpreter cores go to ONE resident wave per program that keeps the program's state in LDS between frames,
+ * bit-identical to the launch per call; up to three programs of a process have one at a time, everything else takes today's path.
+ * "frame_server_idle_us" (50 .. 20000, default 1000) = the server leaves after that long without a request.  Read-only:
+ * "frame_server_frames" (core calls served), "frame_server_launches" (servers started), "frame_server_fallbacks" (calls whose bounded
+ * wait for the server ran out and that went the ordinary way) -- per device copy of the program, 0 before there is one.
  * A program's options are also the defaults of programs loaded later.                                */
 int dspRuntimeSetOption(const char *key, int value);
 int dspRuntimeGetOption(const char *key);
