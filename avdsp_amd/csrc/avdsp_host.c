@@ -113,11 +113,12 @@ typedef struct avdsp_ctx {
     size_t          chain_inst_in, chain_inst_out;         /* ... these distances between the instances' sample blocks (words) */
     int             chain_inst_win[5];                     /* the windows the cores' IOs were last checked against (format, in base, in stride, out base, out stride); [0] = 0: none */
     int             opt_frame_server, opt_frame_server_idle_us;      /* "frame_server" (AVDSP_OPT_FRAME_SERVER), "frame_server_idle_us" */
+    int             opt_fir_shared;                        /* "fir_shared" (AVDSP_OPT_FIR_SHARED), default 1 */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
 static avdsp_ctx g_template = { .opt_lane_hw = 1, .opt_ring_wait = 1, .opt_ready_words = -1, .opt_fir_impl = 1, .opt_biquad_impl = 1, .opt_device = -1, .opt_interp_impl = 1, .opt_strand_split = 1, .opt_strand_lanes = 1, .shard_world = 1,
-                                .mantissa = DSP_MANT, .device_ordinal = -1, .opt_frame_server_idle_us = 1000 };
+                                .mantissa = DSP_MANT, .device_ordinal = -1, .opt_frame_server_idle_us = 1000, .opt_fir_shared = 1 };
 
 /* A host written for the reference cannot call dspRuntimeSetOption: AVDSP_FRAME_SERVER=1 in the environment makes "frame_server" 1 the
  * default (read once, when the library is loaded) */
@@ -295,6 +296,13 @@ static int set_option_here(const char *key, int value)
         G.opt_fir_lean = value; G.opt_fir_lean_set = 1;
         return 0;
     }
+    if (!strcmp(key, "fir_shared")) {                    /* chains of one impulse bank on fir_shared; 0: every chain as before */
+        if (value != 0 && value != 1) return fail(-1, "fir_shared: 0 or 1");
+        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SHARED, value)) return hip_fail();
+        G.opt_fir_shared = value;
+        return 0;
+    }
+    if (!strcmp(key, "fir_shared_chains") || !strcmp(key, "fir_shared_groups")) return fail(-1, "%s is read-only", key);
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -385,6 +393,9 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_launch"))  return G.opt_fir_launch_set ? G.opt_fir_launch : -1;
     if (!strcmp(key, "fir_lean"))    return G.opt_fir_lean_set ? G.opt_fir_lean : -1;
     if (!strcmp(key, "ring_wait"))   return G.opt_ring_wait;
+    if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
+    if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
+    if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strncmp(key, "timing_pairs_", 13) && key[13] >= '0' && key[13] <= '7' && !key[14])      /* of the latest dspRuntimeKernelTime(kind) */
         return G.dev ? avdsp_hip_profile_last_pairs(G.dev, key[13] - '0') : 0;
     if (!strcmp(key, "ready_timeouts")) { device_current(); return G.dev ? avdsp_hip_ready_timeouts(G.dev) : 0; }
@@ -521,7 +532,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -1307,11 +1318,59 @@ static int ensure_device(void)
         (G.opt_cu_split && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_CU_SPLIT, G.opt_cu_split)) ||
         (G.opt_group_serial && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_GROUP_FANOUT, 0)) ||
         (G.opt_frame_server && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER, 1)) ||
+        (!G.opt_fir_shared && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SHARED, 0)) ||
         (G.opt_frame_server_idle_us != 1000 && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER_IDLE_US, G.opt_frame_server_idle_us)) ||
         (G.ninst > 1 && avdsp_hip_set_instances(G.dev, G.ninst))) {
         hip_fail(); drop_device(); return g_err_code;
     }
     return 0;
+}
+
+/* The shared-impulse FIR path: the chains of a plan whose DSP_FIR points at one impulse bank at the current rate --
+ * same first tap word, same length -- grouped, groups of AVDSP_FIR_GROUP_MIN chains or more, in the order of their first chain; a group
+ * lists its chains in plan order.  Returns the number of groups (start / members: malloc'ed, NULL when 0) or -1 (out of memory). */
+static const avdsp_chain *g_fg_chains;
+static int fir_group_cmp(const void *pa, const void *pb)
+{
+    const avdsp_chain *a = &g_fg_chains[*(const int32_t *)pa], *b = &g_fg_chains[*(const int32_t *)pb];
+    if (a->fir_coef_word != b->fir_coef_word) return a->fir_coef_word < b->fir_coef_word ? -1 : 1;
+    if (a->fir_taps != b->fir_taps) return a->fir_taps < b->fir_taps ? -1 : 1;
+    return *(const int32_t *)pa < *(const int32_t *)pb ? -1 : *(const int32_t *)pa > *(const int32_t *)pb;
+}
+static int fir_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **members)
+{
+    *start = 0; *members = 0;
+    int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
+    int32_t *mem = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+    int32_t *first = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
+    int32_t *len = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
+    if (!idx || !st || !mem || !first || !len) { free(idx); free(st); free(mem); free(first); free(len); return -1; }
+    int m = 0;
+    for (int i = 0; i < n; i++) if (ch[i].fir_taps > 0) idx[m++] = i;
+    g_fg_chains = ch;
+    qsort(idx, (size_t)m, sizeof(int32_t), fir_group_cmp);
+    int ng = 0;
+    for (int b = 0, e; b < m; b = e) {                   /* runs of one bank; a run is in plan order */
+        for (e = b + 1; e < m && ch[idx[e]].fir_coef_word == ch[idx[b]].fir_coef_word && ch[idx[e]].fir_taps == ch[idx[b]].fir_taps; e++) {}
+        if (e - b >= AVDSP_FIR_GROUP_MIN) { first[ng] = b; len[ng] = e - b; ng++; }
+    }
+    /* the groups in the order of their first chains (small: insertion sort) */
+    for (int g = 1; g < ng; g++)
+        for (int h = g; h > 0 && idx[first[h]] < idx[first[h - 1]]; h--) {
+            int32_t t = first[h]; first[h] = first[h - 1]; first[h - 1] = t;
+            t = len[h]; len[h] = len[h - 1]; len[h - 1] = t;
+        }
+    int k = 0;
+    for (int g = 0; g < ng; g++) {
+        st[g] = k;
+        for (int j = 0; j < len[g]; j++) mem[k++] = idx[first[g] + j];
+    }
+    st[ng] = k;
+    free(idx); free(first); free(len);
+    if (!ng) { free(st); free(mem); return 0; }
+    *start = st; *members = mem;
+    return ng;
 }
 
 static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
@@ -1387,6 +1446,12 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.nchains = hi - lo; d.chains = L.chains + lo;
         d.nsections = sec1 - sec0; d.sec_coef_word = L.coef_word + sec0; d.sec_state_word = L.state_word + sec0;
         d.store_mask = G.store_mask;
+        int32_t *fg_start = 0, *fg_chains = 0;
+        if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
+            const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
+            if (ng < 0) { lowered_free(&L); fail(-9, "out of memory"); return 0; }
+            d.fir_ngroups = ng; d.fir_group_start = fg_start; d.fir_group_chains = fg_chains;
+        }
         /* Instances of a chain core (round 5): the chain list ninst times -- copy i of a chain reads and writes copy i of the mirror
          * (every word index + i * total words: its own state, FIR history and parameters) and block i of the callers' samples (IO
          * numbers + i * the blocks' distance: the kernels form `column = IO - window base`, which then lands in block i).  To the
@@ -1417,7 +1482,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
             d.instances = N;
         }
         cp->plan_id = avdsp_hip_prog_add_plan(G.dev, &d);
-        free(xch); free(xco); free(xst);
+        free(xch); free(xco); free(xst); free(fg_start); free(fg_chains);
         for (int i = lo; i < hi; i++) {
             if (L.chains[i].nsec > cp->max_sections) cp->max_sections = L.chains[i].nsec;
             if (L.chains[i].fir_taps > cp->max_taps) cp->max_taps = L.chains[i].fir_taps;
@@ -1475,6 +1540,42 @@ int dspRuntimeCoreInfo(int format, opcode_t *core, int *nchains, int *max_sectio
     if (nchains) *nchains = nc;
     if (max_sections) *max_sections = ms;
     if (max_taps) *max_taps = mt;
+    return 0;
+}
+
+/* Host-only: the groups of AVDSP_FIR_GROUP_MIN chains or more that share one impulse bank at the current rate, among the chains of the
+ * core this process runs (dspRuntimeSetShard) -- what fir_shared takes.  No device is touched.  A core that is not a set
+ * of chains, or a format without the chain FIR (2, 3, 5), has none. */
+int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped_chains, int *largest_group)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int ng = 0, nc = 0, big = 0;
+    if (!G.opt_generic && (format == 4 || format == 6)) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0) {
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            int32_t *st = 0, *mem = 0;
+            ng = fir_groups(L.chains + lo, hi - lo, &st, &mem);
+            if (ng < 0) { lowered_free(&L); return fail(-9, "out of memory"); }
+            for (int g = 0; g < ng; g++) {
+                const int n = st[g + 1] - st[g];
+                nc += n;
+                if (n > big) big = n;
+            }
+            free(st); free(mem);
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (groups) *groups = ng;
+    if (grouped_chains) *grouped_chains = nc;
+    if (largest_group) *largest_group = big;
     return 0;
 }
 

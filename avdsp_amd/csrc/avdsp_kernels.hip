@@ -2257,6 +2257,184 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
 
 
 /* ------------------------------------------------------------------------------------------
+ * fir_shared<FMT, R>: fir_tile's contraction for chains that share ONE impulse bank -- the 16 columns of the
+ * tile are 16 chains of one group instead of 16 frame groups of one chain:
+ *
+ *   y_c[F0 + 16 r + i] = sum_m A_r[i][m] * B[m][c],   A_r[i][m] = h[m + 16 r + i],   B[m][c] = x_{chain(c)}[F0 - m]
+ *   c = 0 .. 15 (chains of one group), i = 0 .. 15, r = 0 .. R-1 (row tiles, one accumulator each), m = -16R .. T-1 in k-steps
+ *   of 4, ascending: every accumulator is the reference's sequential sum, bit for bit, by fir_tile's argument.
+ *
+ * A workgroup is one column group (16 chains) over 64 R frames: its four waves are four row-tile groups of 16 R frames each.
+ * Both operand images are the workgroup's: the taps image (A_r, fir_tile's layout, one f64 row per GROUP, copied by LDS-DMA a
+ * chunk ahead into the other of two images) and the window image (the 16 chains' samples over the 4 CK + 48 R frames that the
+ * four waves' k-steps of a chunk read, converted while staged).  The window image is [chain][frame] with CP = 2 (mod 32) doubles
+ * per chain: a k-step's B read (16 chains x 2 k per half wave) and the staging writes (64 consecutive frames of one chain) are
+ * both free of bank conflicts.
+ * ---------------------------------------------------------------------------------------- */
+template <int R> struct SharedGeom {
+    static constexpr int CK = 64;                            /* k-steps per chunk (multiple of 16) */
+    static constexpr int FW = 64 * R;                        /* frames per workgroup: four waves of R row tiles */
+    static constexpr int NU = 4 * CK + 48 * R;               /* window frames a chunk's k-steps read, over the four waves */
+    static constexpr int CP = (NU - 2 + 31) / 32 * 32 + 2;   /* doubles per chain in the window image, = 2 (mod 32) */
+    static constexpr int HNEED = 4 * CK + 16 * R;            /* doubles of a chunk's taps image */
+    static constexpr int HLEN = (HNEED + 127) / 128 * 128;   /* ... in whole 1-KiB pieces of the LDS-DMA */
+    static constexpr int NWR = (NU + 63) / 64;               /* window samples a lane stages per chain and chunk */
+    static constexpr int LDS_DOUBLES = 2 * HLEN + 16 * CP;   /* per workgroup: two taps images, one window image */
+};
+static_assert(SharedGeom<1>::LDS_DOUBLES * 8 <= 64 * 1024 && SharedGeom<2>::LDS_DOUBLES * 8 <= 64 * 1024 &&
+              SharedGeom<4>::LDS_DOUBLES * 8 <= 64 * 1024, "two fir_shared workgroups per CU");
+static_assert(SharedGeom<4>::HLEN / 128 <= 4, "one taps piece per wave");
+
+/* a column group: chains ids[first .. first + n) (n <= 16) of group `group` (its taps row) */
+struct SharedTile { int group, first, n, taps; };
+struct FirSharedArgs {
+    int *buf; const avdsp_chain *chains; const int *ids; const SharedTile *tiles; int ntiles; int nfb; Ring ring; int per_xcd;
+    const double *taps64; int pitch64;       /* f64 copy of the groups' taps, [group][pitch64] (taps64_pitch) */
+    BlockIO io;
+};
+
+template <int FMT, int R>
+__global__ __launch_bounds__(kBlock, 2) void fir_shared(const FirSharedArgs a)
+{
+    using G = SharedGeom<R>;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    flush_f32_subnormals_like_the_reference();            /* (the window's conversions read a subnormal as a signed zero: mulop) */
+    const int L = xcd_remap(blockIdx.x, a.per_xcd);      /* (the frame blocks of one column group share an XCD: their windows overlap) */
+    if (L >= a.ntiles * a.nfb) return;                   /* (the whole workgroup) */
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int B = a.io.nframes;
+    const SharedTile tile = a.tiles[L / a.nfb];
+    const int F0 = (L % a.nfb) * G::FW, F0w = F0 + 16 * R * wv;
+    const int T = tile.taps;
+    double *hs = lds, *ws = lds + 2 * G::HLEN;           /* taps images at hs and hs + HLEN, the window image [16][CP] behind them */
+    const double *hbuf = a.taps64 + (size_t)tile.group * a.pitch64;
+    const int rmask = a.ring.R - 1;
+
+    /* the chains this lane stages: c = wv + 4 q (q = 0 .. 3), frames lane + 64 p of the chunk's window; a column without a chain reads zeros */
+    const char *srow[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int c = wv + 4 * q;
+        srow[q] = c < tile.n ? reinterpret_cast<const char *>(ring_row(a.ring, a.ids[tile.first + c])) : nullptr;
+    }
+    const int i16 = lane & 15, k = lane >> 4;
+    const bool col = i16 < tile.n;                        /* the lane's output column holds a chain */
+    const int my_cid = col ? a.ids[tile.first + i16] : -1;
+
+    constexpr int NR = 16 * R;
+    const int S = (((T + NR + 3) >> 2) + 15) & ~15;     /* k-steps m_s = -16R + 4 s, s = 0 .. S-1 */
+    float wreg[4][G::NWR];
+    /* frame of window row u in a chunk of ckc k-steps from s0: F0 - m0 - 4 ckc + 1 + u, m0 = -16R + 4 s0 (the ring holds every sample
+     * twice, so one masked offset per lane and chain and immediates behind it) */
+    auto win_fetch = [&](int s0, int ckc) {
+        const unsigned b0 = (unsigned)(a.ring.wpos + F0 + NR - 4 * s0 - 4 * ckc + 1 + lane) << 2;
+        const unsigned off = b0 & ((unsigned)rmask << 2);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int p = 0; p < G::NWR; p++)
+                wreg[q][p] = srow[q] ? *reinterpret_cast<const float *>(srow[q] + off + 256 * p) : 0.0f;
+    };
+    auto win_store = [&]() {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int p = 0; p < G::NWR; p++)
+                if (64 * p + 63 < G::NU || lane + 64 * p < G::NU) ws[(wv + 4 * q) * G::CP + lane + 64 * p] = (double)wreg[q][p];
+    };
+    /* the taps image of a chunk: u = 0 .. 4 ckc + 16 R - 1 <- Hbuf[kTapsLead - 16 R + 4 s0 + u], by LDS-DMA (fir_tile's dma16: a scalar
+     * base, the lane's offset, the LDS address in M0); wave t copies piece t, lanes past the chunk's need re-read its last 16 bytes */
+    const unsigned hs_addr = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char *)hs);
+    auto taps_dma = [&](int which, int s0, int ckc) {
+        if (64 * wv * 2 >= 4 * ckc + 16 * R) return;
+        const unsigned long long sv = reinterpret_cast<unsigned long long>(hbuf + (kTapsLead - 16 * R) + 4 * s0);
+        const char *src = reinterpret_cast<const char *>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(sv >> 32)) << 32) |
+                                                         (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)sv));
+        const int np = (4 * ckc + 16 * R) / 2;           /* 16-byte pieces the chunk needs */
+        const int pi = min(64 * wv + lane, np - 1);
+        const unsigned dst = __builtin_amdgcn_readfirstlane(hs_addr + (unsigned)which * (unsigned)(G::HLEN * 8) + 1024u * (unsigned)wv);
+        unsigned keep;
+        asm volatile("s_mov_b32 %[k], m0\n\t"
+                     "s_mov_b32 m0, %[d]\n\t"
+                     "s_nop 0\n\t"
+                     "global_load_lds_dwordx4 %[v], %[s]\n\t"
+                     "s_mov_b32 m0, %[k]"
+                     : [k] "=&s"(keep) : [v] "v"((unsigned)pi * 16u), [s] "s"(src), [d] "s"(dst) : "memory");
+    };
+
+    v4f64 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = v4f64{0.0, 0.0, 0.0, 0.0};
+    const bool active = F0w < B;                          /* (a wave past the block stages and attends the barriers, nothing more) */
+
+    win_fetch(0, min(G::CK, S));
+    taps_dma(0, 0, min(G::CK, S));
+    int cur = 0;
+    for (int s0 = 0; s0 < S; s0 += G::CK, cur ^= 1) {
+        const int ckc = min(G::CK, S - s0);
+        __syncthreads();                                  /* every wave is through the previous chunk's k-steps */
+        win_store();                                      /* (waits for the samples requested a chunk ago) */
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* ... and for this wave's piece of this chunk's taps image */
+        __syncthreads();
+        if (s0 + ckc < S) {
+            win_fetch(s0 + ckc, min(G::CK, S - s0 - ckc));
+            taps_dma(cur ^ 1, s0 + ckc, min(G::CK, S - s0 - ckc));
+        }
+        if (active) {
+            const double *hp = hs + cur * G::HLEN + k + i16;                        /* A_r of step j: hp[4 j + 16 r] */
+            const double *wp = ws + i16 * G::CP + 16 * R * wv + 4 * ckc - 1 - k;     /* B of step j: wp[-4 j] */
+            for (int g = 0; g < ckc / 16; g++) {
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const double b = wp[-4 * (16 * g + j)];
+#pragma unroll
+                    for (int r = 0; r < R; r++)
+                        acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(hp[4 * (16 * g + j) + 16 * r], b, acc[r], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (!active || !col) return;
+    /* C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15 (the chain), row = (lane >> 4) + 4 * reg (the frame) */
+    const avdsp_chain c = a.chains[my_cid];
+    /* Inf / NaN among a column's samples make its sums non-finite (Inf x 0 is a NaN; the reference reads exponent 255 as 2^128 x 1.m):
+     * such an output is summed again tap by tap with the reference's operands (fir_tile's LEAN look, per output) */
+    bool odd = false;
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+            odd |= F0w + 16 * r + 4 * v + k < B && ((unsigned long long)__double_as_longlong(acc[r][v]) >> 52 & 0x7FF) == 0x7FF;
+    if (__builtin_expect(__ballot(odd) != 0, 0)) {
+        const float *ftaps = reinterpret_cast<const float *>(a.buf + c.fir_coef_word);
+        const float *ringrow = ring_row(a.ring, my_cid);
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const int n = F0w + 16 * r + 4 * v + k;
+                if (n < B && ((unsigned long long)__double_as_longlong(acc[r][v]) >> 52 & 0x7FF) == 0x7FF) {
+                    double sum = 0.0;
+                    for (int tp = 0; tp < T; tp++)
+                        sum = __builtin_fma(mulop(ringrow[(a.ring.wpos + n - tp) & rmask]), mulop(ftaps[tp]), sum);
+                    acc[r][v] = sum;
+                }
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const int n = F0w + 16 * r + 4 * v + k;
+            if (n < B) {
+                unsigned word = store_stage<FMT>(acc[r][v], c.sat, a.io.store_mask);
+                if constexpr (FMT == 6) word = ftz_bits(word);      /* (as fir_tile) */
+                emit_out(a.io, c, n, word);
+            }
+        }
+}
+
+/* ------------------------------------------------------------------------------------------
  * fir_stream<FMT, R>: fir_tile's contraction (same tile, same operand order, same accumulators: see there) with NO
  * instruction work at the chunk boundaries.
  *
@@ -2781,13 +2959,13 @@ __global__ __launch_bounds__(kBlock) void fir_feed(const FirTileArgs a)
 }
 
 /* the f64 copy of a chain's taps, made once per plan: Hbuf[j] = mulop(h[j - kTapsLead]), zeros around */
-struct Taps64Args { const int *buf; const avdsp_chain *chains; const int *group; double *taps64; int pitch64; };
+struct Taps64Args { const int *buf; const avdsp_chain *chains; const int *group; double *taps64; int pitch64; int by_index; };
 __global__ __launch_bounds__(kBlock) void taps_to_f64(const Taps64Args a)
 {
     const int cid = a.group[blockIdx.x];
     const avdsp_chain c = a.chains[cid];
     const float *taps = reinterpret_cast<const float *>(a.buf + c.fir_coef_word);
-    double *dst = a.taps64 + (size_t)cid * a.pitch64;
+    double *dst = a.taps64 + (size_t)(a.by_index ? (int)blockIdx.x : cid) * a.pitch64;     /* (by_index: fir_shared's row per group) */
     for (int j = threadIdx.x; j < a.pitch64; j += blockDim.x) {
         const int t = j - kTapsLead;
         dst[j] = (t >= 0 && t < c.fir_taps) ? mulop(taps[t]) : 0.0;
@@ -3688,7 +3866,15 @@ struct Plan {
     int io_in_min = 0, io_in_max = -1, io_out_min = 0, io_out_max = -1;
     bool wave_ok = false; unsigned carried_io[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* frame-parallel interpreter */
     int *d_own = nullptr;                                /* owned mirror ranges (pairs), generic plans */
-    double *d_taps64 = nullptr; int pitch64 = 0;         /* fir_tile: the taps as doubles, [chain][pitch64] */
+    double *d_taps64 = nullptr; int pitch64 = 0;         /* fir_tile: the taps as doubles, [chain][pitch64] (a plan whose FIR chains are all
+                                                            grouped makes it when a launch first needs it: ensure_private_taps) */
+    /* fir_shared: FIR chains grouped by impulse bank (avdsp_plan_desc::fir_group_*), groups of AVDSP_FIR_GROUP_MIN or more */
+    int n_sh_groups = 0, n_sh_chains = 0;
+    int *d_sh_ids = nullptr;                             /* the grouped chains, group by group */
+    SharedTile *d_sh_tiles = nullptr; int n_sh_tiles = 0;     /* column groups of <= 16 chains of one group */
+    double *d_sh_taps64 = nullptr;                       /* the taps as doubles, [group][pitch64] */
+    int *d_sh_feed = nullptr; int n_sh_feed = 0;         /* grouped chains without a cascade in front (fir_feed appends their input) */
+    int *d_fir_rest = nullptr; int n_fir_rest = 0;       /* the FIR chains in no group: fir_tile beside fir_shared */
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
     int *d_lane_rows = nullptr; int n_lane_rows = 0;     /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
@@ -3748,6 +3934,8 @@ struct avdsp_hip_prog {
     int fir_rows = 0;                    /* fir_tile: row tiles per wave (1, 2, 4), 0 = by the number of chains */
     int fir_lean = -1;                   /* fir_tile's lean chunk boundary: -1 by the plan (launch_fir), 0 never, 1 always */
     int fir_split = 0;                   /* fir_tile: launches of at most a tile per SIMD cut every tile's taps over two waves (sums within 1e-6, not the reference's bits) */
+    int fir_shared = 1;                  /* chains of one impulse bank as the columns of fir_shared; 0: every chain on fir_launch's kernels */
+    int sh_chains_now = 0, sh_groups_now = 0;        /* of the latest FIR launch: chains and groups fir_shared took */
     hipStream_t s_bq = nullptr;
     hipStream_t s_fir[2] = {nullptr, nullptr};           /* "overlap" 2: the FIRs of consecutive blocks in turn */
     static constexpr int kAhead = 3;     /* cascade k waits for FIR k - kAhead: it may run under FIR k - 2 and be done before FIR k - 1 ends */
@@ -3936,6 +4124,7 @@ void free_plan(Plan &p)
     (void)hipFree(p.d_sops); (void)hipFree(p.d_sargs); (void)hipFree(p.d_lseq); (void)hipFree(p.d_lane_rows);
     (void)hipFree(p.d_fir_ids); (void)hipFree(p.d_pass_ids); (void)hipFree(p.d_ring); (void)hipFree(p.d_ring64); (void)hipFree(p.d_own); (void)hipFree(p.d_taps64);
     (void)hipFree(p.d_ready);
+    (void)hipFree(p.d_sh_ids); (void)hipFree(p.d_sh_tiles); (void)hipFree(p.d_sh_taps64); (void)hipFree(p.d_sh_feed); (void)hipFree(p.d_fir_rest);
 }
 
 int fir_groups_per_chunk(int max_taps)
@@ -4203,6 +4392,75 @@ int launch_fir_flow(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, Block
     return launch_timed(scope, (const void *)fir_flow<FMT, R, BIG>, dim3(a.per_xcd * 8), dim3(kBlock), lds, stream, a, stop);
 }
 
+/* The per-chain f64 taps of a plan whose FIR chains are all grouped are made when a launch first needs them (a fallback of the shared
+ * path: "fir_shared" 0, the overlap modes, "fir_split", fir_impl other than 1) -- on the launch's stream, ahead of it */
+int ensure_private_taps(avdsp_hip_prog *prog, Plan &pl, hipStream_t stream)
+{
+    if (pl.d_taps64 || !pl.n_fir) return 0;
+    HIP_TRY(hipMalloc((void **)&pl.d_taps64, (size_t)pl.nchains * pl.pitch64 * sizeof(double)));
+    Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};
+    hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, stream, ta);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* the shared path takes a launch's groups only with fir_impl 1, no overlap mode, no tap split, no chain instances */
+bool shared_path(const avdsp_hip_prog *prog, const Plan &pl, int fir_impl)
+{
+    return pl.n_sh_groups > 0 && prog->fir_shared && fir_impl == 1 && !prog->overlap && !prog->fir_split && pl.instances <= 1;
+}
+
+/* fir_shared over every group of the plan: R by launch_fir's cost rule on this kernel's waves, ceil(C / 16) x ceil(B / 16 R) */
+template <int FMT, int R>
+int launch_fir_shared_r(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream, ProfileScope &scope)
+{
+    FirSharedArgs a{};
+    a.buf = prog->d_buf; a.chains = pl.d_chains; a.ids = pl.d_sh_ids; a.tiles = pl.d_sh_tiles; a.ntiles = pl.n_sh_tiles;
+    a.nfb = (io.nframes + SharedGeom<R>::FW - 1) / SharedGeom<R>::FW;
+    a.ring = plan_ring(pl); a.taps64 = pl.d_sh_taps64; a.pitch64 = pl.pitch64; a.io = io;
+    const long long nwg = (long long)a.ntiles * a.nfb;
+    a.per_xcd = (int)((nwg + 7) / 8);
+    return launch_timed(scope, (const void *)fir_shared<FMT, R>, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)SharedGeom<R>::LDS_DOUBLES * sizeof(double), stream, a);
+}
+
+template <int FMT>
+int launch_fir_shared(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
+{
+    if constexpr (FMT != 4 && FMT != 6) { (void)prog; (void)pl; (void)io; (void)stream; return set_err("fir_shared: formats 4 and 6 only"); }
+    else {
+        if (pl.n_sh_feed) {                               /* grouped chains without a cascade: their input into the rings first (a chain's frames span workgroups) */
+            FirTileArgs f{};
+            f.buf = prog->d_buf; f.chains = pl.d_chains; f.group = pl.d_sh_feed; f.ngroup = pl.n_sh_feed; f.ring = plan_ring(pl); f.io = io;
+            const long long total = (long long)pl.n_sh_feed * io.nframes;
+            hipLaunchKernelGGL(fir_feed<FMT>, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, stream, f);
+            HIP_TRY(hipGetLastError());
+        }
+        ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
+        int rows = prog->fir_rows;
+        if (rows != 1 && rows != 2 && rows != 4) {
+            /* (launch_fir's rule: the chip holds 2048 such waves at a time -- two 64-KB workgroups per CU --, a wave of R row tiles lasts R
+             * units, the launch is over when its last round is; 0.90 / 0.84 / 0.79 of the pipe at 4 / 2 / 1 row tiles) */
+            double best = 1e30;
+            rows = 1;
+            for (int r : {4, 2, 1}) {
+                if (r > 1 && 32 * r >= io.nframes) continue;               /* a workgroup of twice the block would multiply zeros */
+                const long long waves = (long long)pl.n_sh_tiles * 4 * ((io.nframes + 64 * r - 1) / (64 * r));
+                const double cost = (double)((waves + 2047) / 2048) * r / (r == 4 ? 0.90 : r == 2 ? 0.84 : 0.79);
+                if (cost < best - 1e-9) { best = cost; rows = r; }
+            }
+        }
+        while (rows > 1 && 32 * rows >= io.nframes) rows >>= 1;
+        if constexpr (FMT == 4) {
+            /* (format 4 stops at two row tiles: with four, store_word_f4's epilogue takes the kernel to 256 VGPRs and spills) */
+            return rows >= 2 ? launch_fir_shared_r<FMT, 2>(prog, pl, io, stream, scope) : launch_fir_shared_r<FMT, 1>(prog, pl, io, stream, scope);
+        } else {
+            return rows == 4 ? launch_fir_shared_r<FMT, 4>(prog, pl, io, stream, scope)
+                 : rows == 2 ? launch_fir_shared_r<FMT, 2>(prog, pl, io, stream, scope)
+                             : launch_fir_shared_r<FMT, 1>(prog, pl, io, stream, scope);
+        }
+    }
+}
+
 /* fir_impl: 0 = fir_plain (the reference's loop), 1 = fir_tile (default), 2 = fir_mfma (round 1's workgroup-per-channel kernel),
  * 3 = fir_stream, 4 = fir_flow */
 template <int FMT>
@@ -4210,6 +4468,7 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
 {
     if constexpr (FMT == 2) { (void)prog; (void)pl; (void)ids; (void)n; (void)io; (void)fir_impl; (void)stream; (void)wait_ready; (void)stop; return 0; }
     else {
+        if (ensure_private_taps(prog, pl, stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
         if (fir_impl == 4) {
             int rows = prog->fir_rows;
@@ -4479,6 +4738,7 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
     const bool under = prog->overlap && pl.overlap_ok && biquad_impl && fir_impl;
     pl.seq++;                                             /* this launch's number in the plan's ready words */
     if (under) {
+        prog->sh_chains_now = prog->sh_groups_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
         if (overlap_ready(prog)) return -1;
         const bool own_fir = prog->overlap >= 2 || prog->cu_split > 0;      /* the FIRs on a stream of the library's own */
         if (probe_side_by_side(prog, prog->overlap >= 2 ? prog->s_fir[prog->blk & 1] : prog->cu_split > 0 ? prog->s_fir[0] : stream)) return -1;     /* (remembered per stream) */
@@ -4565,7 +4825,15 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         prog->blk++;
     } else {
         if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false)) return -1;
-        if (pl.n_fir && launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, stream)) return -1;
+        if (pl.n_fir && shared_path(prog, pl, fir_impl)) {
+            /* chains of one bank on fir_shared, the others on fir_tile as ever: two launches on the stream */
+            if (pl.n_fir_rest && launch_fir<FMT>(prog, pl, pl.d_fir_rest, pl.n_fir_rest, io, fir_impl, stream)) return -1;
+            if (launch_fir_shared<FMT>(prog, pl, io, stream)) return -1;
+            prog->sh_chains_now = pl.n_sh_chains; prog->sh_groups_now = pl.n_sh_groups;
+        } else if (pl.n_fir) {
+            if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, stream)) return -1;
+            prog->sh_chains_now = prog->sh_groups_now = 0;
+        }
     }
     if (pl.n_pass) {
         ProfileScope scope(prog, stream, AVDSP_KERNEL_PASS); scope.begin();
@@ -5074,11 +5342,60 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
                 if (e2 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_tile LDS %d): %s", tlds[v], hipGetErrorString(e2)); }
             }
             pl.pitch64 = taps64_pitch(pl.max_taps);
-            hipError_t e2 = hipMalloc((void **)&pl.d_taps64, (size_t)d->nchains * pl.pitch64 * sizeof(double));
-            if (e2 != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 taps, %d x %d): %s", d->nchains, pl.pitch64, hipGetErrorString(e2)); }
-            Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64};
-            hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ta);
-            if (hipGetLastError() != hipSuccess) { free_plan(pl); return set_err("taps_to_f64 failed to launch"); }
+            /* fir_shared: the host's groups of chains on one impulse bank -- a taps row per group, column groups of <= 16 chains */
+            if (d->fir_ngroups > 0 && d->fir_group_start && d->fir_group_chains && pl.instances <= 1 && (d->format == 4 || d->format == 6)) {
+                std::vector<int> sh_ids, feed, rest, reps;
+                std::vector<SharedTile> tiles;
+                std::vector<char> in_group(d->nchains, 0);
+                for (int g = 0; g < d->fir_ngroups; g++) {
+                    const int b = d->fir_group_start[g], e = d->fir_group_start[g + 1];
+                    if (b < 0 || e < b || e - b < AVDSP_FIR_GROUP_MIN) { free_plan(pl); return set_err("FIR group %d: %d chains", g, e - b); }
+                    const int c0 = d->fir_group_chains[b];
+                    for (int j = b; j < e; j++) {
+                        const int ci = d->fir_group_chains[j];
+                        if (ci < 0 || ci >= d->nchains || in_group[ci] || !chains[ci].fir_taps || chains[ci].fir_taps != chains[c0].fir_taps ||
+                            chains[ci].fir_coef_word != chains[c0].fir_coef_word) { free_plan(pl); return set_err("FIR group %d: chain %d is not one of its bank", g, ci); }
+                        in_group[ci] = 1;
+                        if (!chains[ci].nsec) feed.push_back(ci);
+                    }
+                    const int gi = (int)reps.size();
+                    reps.push_back(c0);
+                    for (int j = b; j < e; j += 16)
+                        tiles.push_back(SharedTile{gi, (int)sh_ids.size() + (j - b), std::min(16, e - j), chains[c0].fir_taps});
+                    sh_ids.insert(sh_ids.end(), d->fir_group_chains + b, d->fir_group_chains + e);
+                }
+                for (int ci : fir) if (!in_group[ci]) rest.push_back(ci);
+                pl.n_sh_groups = (int)reps.size(); pl.n_sh_chains = (int)sh_ids.size(); pl.n_sh_tiles = (int)tiles.size();
+                pl.n_sh_feed = (int)feed.size(); pl.n_fir_rest = (int)rest.size();
+                if (upload_vec(&pl.d_sh_ids, sh_ids) || upload_vec(&pl.d_sh_tiles, tiles) || upload_vec(&pl.d_sh_feed, feed) ||
+                    upload_vec(&pl.d_fir_rest, rest)) { free_plan(pl); return -1; }
+                int *d_reps = nullptr;
+                hipError_t e4 = hipMalloc((void **)&pl.d_sh_taps64, (size_t)pl.n_sh_groups * pl.pitch64 * sizeof(double));
+                if (e4 != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 taps of %d groups): %s", pl.n_sh_groups, hipGetErrorString(e4)); }
+                if (upload_vec(&d_reps, reps)) { free_plan(pl); return -1; }
+                Taps64Args tg{prog->d_buf, pl.d_chains, d_reps, pl.d_sh_taps64, pl.pitch64, 1};
+                hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_sh_groups), dim3(kBlock), 0, nullptr, tg);
+                const bool launched = hipGetLastError() == hipSuccess;
+                (void)hipDeviceSynchronize();
+                (void)hipFree(d_reps);
+                if (!launched) { free_plan(pl); return set_err("taps_to_f64 (groups) failed to launch"); }
+                const void *sfn[3] = { d->format == 4 ? (const void *)fir_shared<4, 1> : (const void *)fir_shared<6, 1>,
+                                       d->format == 4 ? (const void *)fir_shared<4, 2> : (const void *)fir_shared<6, 2>,
+                                       (const void *)fir_shared<6, 4> };
+                const int slds[3] = { SharedGeom<1>::LDS_DOUBLES * 8, SharedGeom<2>::LDS_DOUBLES * 8, SharedGeom<4>::LDS_DOUBLES * 8 };
+                for (int v = 0; v < (d->format == 4 ? 2 : 3); v++) {
+                    hipError_t e5 = hipFuncSetAttribute(sfn[v], hipFuncAttributeMaxDynamicSharedMemorySize, slds[v]);
+                    if (e5 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_shared LDS %d): %s", slds[v], hipGetErrorString(e5)); }
+                }
+            }
+            /* the per-chain rows: today's, unless every FIR chain is grouped and the shared path is on (then ensure_private_taps, if ever) */
+            if (!(pl.n_sh_groups > 0 && pl.n_fir_rest == 0 && prog->fir_shared)) {
+                hipError_t e2 = hipMalloc((void **)&pl.d_taps64, (size_t)d->nchains * pl.pitch64 * sizeof(double));
+                if (e2 != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 taps, %d x %d): %s", d->nchains, pl.pitch64, hipGetErrorString(e2)); }
+                Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};
+                hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ta);
+                if (hipGetLastError() != hipSuccess) { free_plan(pl); return set_err("taps_to_f64 failed to launch"); }
+            }
         }
         RingConvArgs ca{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
         hipLaunchKernelGGL(state_to_ring, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ca);   /* history the caller's buffer holds */
@@ -6428,6 +6745,7 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
     case AVDSP_OPT_READY_WORDS: if (value < -1 || value > 2) return set_err("ready_words: -1 (by plan), 0 (events), 1 (the cascade's waves publish) or 2 (a kernel behind the cascade publishes)"); prog->ready_words = value; return 0;
     case AVDSP_OPT_LANE_HW: prog->lane_hw = value != 0; return 0;
     case AVDSP_OPT_FIR_SPLIT: prog->fir_split = value != 0; return 0;
+    case AVDSP_OPT_FIR_SHARED: if (value != 0 && value != 1) return set_err("fir_shared: 0 or 1"); prog->fir_shared = value; return 0;
     case AVDSP_OPT_FIR_LEAN: if (value < -1 || value > 1) return set_err("fir_lean: -1 (auto), 0 or 1"); prog->fir_lean = value; return 0;
     case AVDSP_OPT_RING_WAIT: prog->ring_wait_host = value != 0; return 0;
     case AVDSP_OPT_READY_TEST: prog->ready_test = value > 0 ? value : 0; return 0;
@@ -6476,6 +6794,9 @@ int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
     case AVDSP_OPT_FRAME_SERVER_FRAMES: return (int)std::min(prog->fs_frames, 0x7FFFFFFFll);
     case AVDSP_OPT_FRAME_SERVER_LAUNCHES: return (int)std::min(prog->fs_launches, 0x7FFFFFFFll);
     case AVDSP_OPT_FRAME_SERVER_FALLBACKS: return (int)std::min(prog->fs_fallbacks, 0x7FFFFFFFll);
+    case AVDSP_OPT_FIR_SHARED: return prog->fir_shared;
+    case AVDSP_OPT_FIR_SHARED_CHAINS: return prog->sh_chains_now;
+    case AVDSP_OPT_FIR_SHARED_GROUPS: return prog->sh_groups_now;
     }
     return -1;
 }

@@ -363,7 +363,7 @@ def synth_sections(channel: int, nsections: int, fmin: int, fmax: int, _cache={}
 def synth_program(fmt: int, channels: int, nsections: int, ntaps: int = 0,
                   fmin: int = F48000, fmax: int = F48000, gain: float = 1.0,
                   shared_taps: bool = False, taps: np.ndarray | None = None,
-                  channel_base: int = 0) -> np.ndarray:
+                  channel_base: int = 0, fir_banks: int | None = None) -> np.ndarray:
     """The synthetic workload of SURVEY.md 8(d) / BASELINE.json:
 
         channel c:  PARAM{bank_c [, impulse_c]}  LOAD_GAIN(IO=C+c, gain)  BIQUADS(bank_c)
@@ -372,18 +372,31 @@ def synth_program(fmt: int, channels: int, nsections: int, ntaps: int = 0,
     Returns the program words (uint32, length = header.totalLength); the caller appends
     header.dataSize words of state space.  `taps` overrides the LCG impulses ([C, T] float32).
     `channel_base` makes this the shard [channel_base, channel_base+channels) of a larger program:
-    filters and impulses are those of the global channel numbers, IO numbers stay local."""
+    filters and impulses are those of the global channel numbers, IO numbers stay local.
+    `fir_banks` k: k impulse banks (LCG impulses 0 .. k-1, or taps[0 .. k-1]) in one PARAM in front of the channels, and
+    channel c's FIR points at bank c % k -- chains of one bank interleave over the IO numbers (the shared-impulse FIR path,
+    DESIGN.md 4.2d).  None: one impulse per channel, as always."""
     nf = fmax - fmin + 1
     per_ch = 16 + nsections * (2 + 6 * nf) + 8 + nf * (ntaps + 3) + 8
-    pw = ProgramWriter(fmt, fmin, fmax, capacity=32 + channels * per_ch)
+    nbanks = 0 if fir_banks is None else int(fir_banks)
+    if nbanks < 0 or (fir_banks is not None and ntaps and nbanks < 1):
+        raise ValueError(f"fir_banks: {fir_banks}")
+    extra = 16 + nbanks * (8 + nf * (ntaps + 3)) if nbanks else 0
+    pw = ProgramWriter(fmt, fmin, fmax, capacity=32 + channels * per_ch + extra)
     if ntaps and taps is None:
-        taps = lcg_taps_all(1 if shared_taps else channels, ntaps, channel_base)
+        taps = lcg_taps_all(nbanks if nbanks else 1 if shared_taps else channels, ntaps, channel_base)
     pw.core()
+    banks = []
+    if nbanks and ntaps:
+        pw.param()
+        banks = [pw.fir_impulses([taps[b]] * nf) for b in range(nbanks)]
     for c in range(channels):
         pw.param()
         bank = pw.biquad_bank(synth_sections(channel_base + c, nsections, fmin, fmax)) if nsections else None
         imp = None
-        if ntaps:
+        if ntaps and banks:
+            imp = banks[c % nbanks]
+        elif ntaps:
             t = taps[0 if shared_taps else c]
             imp = pw.fir_impulses([t] * nf)
         pw.load_gain_fixed(channels + c, gain)

@@ -56,7 +56,13 @@ typedef struct avdsp_plan_desc {
     int32_t  instances;              /* > 1: the chains are that many copies of a core's, copy i addressing mirror copy i (word indices
                                         + i * total words) and sample block i (IO numbers + i * the blocks' distance in words):
                                         avdsp_hip_chain_instances() must have made the copies; 0 / 1: an ordinary plan */
+    /* FIR chains on one impulse bank (same fir_coef_word and fir_taps: the bank at the current rate), AVDSP_FIR_GROUP_MIN chains or
+     * more per group: the shared-impulse FIR path (fir_shared) takes each group as the columns of its tiles.  0 groups: none. */
+    int32_t  fir_ngroups;
+    const int32_t *fir_group_start;  /* [fir_ngroups + 1]: group g is fir_group_chains[start[g] .. start[g + 1])                */
+    const int32_t *fir_group_chains; /* indices into chains[]                                                                 */
 } avdsp_plan_desc;
+#define AVDSP_FIR_GROUP_MIN 16
 
 /* A core that is not a set of independent chains runs through the general device interpreter
  * (avdsp_interp.inc: every opcode of dsp_runtime.c:302-1314, formats 2..6, sequential over frames).
@@ -234,7 +240,11 @@ enum { AVDSP_OPT_OVERLAP = 0, AVDSP_OPT_PROFILE_STRIDE = 1, AVDSP_OPT_FIR_ROWS =
        AVDSP_OPT_FRAME_SERVER_IDLE_US = 19,     /* the server leaves after that many microseconds without a request: 50 .. 20000, default 1000 */
        AVDSP_OPT_FRAME_SERVER_FRAMES = 20,      /* read-only: core calls the servers answered */
        AVDSP_OPT_FRAME_SERVER_LAUNCHES = 21,    /* read-only: servers started */
-       AVDSP_OPT_FRAME_SERVER_FALLBACKS = 22    /* read-only: calls whose bounded wait for the server ran out and that went the ordinary way */ };
+       AVDSP_OPT_FRAME_SERVER_FALLBACKS = 22,   /* read-only: calls whose bounded wait for the server ran out and that went the ordinary way */
+       AVDSP_OPT_FIR_SHARED = 23,               /* 1 (default): FIR groups of one impulse bank on fir_shared (with fir_impl 1, no overlap mode, no fir_split,
+                                                   no chain instances); 0: every FIR chain on the kernels fir_impl names */
+       AVDSP_OPT_FIR_SHARED_CHAINS = 24,        /* read-only: chains the latest FIR launch ran on fir_shared */
+       AVDSP_OPT_FIR_SHARED_GROUPS = 25         /* read-only: ... in that many groups */ };
 /* FIR_LEAN: fir_tile's chunk boundary with a third of the vector instructions: -1 by the plan (default), 0 never, 1 always. */
 /* READY_WORDS (under OVERLAP): how a block's FIR finds its cascades' block in the rings: 0 an event between the two queues, 1 per-chain
  * words published by the cascade's waves (write-through stores) and polled by the FIR's, 2 the words set by a kernel behind the

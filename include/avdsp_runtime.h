@@ -243,6 +243,12 @@ int dspRuntimeStrandInfo(int format, opcode_t *core, int *strands, int *ops_per_
  * "frame_server_idle_us" (50 .. 20000, default 1000) = the server leaves after that long without a request.  Read-only:
  * "frame_server_frames" (core calls served), "frame_server_launches" (servers started), "frame_server_fallbacks" (calls whose bounded
  * wait for the server ran out and that went the ordinary way) -- per device copy of the program, 0 before there is one.
+ * "fir_split" 1 (opt-in, default 0): a fir_tile launch of at most one tile per SIMD cuts every tile's taps over two waves (within 1e-6 of
+ * the reference, not its bits).  "fir_shared" 1 (default) = FIR chains that point at ONE impulse bank at the current rate, in groups of 16
+ * chains or more, run as the columns of fir_shared's tiles (bit-identical); every other chain keeps fir_tile.  Only with
+ * "fir_impl" 1, "overlap" 0, "fir_split" 0 and no chain instances -- everywhere else every chain takes today's path; 0 = every chain on
+ * today's path.  Read-only: "fir_shared_chains" / "fir_shared_groups" = the chains / groups fir_shared took in the latest FIR launch of the
+ * program (0 before there is one); "fir_rows" forces its row tiles as it does fir_tile's.  dspRuntimeFirGroupInfo tells what the lowering groups.
  * A program's options are also the defaults of programs loaded later.                                */
 int dspRuntimeSetOption(const char *key, int value);
 int dspRuntimeGetOption(const char *key);
@@ -259,6 +265,10 @@ int dspRuntimeKernelTime(int kind, double *total_ms, int *launches);
  * parallel chain kernels take it; nchains == 0: the general interpreter takes it; negative: neither
  * (encoding mismatch, an offset outside the buffer, an opcode with no defined result in this format). */
 int dspRuntimeCoreInfo(int format, opcode_t *core, int *nchains, int *max_sections, int *max_taps);
+/* Host-only, nothing runs on the GPU: the groups of 16 chains or more whose DSP_FIR points at one impulse bank at the current sample rate,
+ * among the chains of the core this process runs (dspRuntimeSetShard) -- what "fir_shared" takes.  A core that the interpreter runs, or a
+ * format without the chain FIR (2, 3, 5), has none. */
+int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped_chains, int *largest_group);
 
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
