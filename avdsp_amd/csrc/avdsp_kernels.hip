@@ -1868,6 +1868,8 @@ struct FirTileArgs {
                                                 TileGeom::WPC.  Round 5: a block of 256 frames is ONE tile of a one-row-tile wave, and with the waves of a
                                                 workgroup fixed at the four tiles of a 1024-frame block three of them left at once while the workgroup kept its
                                                 LDS -- two live waves per CU: 4096 chains x 256 frames took 289 us, eight rounds of 512 waves */
+    int all_cascaded;                        /* fir_tile: 1 = no chain of the launch is FIR-only (nsec == 0), known to the host from the plan: the waves
+                                                skip the look for such chains (two dependent loads per chain) and the barrier behind it */
 #ifdef AVDSP_FIR_STAMPS
     unsigned long long *stamps;              /* diagnostic build (tools/fir_timeline.py): 32 s_memtime stamps per wave */
 #endif
@@ -1920,7 +1922,7 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
     const int wsh = SPLIT ? (G::WPC == 4 ? 2 : G::WPC == 2 ? 1 : 0) : a.wpc_shift;
     /* FIR-only chains: the FIR's input is (float)X of the load stage; the workgroup's chains get theirs appended first
      * (the waves of one chain sit in one workgroup) */
-    {
+    if (!a.all_cascaded) {                   /* (a launch argument: the same for every wave, so is the barrier) */
         FirArgs fa{};
         fa.ring = a.ring; fa.io = a.io;
         for (int q = 0; q < (SPLIT ? 1 : 4 >> wsh); q++) {
@@ -1959,7 +1961,6 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
     const int cid = __builtin_amdgcn_readfirstlane(a.group[slot]);
     const avdsp_chain c = a.chains[cid];
     const int T = __builtin_amdgcn_readfirstlane(c.fir_taps);
-    if (a.ready && c.nsec) chain_ready_wait(a.ready, cid, a.seq, a.timeouts, a.ready_acquire != 0);       /* the chain's cascade of this launch has left its block in the ring */
     double *hs = lds + (size_t)wv * G::LDS_DOUBLES, *ws = hs + 2 * G::HLEN;     /* taps images at hs and hs + HLEN */
     const double *hbuf = a.taps64 + (size_t)cid * a.pitch64;
     const float *ringrow = ring_row(a.ring, cid);
@@ -2077,35 +2078,60 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
         for (int j = 0; j < G::QD; j++) q[(16 - G::QD + j) & 15] = hp[4 * j];
         q[0] = hp[16 * (R - 1)]; q[1] = hp[16 * (R - 1) + 4];
         bq[0] = wp[win_off<R, BIG>(0)]; bq[1] = wp[win_off<R, BIG>(1)];
+        if constexpr (LEAN) {
+            /* These operands are needed by the first MFMAs anyway.  Waiting for them HERE makes the state at the head of the group loop
+             * the same from both its edges -- nothing pending but the read-ahead -- so that the first k-step of a group gets the exact
+             * lgkmcnt(4) of the other fifteen instead of a full wait for the two reads it has just issued (the header merged the back
+             * edge with these nine reads, pending in another order).  The long boundary keeps the compiler's waits (taps_dma). */
+            __builtin_amdgcn_s_waitcnt(0xC07F);             /* lgkmcnt(0), vmcnt and expcnt left alone */
+            __builtin_amdgcn_sched_barrier(0);
+        }
     };
+    /* Row tile r at k-step s (m = -NR + 4 s) multiplies the taps h[m + k + 16 r + i], k = 0 .. 3, i = 0 .. 15: all of them padding
+     * zeros iff s < 4 (R-1-r) (the zeros in front: m + 18 + 16 r < 0) or s > slast - 4 r (behind: m + 16 r > T - 1).  Such an MFMA
+     * adds 0 x sample to a sum that began at +0 -- the bits stay for every finite sample, and an Inf or NaN that meets padding only
+     * contributes nothing in the reference either -- so it is not issued: at the front a matter of (j, r) alone, compiled out of
+     * the launch's very first group (EDGE 1); at the back a wave-uniform comparison per MFMA in the groups that reach beyond the
+     * last step all row tiles have (EDGE 2, which ends at the first k-step no row tile has a tap in -- Sall is rounded up to 16 --
+     * reads and all, and looks at the front at run time: a short FIR's only group is both).  The comparisons sit between the reads
+     * and never around one, so the waits stay exact.  4096 taps at four row tiles: 48 of a wave's 4160 MFMAs. */
+    const int slast = (T - 1 + NR) >> 2;            /* the last k-step with a tap in it (row tile 0) */
     /* one k-step: the reads of step j + 2 (of the next group for j = 14, 15: the same code, offsets continue), R MFMAs */
-    auto kstep = [&](const double *hg, const double *wg, auto jc) {
-        constexpr int j = decltype(jc)::value;
+    auto kstep = [&](const double *hg, const double *wg, auto jc, auto ec, [[maybe_unused]] int sg) {
+        constexpr int j = decltype(jc)::value, EDGE = decltype(ec)::value;
+        if (EDGE == 2 && sg + j > slast) return false;      /* no row tile has a tap here or further on: the group ends */
         q[(j + 2) & 15] = hg[4 * (j + 2)];
         bq[(j + 2) & 3] = j + 2 < 16 ? wg[win_off<R, BIG>((j + 2) & 15)] : (wg - 64 / NR)[win_off<R, BIG>((j + 2) & 15)];
         __builtin_amdgcn_sched_barrier(0);          /* the reads stay two steps ahead of their MFMAs */
 #pragma unroll
-        for (int r = 0; r < R; r++)
-            acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(q[(j - 4 * (R - 1 - r)) & 15], bq[j & 3], acc[r], 0, 0, 0);
+        for (int r = 0; r < R; r++) {
+            const int first = 4 * (R - 1 - r);
+            if (EDGE == 0 || (EDGE == 1 && j >= first) || (EDGE == 2 && (unsigned)(sg + j - first) <= (unsigned)(slast - 4 * r - first)))
+                acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(q[(j - 4 * (R - 1 - r)) & 15], bq[j & 3], acc[r], 0, 0, 0);
+        }
         __builtin_amdgcn_sched_barrier(0);
+        return true;
     };
-    auto group16 = [&](const double *hg, const double *wg) {
-        kstep(hg, wg, std::integral_constant<int, 0>{});  kstep(hg, wg, std::integral_constant<int, 1>{});
-        kstep(hg, wg, std::integral_constant<int, 2>{});  kstep(hg, wg, std::integral_constant<int, 3>{});
-        kstep(hg, wg, std::integral_constant<int, 4>{});  kstep(hg, wg, std::integral_constant<int, 5>{});
-        kstep(hg, wg, std::integral_constant<int, 6>{});  kstep(hg, wg, std::integral_constant<int, 7>{});
-        kstep(hg, wg, std::integral_constant<int, 8>{});  kstep(hg, wg, std::integral_constant<int, 9>{});
-        kstep(hg, wg, std::integral_constant<int, 10>{}); kstep(hg, wg, std::integral_constant<int, 11>{});
-        kstep(hg, wg, std::integral_constant<int, 12>{}); kstep(hg, wg, std::integral_constant<int, 13>{});
-        kstep(hg, wg, std::integral_constant<int, 14>{}); kstep(hg, wg, std::integral_constant<int, 15>{});
+    auto group16 = [&](const double *hg, const double *wg, auto ec, int sg) {
+        (void)(kstep(hg, wg, std::integral_constant<int, 0>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 1>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 2>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 3>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 4>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 5>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 6>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 7>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 8>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 9>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 10>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 11>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 12>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 13>{}, ec, sg) &&
+               kstep(hg, wg, std::integral_constant<int, 14>{}, ec, sg) && kstep(hg, wg, std::integral_constant<int, 15>{}, ec, sg));
     };
 
     /* A chunk: write the window image (its samples were requested a chunk ago), request the next chunk's window samples and
      * taps image, run the k-steps.  While a wave is at a boundary the other wave of its SIMD has the matrix pipe to itself.
      * (Tried and dropped, measured slower: a second WINDOW image filled in slices between the MFMAs -- the slices' address
      * arithmetic and conversions cost the f64 matrix pipe more than the stop they replace, 83 -> 95 us on a 512-chain shard.) */
-    win_fetch(Sb, min(ck, S - Sb));
+    /* The taps do not depend on the cascade: their first image is on its way while the wave waits for the chain's ready word.  The
+     * window stays behind the wait. */
     taps_dma(0, Sb, min(ck, S - Sb));
+    if (a.ready && c.nsec) chain_ready_wait(a.ready, cid, a.seq, a.timeouts, a.ready_acquire != 0);       /* the chain's cascade of this launch has left its block in the ring */
+    win_fetch(Sb, min(ck, S - Sb));
     [[maybe_unused]] int stamp_i = 1;
     int cur = 0;
     for (int s0 = Sb; s0 < S; s0 += ck, cur ^= 1) {
@@ -2129,7 +2155,13 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
         const double *wp = ws + (3 - k) * G::ROW + i16 + JT - (64 / NR - 1);   /* group g: wp - g * (64 / NR) + win_off(j) */
         chunk_begin(hp, wp);
         FIR_STAMP_CHUNK();
-        for (int g = 0; g < ckc / 16; g++) group16(hp + 16 * (R - 1) + 64 * g, wp - g * (64 / NR));
+        /* groups [0, gfull) of the chunk lie before the last k-step that every row tile has (slast - 4 (R-1)): the code they always
+         * were, but for the launch's first group; the others -- the last one or two of the last chunk(s) -- take the guarded form */
+        const int gfull = min(ckc / 16, ((slast - 4 * (R - 1) - 15 - s0) >> 4) + 1);
+        int g = 0;
+        if (R > 1 && s0 == 0 && gfull > 0) { group16(hp + 16 * (R - 1), wp, std::integral_constant<int, 1>{}, 0); g = 1; }
+        for (; g < gfull; g++) group16(hp + 16 * (R - 1) + 64 * g, wp - g * (64 / NR), std::integral_constant<int, 0>{}, 0);
+        for (; g < ckc / 16; g++) group16(hp + 16 * (R - 1) + 64 * g, wp - g * (64 / NR), std::integral_constant<int, 2>{}, s0 + 16 * g);
         FIR_STAMP_CHUNK();
     }
     FIR_STAMP(23);
@@ -4312,6 +4344,7 @@ int launch_fir_tile(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, Block
     const bool quarters = SPLIT || (BIG && n <= (prog->num_cus > 0 ? prog->num_cus : 256));
     const int wpc = quarters ? kWpc : tiles <= 1 ? 1 : tiles <= 2 ? std::min(2, kWpc) : kWpc;
     a.wpc_shift = wpc == 4 ? 2 : wpc == 2 ? 1 : 0;
+    a.all_cascaded = pl.n_fir_only == 0;
     const int nwg = (n * wpc * (SPLIT ? 2 : 1) + 3) / 4;
     a.per_xcd = (nwg + 7) / 8;
     const size_t lds = (size_t)4 * TileGeom<R, BIG>::LDS_DOUBLES * sizeof(double) + 64;      /* + the four words the waves exchange at the end */
