@@ -6,7 +6,7 @@
  * dsp_runtime.c:150-195), sample-rate selection and state reset (dspRuntimeReset, :116-145), core
  * lookup (:42-77) and the *lowering* of a core's opcode stream into channel chains for the device.
  * It contains no signal arithmetic: every sample is computed by the gfx950 kernels.  A core that
- * is a set of independent  LOAD|LOAD_GAIN -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+  chains goes to
+ * is a set of independent  LOAD|LOAD_GAIN|LOAD_MUX -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+  chains goes to
  * the parallel kernels; any other core is bounds-checked here (scan_generic) and handed to the
  * general device interpreter.  There is no CPU fallback.
  */
@@ -728,17 +728,27 @@ static int check_independent(const lowered *L)
     int rc = 0;
     for (int i = 1; i < nout && !rc; i++)
         if (outs[i] == outs[i - 1]) rc = fail(-8, "IO %d is stored by more than one chain of the core", outs[i]);
-    for (int i = 0; i < L->nchains && !rc; i++)
-        if (bsearch(&L->chains[i].in_io, outs, (size_t)nout, sizeof(int), cmp_int))
-            rc = fail(-8, "IO %d is both loaded and stored inside one core (cross-chain dependency)", L->chains[i].in_io);
+    for (int i = 0; i < L->nchains && !rc; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        if (c->load_mode == AVDSP_LOAD_MUX) {                /* every IO the list names */
+            for (int k = 0; k < c->mux_count && !rc; k++)
+                if (bsearch(&G.code[c->mux_word + 2 * k].i32, outs, (size_t)nout, sizeof(int), cmp_int))
+                    rc = fail(-8, "IO %d is named by a LOAD_MUX list and stored inside one core (cross-chain dependency)", G.code[c->mux_word + 2 * k].i32);
+        } else if (bsearch(&c->in_io, outs, (size_t)nout, sizeof(int), cmp_int))
+            rc = fail(-8, "IO %d is both loaded and stored inside one core (cross-chain dependency)", c->in_io);
+    }
     free(outs);
     return rc;
 }
 
 #define GENERIC_IO_LIMIT 65536            /* IO numbers a program may use (the reference's hosts use well under 100) */
 
-static int lower_core(int format, opcode_t *core, lowered *L)
+/* mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used (dspRuntimeMuxInfo tells it from the others) */
+static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damaged)
 {
+    int damaged_ = 0;
+    if (!mux_damaged) mux_damaged = &damaged_;
+    *mux_damaged = 0;
     const int float_alu = (format != DSP_FORMAT_INT64);
     const int prog_words = dspHeaderPtr->totalLength;
     opcode_t *p = dspFindCoreBegin(core);
@@ -784,6 +794,36 @@ static int lower_core(int format, opcode_t *core, lowered *L)
                 cur.gain_bits = p[a[1]].u32;
             }
             break;
+        case DSP_LOAD_MUX: {                                  /* :871-897: a chain head like LOAD, the accumulator a weighted sum of inputs */
+            if (format != 2 && format != 4 && format != 6)
+                return fail(-8, "word %d: LOAD_MUX is not lowered to the HIP path in format %d", at, format);
+            *mux_damaged = 1;                                 /* (taken back below, once the table has passed) */
+            LC_NEED(2);
+            LC_PROG(a[0], 1);
+            const opcode_t *t = p + a[0];
+            const int n = (short)t[0].i32;                    /* the reference counts in a `short` */
+            if (n < 1) return fail(-8, "word %d: LOAD_MUX table with %d entries", at, n);
+            LC_PROG(a[0], 1 + 2 * n);
+            for (int k = 0; k < n; k++)
+                if (t[1 + 2 * k].i32 < 0 || t[1 + 2 * k].i32 >= GENERIC_IO_LIMIT)
+                    return fail(-8, "word %d: LOAD_MUX entry %d: IO number %d outside [0,%d)", at, k, t[1 + 2 * k].i32, GENERIC_IO_LIMIT);
+            if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
+                return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
+            *mux_damaged = 0;
+            if (open) {
+                if (cur.n_out == 0)
+                    return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
+                if (push_chain(L, &cur)) return fail(-9, "out of memory");
+            }
+            memset(&cur, 0, sizeof cur);
+            open = 1;
+            cur.in_io = t[1].i32;
+            cur.sec_base = L->nsec;
+            cur.load_mode = AVDSP_LOAD_MUX;
+            cur.mux_word = (int)(t - G.code) + 1;
+            cur.mux_count = n;
+            cur.mux_result_word = prog_words + a[1];
+            break; }
         case DSP_BIQUADS: {                                   /* :827-849 */
             if (!open || cur.n_out || cur.sat || cur.fir_taps)
                 return fail(-8, "word %d: BIQUADS outside the supported LOAD->BIQUADS->FIR->SAT0DB->STORE order", at);
@@ -853,6 +893,8 @@ static int lower_core(int format, opcode_t *core, lowered *L)
     if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
     return check_independent(L);
 }
+
+static int lower_core(int format, opcode_t *core, lowered *L) { return lower_core_ex(format, core, L, 0); }
 
 
 /* ------------------------------------------------------------------------------------------
@@ -1373,6 +1415,66 @@ static int fir_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **m
     return ng;
 }
 
+/* Mix groups: the LOAD_MUX chains of a plan whose lists name the same IO sequence -- same length, same IOs, same order;
+ * the gains are free -- grouped, groups of AVDSP_MUX_GROUP_MIN chains or more, in the order of their first chain; a group lists its chains
+ * in plan order.  Returns the number of groups (start / members: malloc'ed, NULL when 0) or -1 (out of memory). */
+static int mux_list_cmp(const avdsp_chain *a, const avdsp_chain *b)
+{
+    if (a->mux_count != b->mux_count) return a->mux_count < b->mux_count ? -1 : 1;
+    if (a->mux_word == b->mux_word) return 0;
+    for (int k = 0; k < a->mux_count; k++) {
+        const int x = G.code[a->mux_word + 2 * k].i32, y = G.code[b->mux_word + 2 * k].i32;
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return 0;
+}
+static int mux_group_cmp(const void *pa, const void *pb)
+{
+    const int r = mux_list_cmp(&g_fg_chains[*(const int32_t *)pa], &g_fg_chains[*(const int32_t *)pb]);
+    if (r) return r;
+    return *(const int32_t *)pa < *(const int32_t *)pb ? -1 : *(const int32_t *)pa > *(const int32_t *)pb;
+}
+static int mux_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **members)
+{
+    *start = 0; *members = 0;
+    const size_t gcap = (size_t)(n / AVDSP_MUX_GROUP_MIN + 2);
+    int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * gcap);
+    int32_t *mem = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+    int32_t *first = (int32_t *)malloc(sizeof(int32_t) * gcap);
+    int32_t *len = (int32_t *)malloc(sizeof(int32_t) * gcap);
+    if (!idx || !st || !mem || !first || !len) { free(idx); free(st); free(mem); free(first); free(len); return -1; }
+    int m = 0;
+    for (int i = 0; i < n; i++) if (ch[i].load_mode == AVDSP_LOAD_MUX) idx[m++] = i;
+    g_fg_chains = ch;
+    qsort(idx, (size_t)m, sizeof(int32_t), mux_group_cmp);
+    int ng = 0;
+    for (int b = 0, e; b < m; b = e) {                   /* runs of one IO sequence; a run is in plan order */
+        for (e = b + 1; e < m && !mux_list_cmp(&ch[idx[e]], &ch[idx[b]]); e++) {}
+        if (e - b >= AVDSP_MUX_GROUP_MIN) { first[ng] = b; len[ng] = e - b; ng++; }
+    }
+    for (int g = 1; g < ng; g++)                         /* the groups in the order of their first chains */
+        for (int h = g; h > 0 && idx[first[h]] < idx[first[h - 1]]; h--) {
+            int32_t t = first[h]; first[h] = first[h - 1]; first[h - 1] = t;
+            t = len[h]; len[h] = len[h - 1]; len[h - 1] = t;
+        }
+    int k = 0;
+    for (int g = 0; g < ng; g++) {
+        st[g] = k;
+        for (int j = 0; j < len[g]; j++) mem[k++] = idx[first[g] + j];
+    }
+    st[ng] = k;
+    free(idx); free(first); free(len);
+    if (!ng) { free(st); free(mem); return 0; }
+    *start = st; *members = mem;
+    return ng;
+}
+static int lowered_has_mux(const lowered *L)
+{
+    for (int i = 0; i < L->nchains; i++) if (L->chains[i].load_mode == AVDSP_LOAD_MUX) return 1;
+    return 0;
+}
+
 static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
 {
     if (!dspHeaderPtr || !G.code) { fail(-1, "no program loaded"); return 0; }
@@ -1452,6 +1554,18 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
             if (ng < 0) { lowered_free(&L); fail(-9, "out of memory"); return 0; }
             d.fir_ngroups = ng; d.fir_group_start = fg_start; d.fir_group_chains = fg_chains;
         }
+        /* mix groups, formed on this process's slice (a sharded group is the rank's part of it) */
+        int32_t *mg_start = 0, *mg_chains = 0;
+        {
+            if (G.chain_inst_made && lowered_has_mux(&L)) {  /* (dspRuntimeBlockAllInstancesDevice puts such a program on the interpreter) */
+                lowered_free(&L); free(fg_start); free(fg_chains);
+                fail(-1, "LOAD_MUX chains have no chain instances");
+                return 0;
+            }
+            const int ng = mux_groups(d.chains, d.nchains, &mg_start, &mg_chains);
+            if (ng < 0) { lowered_free(&L); free(fg_start); free(fg_chains); fail(-9, "out of memory"); return 0; }
+            d.mux_ngroups = ng; d.mux_group_start = mg_start; d.mux_group_chains = mg_chains;
+        }
         /* Instances of a chain core (round 5): the chain list ninst times -- copy i of a chain reads and writes copy i of the mirror
          * (every word index + i * total words: its own state, FIR history and parameters) and block i of the callers' samples (IO
          * numbers + i * the blocks' distance: the kernels form `column = IO - window base`, which then lands in block i).  To the
@@ -1482,7 +1596,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
             d.instances = N;
         }
         cp->plan_id = avdsp_hip_prog_add_plan(G.dev, &d);
-        free(xch); free(xco); free(xst); free(fg_start); free(fg_chains);
+        free(xch); free(xco); free(xst); free(fg_start); free(fg_chains); free(mg_start); free(mg_chains);
         for (int i = lo; i < hi; i++) {
             if (L.chains[i].nsec > cp->max_sections) cp->max_sections = L.chains[i].nsec;
             if (L.chains[i].fir_taps > cp->max_taps) cp->max_taps = L.chains[i].fir_taps;
@@ -1579,6 +1693,43 @@ int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped
     return 0;
 }
 
+/* Host-only: the LOAD_MUX chain heads among the chains of the core this process runs (dspRuntimeSetShard), the mix groups of
+ * AVDSP_MUX_GROUP_MIN chains or more that mux_tile takes, the chains in them and the longest list.  No device is
+ * touched.  A core that is not a set of chains (formats 3 and 5 with a LOAD_MUX among them) has none; a damaged table is -8. */
+int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, int *grouped_chains, int *longest_list)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nm = 0, ng = 0, nc = 0, big = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        int damaged = 0;
+        const int rc = lower_core_ex(format, core, &L, &damaged);
+        if (rc == 0) {
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            for (int i = lo; i < hi; i++)
+                if (L.chains[i].load_mode == AVDSP_LOAD_MUX) { nm++; if (L.chains[i].mux_count > big) big = L.chains[i].mux_count; }
+            int32_t *st = 0, *mem = 0;
+            ng = mux_groups(L.chains + lo, hi - lo, &st, &mem);
+            if (ng < 0) { lowered_free(&L); return fail(-9, "out of memory"); }
+            if (ng) nc = st[ng];
+            free(st); free(mem);
+        }
+        lowered_free(&L);
+        if (rc == -8 && damaged) return rc;
+        if (rc && rc != -8) return rc;
+    }
+    if (mux_chains) *mux_chains = nm;
+    if (groups) *groups = ng;
+    if (grouped_chains) *grouped_chains = nc;
+    if (longest_list) *longest_list = big;
+    return 0;
+}
+
 /* Host-only: which chains of the core this process runs under the current dspRuntimeSetShard, and the IO numbers
  * they load and store -- what the block call's windows must cover, so a host can cut its column slice of a
  * [frames][channels] block for ANY loaded program.  total == 0: not a chain core (it runs whole on every rank). */
@@ -1599,8 +1750,11 @@ int dspRuntimeShardInfo(int format, opcode_t *core, int *total_chains, int *firs
             shard_range(tot, G.shard_world, G.shard_rank, &lo, &hi);
             for (int i = lo; i < hi; i++) {
                 const avdsp_chain *c = &L.chains[i];
-                if (imax < imin || c->in_io < imin) imin = c->in_io;
-                if (imax < imin || c->in_io > imax) imax = c->in_io;
+                for (int k = 0; k < (c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : 1); k++) {      /* (a LOAD_MUX head: every IO of its list) */
+                    const int io = c->load_mode == AVDSP_LOAD_MUX ? G.code[c->mux_word + 2 * k].i32 : c->in_io;
+                    if (imax < imin || io < imin) imin = io;
+                    if (imax < imin || io > imax) imax = io;
+                }
                 for (int k = 0; k < c->n_out; k++) {
                     if (omax < omin || c->out_io[k] < omin) omin = c->out_io[k];
                     if (omax < omin || c->out_io[k] > omax) omax = c->out_io[k];
@@ -2434,8 +2588,9 @@ int dspRuntimeBlockAllInstancesDevice(int format, int *rundata, const void *d_in
             lowered L;
             memset(&L, 0, sizeof L);
             const int rc = G.opt_generic ? -8 : lower_core(format, dspFindCoreBegin(c), &L);
+            const int mux = rc == 0 && lowered_has_mux(&L);      /* LOAD_MUX chains have no chain instances: such a program counts as one of both kinds */
             lowered_free(&L);
-            if (rc == 0) nchain++; else if (rc == -8) nother++; else return g_err_code;
+            if (rc == 0) { nchain++; nother += mux; } else if (rc == -8) nother++; else return g_err_code;
             if (c == G.code) break;
         }
         if (nchain && nother) {

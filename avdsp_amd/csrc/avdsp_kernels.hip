@@ -1667,6 +1667,14 @@ __device__ __forceinline__ int win_pos(int w, int row) { return (w & 15) * row +
 constexpr int kHRegs = (16 * kMaxGpc + 16 * (kNG + 1) + 32 + kBlock - 1) / kBlock;              /* 6 */
 constexpr int kWRegs = (kFirPad + 16 * kMaxGpc + 16 * (kNG + 2) + kBlock - 1) / kBlock;         /* 10: slots enumerate w in blocks of 256 */
 
+/* the word a FIR-only chain appends for one sample word: (float)X of the load stage -- or the word as it is where a stage in front of
+ * the chain has formed (float)X already (kLoadRaw: the mux stage's column) */
+template <int FMT>
+__device__ __forceinline__ unsigned fir_input_word(unsigned raw, int load_mode, unsigned gain_bits)
+{
+    return ftz_bits(load_mode == kLoadRaw ? raw : narrow_stage<FMT>(load_stage<FMT>(raw, load_mode, gain_bits)));
+}
+
 /* FIR-only chains: the FIR's input is (float)X of the load stage; append it to the ring first */
 template <int FMT>
 __device__ __forceinline__ void fir_append_input(const FirArgs &a, const avdsp_chain &c, int cid)
@@ -1676,7 +1684,7 @@ __device__ __forceinline__ void fir_append_input(const FirArgs &a, const avdsp_c
     for (int q = threadIdx.x; q < B; q += blockDim.x) {
         unsigned raw = inp[(size_t)q * a.io.in_stride];
         if constexpr (FMT == 6) raw = ftz_bits(raw);           /* fir_mfma runs in the default MODE: flush by hand */
-        ring_put(a.ring, cid, q, ftz_bits(narrow_stage<FMT>(load_stage<FMT>(raw, c.load_mode, c.gain_bits))));
+        ring_put(a.ring, cid, q, fir_input_word<FMT>(raw, c.load_mode, c.gain_bits));
     }
     __syncthreads();
 }
@@ -2986,7 +2994,7 @@ __global__ __launch_bounds__(kBlock) void fir_feed(const FirTileArgs a)
         if (c.nsec) continue;
         unsigned raw = a.io.in[(size_t)n * a.io.in_stride + (c.in_io - a.io.in_base)];
         if constexpr (FMT == 6) raw = ftz_bits(raw);
-        ring_put(a.ring, cid, n, ftz_bits(narrow_stage<FMT>(load_stage<FMT>(raw, c.load_mode, c.gain_bits))));
+        ring_put(a.ring, cid, n, fir_input_word<FMT>(raw, c.load_mode, c.gain_bits));
     }
 }
 
@@ -3073,6 +3081,176 @@ __global__ __launch_bounds__(kBlock) void passthrough(const PassArgs a)
         const avdsp_chain c = a.chains[a.group[slot]];
         auto X = load_stage<FMT>(a.io.in[(size_t)n * a.io.in_stride + (c.in_io - a.io.in_base)], c.load_mode, c.gain_bits);
         emit_out(a.io, c, n, store_stage<FMT>(X, c.sat, a.io.store_mask));
+    }
+}
+
+/* ------------------------------------------------------------------------------------------
+ * LOAD_MUX chain heads (dsp_runtime.c:871-897): one stage in front of the cascades.
+ *
+ *     ALU = 0;  for every (IO, gain) pair of the chain's list, in list order:  ALU += sample[IO] x gain
+ *
+ * one addition per entry, never re-associated (the compiled reference was checked on lists of up to 200 entries): in formats 4 and 6
+ * the products are those of two floats through mulop(), exact in f64, so an fma on the widened operands IS the reference's
+ * multiply-then-add; in format 2 the sum is a wrapping 64-bit integer one, which has no order.  The stage hands every (chain, frame)
+ * on as ONE 32-bit word in the chain's column of the plan's scratch block, [1024 frames][chains] -- the word the chain's first section
+ * or its FIR takes from the accumulator, (float)ALU or (int)(ALU >> 28) -- and the chain's record reads it with kLoadRaw, so the
+ * cascade and FIR kernels run as for any other chain.  A chain with neither is stored here, from the full accumulator
+ * (store_stage: SAT0DB and the s.31 store work on the double).  The reference leaves ALU in the opcode's result word every frame:
+ * the block's last frame writes it.
+ * ---------------------------------------------------------------------------------------- */
+struct MuxRec {                      /* one per chain of a plan that holds LOAD_MUX chains */
+    int list_word, count;            /* first (IO, gain) pair in the mirror and the number of pairs; count 0: a LOAD / LOAD_GAIN chain
+                                        beside them -- its sample word of IO `list_word` is copied into its column as it is */
+    int result_word;                 /* the opcode's 8-byte result word in the mirror */
+    int col;                         /* scratch column; -1: no filter behind the head, the stage stores the chain itself */
+    int sat, n_out, out_io[AVDSP_MAX_STORES];
+};
+/* up to 64 chains of one mix group (lists of one IO sequence): four row tiles of mux_tile's workgroup */
+struct MuxTile {
+    int id0, nrec;                   /* its chains: ids[id0 .. id0 + nrec) */
+    int count, kpad;                 /* list length, and that padded to a multiple of 4 (the pitch of the gains rows) */
+    int list_word;                   /* the list that names the group's IO sequence (its first chain's) */
+    long long g64;                   /* the gains as doubles, mulop(gain): [nrec][kpad] from here, zeros behind `count` */
+};
+struct MuxArgs {
+    int *buf;
+    const MuxRec *recs;              /* [chain] */
+    const int *ids; int nids;        /* mux_plain: the chains it takes; mux_tile: the tiles' chains */
+    const MuxTile *tiles;
+    const double *g64;
+    unsigned *scratch; int scratch_stride;
+    BlockIO io;
+};
+
+template <int FMT>
+__device__ __forceinline__ void mux_emit(const MuxArgs &a, const MuxRec &r, int n, typename Alu<FMT>::type X)
+{
+    if (r.col >= 0) a.scratch[(size_t)n * a.scratch_stride + r.col] = narrow_stage<FMT>(X);
+    else {
+        const unsigned word = store_stage<FMT>(X, r.sat, a.io.store_mask);
+#pragma unroll
+        for (int k = 0; k < AVDSP_MAX_STORES; k++)
+            if (k < r.n_out) a.io.out[(size_t)n * a.io.out_stride + (r.out_io[k] - a.io.out_base)] = word;
+    }
+    if (n == a.io.nframes - 1) {                        /* what the reference's last frame leaves in the result word */
+        unsigned long long u;
+        if constexpr (FMT == 2) u = (unsigned long long)X; else u = (unsigned long long)__double_as_longlong(X);
+        a.buf[r.result_word] = (int)(unsigned)u; a.buf[r.result_word + 1] = (int)(unsigned)(u >> 32);
+    }
+}
+
+/* a sample word as the operand of the list's products */
+template <int FMT>
+__device__ __forceinline__ double mux_sample(unsigned raw)
+{
+    if constexpr (FMT == 4) return (double)int_to_float_scaled31((int)raw);      /* :885 (zero or normal: mulop() of it is its widening) */
+    else return mulop(__uint_as_float(raw));
+}
+
+/* mux_plain<FMT>: one lane per (chain, frame) walks the chain's own list in order -- format 2, chains in no mix group, groups under
+ * AVDSP_MUX_GROUP_MIN.  Consecutive lanes take consecutive chains of one frame: the column stores coalesce. */
+template <int FMT>
+__global__ __launch_bounds__(kBlock) void mux_plain(const MuxArgs a)
+{
+    if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
+    const long long total = (long long)a.nids * a.io.nframes;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
+        const int slot = (int)(g % a.nids), n = (int)(g / a.nids);
+        const MuxRec r = a.recs[a.ids[slot]];
+        const unsigned *frame = a.io.in + (size_t)n * a.io.in_stride;
+        if (r.count == 0) { a.scratch[(size_t)n * a.scratch_stride + r.col] = frame[r.list_word - a.io.in_base]; continue; }
+        const int *t = a.buf + r.list_word;
+        typename Alu<FMT>::type X = 0;
+        for (int j = 0; j < r.count; j++) {
+            const unsigned raw = frame[t[2 * j] - a.io.in_base];
+            const int gw = t[2 * j + 1];
+            if constexpr (FMT == 2) X = (long long)((unsigned long long)X + (unsigned long long)((long long)(int)raw * (long long)gw));      /* v_mad_i64_i32, wrapping */
+            else X = __builtin_fma(mux_sample<FMT>(raw), mulop(__int_as_float(gw)), X);
+        }
+        mux_emit<FMT>(a, r, n, X);
+    }
+}
+
+/* the gains of the grouped chains as doubles, once per plan: row[j] = mulop(gain j), zeros from `count` to the pitch */
+struct MuxGainArgs { const int *buf; const MuxRec *recs; const int *ids; const long long *row; const int *kpad; double *g64; };
+__global__ __launch_bounds__(kBlock) void mux_gains_to_f64(const MuxGainArgs a)
+{
+    const MuxRec r = a.recs[a.ids[blockIdx.x]];
+    double *dst = a.g64 + a.row[blockIdx.x];
+    for (int j = threadIdx.x; j < a.kpad[blockIdx.x]; j += blockDim.x)
+        dst[j] = j < r.count ? mulop(__int_as_float(a.buf[r.list_word + 2 * j + 1])) : 0.0;
+}
+
+/* mux_tile<FMT>, formats 4 and 6: a mix group as a dense contraction on v_mfma_f64_16x16x4_f64,
+ *     Y[m][f] = sum_j G[m][j] * X[f][io_j],   A = G (rows: 16 chains; the gains widened once per plan, mux_gains_to_f64),
+ *                                             B = X (columns: 16 frames; widened while they are staged in LDS: format 4 through
+ *                                                    the branch-free int -> float first, then mulop() with its Inf / NaN / subnormal
+ *                                                    readings -- the samples are staged once per 64 chains, a select there is free),
+ * the instruction's K index = the list position, ascending.  ONE accumulator holds a (chain, frame) for the whole list: no split
+ * sums, no second accumulator per output -- every element of D is the reference's sequential sum, one exact product added per
+ * step, which is what makes fir_tile exact too.  K is padded to a multiple of 4 with gain 0 AND sample 0: the accumulator starts
+ * at +0 and can never become -0 (x + -x is +0, +0 + -0 is +0), so adding the padding's +0 changes no bit; a zero gain against a
+ * real sample is never formed for a stored element.  A workgroup is four waves = 64 chains x 64 frames: wave w holds chains
+ * 16 w .. 16 w + 15 against four frame tiles (four accumulators), so a gains operand is read once per four MFMAs and a staged
+ * sample serves 64 chains.  The list is walked in chunks of 32 positions: A [64][33] and B [32][66] doubles in LDS (pitches of 33 and
+ * 66 doubles), 33 792 bytes. */
+constexpr int kMuxKc = 32, kMuxRows = 64, kMuxFrames = 64, kMuxApitch = kMuxKc + 1, kMuxBpitch = kMuxFrames + 2;
+template <int FMT>
+__global__ __launch_bounds__(kBlock) void mux_tile(const MuxArgs a)
+{
+    __shared__ double As[kMuxRows * kMuxApitch], Xs[kMuxKc * kMuxBpitch];
+    flush_f32_subnormals_like_the_reference();
+    const MuxTile T = a.tiles[blockIdx.x];
+    const int f0 = (int)blockIdx.y * kMuxFrames, B = a.io.nframes;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ij = lane & 15, k = lane >> 4;
+    const int *list = a.buf + T.list_word;
+    const double *gains = a.g64 + T.g64;
+    const bool busy = 16 * wave < T.nrec;                /* (wave-uniform) */
+    v4f64 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
+    const int sk = tid & (kMuxKc - 1), s0 = tid >> 5;    /* staging: consecutive threads take consecutive list positions */
+    for (int j0 = 0; j0 < T.count; j0 += kMuxKc) {
+        __syncthreads();                                  /* everyone is done with the previous chunk */
+        const int j = j0 + sk;
+        const int io = j < T.count ? list[2 * j] : -1;
+#pragma unroll
+        for (int u = 0; u < kMuxRows / 8; u++) {
+            const int m = s0 + 8 * u;
+            As[m * kMuxApitch + sk] = (m < T.nrec && j < T.kpad) ? gains[(size_t)m * T.kpad + j] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kMuxFrames / 8; u++) {
+            const int f = s0 + 8 * u, n = f0 + f;
+            double v = 0.0;
+            if (io >= 0 && n < B) v = mux_sample<FMT>(a.io.in[(size_t)n * a.io.in_stride + (io - a.io.in_base)]);
+            Xs[sk * kMuxBpitch + f] = v;
+        }
+        __syncthreads();
+        if (busy) {
+            const int ksteps = (min(kMuxKc, T.count - j0) + 3) >> 2;
+            const double *ap = As + (16 * wave + ij) * kMuxApitch + k;      /* A[i = lane & 15][k = lane >> 4] */
+            const double *bp = Xs + k * kMuxBpitch + ij;                     /* B[k = lane >> 4][col = lane & 15] */
+            for (int s = 0; s < ksteps; s++) {
+                const double av = ap[4 * s];
+#pragma unroll
+                for (int t = 0; t < 4; t++)
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bp[4 * s * kMuxBpitch + 16 * t], acc[t], 0, 0, 0);
+            }
+        }
+    }
+    if (!busy) return;
+    /* C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15 (the frame), row = (lane >> 4) + 4 * reg (the chain) */
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int m = 16 * wave + k + 4 * r;
+        if (m >= T.nrec) continue;
+        const MuxRec rec = a.recs[a.ids[T.id0 + m]];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int n = f0 + 16 * t + ij;
+            if (n < B) mux_emit<FMT>(a, rec, n, acc[t][r]);
+        }
     }
 }
 
@@ -3907,6 +4085,15 @@ struct Plan {
     double *d_sh_taps64 = nullptr;                       /* the taps as doubles, [group][pitch64] */
     int *d_sh_feed = nullptr; int n_sh_feed = 0;         /* grouped chains without a cascade in front (fir_feed appends their input) */
     int *d_fir_rest = nullptr; int n_fir_rest = 0;       /* the FIR chains in no group: fir_tile beside fir_shared */
+    /* LOAD_MUX chain heads: the stage in front of the cascades.  Every chain of such a plan reads its input from its
+     * column of d_mux_scratch ([1024 frames][nchains] words), which the stage fills */
+    bool has_mux = false;
+    MuxRec *d_mux_recs = nullptr;                        /* [nchains] */
+    int *d_mux_plain = nullptr; int n_mux_plain = 0;     /* the chains mux_plain takes */
+    int *d_mux_tile_ids = nullptr; MuxTile *d_mux_tiles = nullptr; int n_mux_tiles = 0, n_mux_tiled = 0;      /* mux_tile: blocks of <= 64 chains of one mix group */
+    double *d_mux_g64 = nullptr;                         /* their gains as doubles */
+    unsigned *d_mux_scratch = nullptr;
+    int n_mux_stored = 0;                                /* chains the stage stores itself (no filter behind the head) */
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
     int *d_lane_rows = nullptr; int n_lane_rows = 0;     /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
@@ -4157,6 +4344,8 @@ void free_plan(Plan &p)
     (void)hipFree(p.d_fir_ids); (void)hipFree(p.d_pass_ids); (void)hipFree(p.d_ring); (void)hipFree(p.d_ring64); (void)hipFree(p.d_own); (void)hipFree(p.d_taps64);
     (void)hipFree(p.d_ready);
     (void)hipFree(p.d_sh_ids); (void)hipFree(p.d_sh_tiles); (void)hipFree(p.d_sh_taps64); (void)hipFree(p.d_sh_feed); (void)hipFree(p.d_fir_rest);
+    (void)hipFree(p.d_mux_recs); (void)hipFree(p.d_mux_plain); (void)hipFree(p.d_mux_tile_ids); (void)hipFree(p.d_mux_tiles); (void)hipFree(p.d_mux_g64);
+    (void)hipFree(p.d_mux_scratch);
 }
 
 int fir_groups_per_chunk(int max_taps)
@@ -4765,6 +4954,31 @@ int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl,
     return 0;
 }
 
+/* the LOAD_MUX stage of a block (at most kFirChunk frames), on the caller's stream in front of the cascades: mux_tile for the mix groups,
+ * mux_plain for everything else; they write different columns and run one behind the other on the stream */
+template <int FMT>
+int launch_mux(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
+{
+    ProfileScope scope(prog, stream, AVDSP_KERNEL_MUX); scope.begin();
+    MuxArgs a{};
+    a.buf = prog->d_buf; a.recs = pl.d_mux_recs; a.g64 = pl.d_mux_g64; a.tiles = pl.d_mux_tiles;
+    a.scratch = pl.d_mux_scratch; a.scratch_stride = pl.nchains; a.io = io;
+    if constexpr (FMT != 2) {
+        if (pl.n_mux_tiles) {
+            a.ids = pl.d_mux_tile_ids; a.nids = pl.n_mux_tiled;
+            hipLaunchKernelGGL(mux_tile<FMT>, dim3((unsigned)pl.n_mux_tiles, (unsigned)((io.nframes + kMuxFrames - 1) / kMuxFrames)), dim3(kBlock), 0, stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (pl.n_mux_plain) {
+        a.ids = pl.d_mux_plain; a.nids = pl.n_mux_plain;
+        const long long total = (long long)pl.n_mux_plain * io.nframes;
+        hipLaunchKernelGGL(mux_plain<FMT>, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 1 << 16)), dim3(kBlock), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 template <int FMT>
 int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
 {
@@ -5177,11 +5391,60 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     std::vector<std::pair<int, std::vector<int>>> byN;   /* (section count, chain ids) in first-seen order */
     std::vector<int> fir, pass;
     pl.io_in_min = pl.io_out_min = 0x7FFFFFFF; pl.io_in_max = pl.io_out_max = -1;
+    /* LOAD_MUX chain heads: the stage's records; every chain of the plan then reads column i of the stage's scratch block -- a chain with
+     * a filter the word the stage has formed (kLoadRaw), a LOAD / LOAD_GAIN chain beside them its sample word, copied there */
+    std::vector<MuxRec> mux_recs;
+    std::vector<char> mux_stored(d->nchains, 0);
+    for (int i = 0; i < d->nchains; i++) {
+        if (chains[i].load_mode != AVDSP_LOAD_PLAIN && chains[i].load_mode != AVDSP_LOAD_GAIN && chains[i].load_mode != AVDSP_LOAD_MUX)
+            return set_err("chain %d: load mode %d", i, chains[i].load_mode);
+        pl.has_mux = pl.has_mux || chains[i].load_mode == AVDSP_LOAD_MUX;
+    }
+    if (pl.has_mux) {
+        if (pl.lane_mode) return set_err("LOAD_MUX chains have no kernels in format %d", d->format);
+        if (d->instances > 1) return set_err("LOAD_MUX chains have no chain instances");
+        int lo = 0x7FFFFFFF, hi = 0;                     /* the mirror words that hold the lists */
+        for (int i = 0; i < d->nchains; i++) {
+            const avdsp_chain &c = chains[i];
+            if (c.load_mode != AVDSP_LOAD_MUX) continue;
+            if (c.mux_count < 1 || c.mux_count > 32767 || c.mux_word < 0 || (long long)c.mux_word + 2ll * c.mux_count > buf_words ||
+                c.mux_result_word < 0 || (long long)c.mux_result_word + 2 > buf_words)
+                return set_err("chain %d: LOAD_MUX list or result word outside the loaded buffer", i);
+            lo = std::min(lo, c.mux_word); hi = std::max(hi, c.mux_word + 2 * c.mux_count);
+        }
+        std::vector<int> words((size_t)(hi - lo));
+        HIP_TRY(hipDeviceSynchronize());
+        if (copy_to_caller(words.data(), prog->d_buf + lo, words.size() * 4)) return -1;
+        mux_recs.resize(d->nchains);
+        for (int i = 0; i < d->nchains; i++) {
+            avdsp_chain &c = chains[i];
+            MuxRec r{};
+            r.sat = c.sat; r.n_out = c.n_out;
+            for (int k = 0; k < AVDSP_MAX_STORES; k++) r.out_io[k] = c.out_io[k];
+            if (c.load_mode == AVDSP_LOAD_MUX) {
+                for (int k = 0; k < c.mux_count; k++) {
+                    const int io = words[(size_t)(c.mux_word - lo) + 2 * k];
+                    if (io < 0) return set_err("chain %d: LOAD_MUX entry %d names IO %d", i, k, io);
+                    pl.io_in_min = std::min(pl.io_in_min, io); pl.io_in_max = std::max(pl.io_in_max, io);
+                }
+                r.list_word = c.mux_word; r.count = c.mux_count; r.result_word = c.mux_result_word;
+                r.col = (c.nsec || c.fir_taps) ? i : -1;
+                if (r.col < 0) { mux_stored[i] = 1; pl.n_mux_stored++; }
+                c.load_mode = kLoadRaw;
+            } else {
+                if (c.in_io < 0) return set_err("chain %d: bad IO", i);
+                pl.io_in_min = std::min(pl.io_in_min, c.in_io); pl.io_in_max = std::max(pl.io_in_max, c.in_io);
+                r.list_word = c.in_io; r.count = 0; r.col = i;
+            }
+            c.in_io = i;
+            mux_recs[i] = r;
+        }
+    }
     for (int i = 0; i < d->nchains; i++) {
         const avdsp_chain &c = chains[i];
         if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return set_err("chain %d: bad section range", i);
         if (c.n_out < 1 || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return set_err("chain %d: bad IO", i);
-        pl.io_in_min = std::min(pl.io_in_min, c.in_io); pl.io_in_max = std::max(pl.io_in_max, c.in_io);
+        if (!pl.has_mux) { pl.io_in_min = std::min(pl.io_in_min, c.in_io); pl.io_in_max = std::max(pl.io_in_max, c.in_io); }
         for (int k = 0; k < c.n_out; k++) {
             if (c.out_io[k] < 0) return set_err("chain %d: bad IO", i);
             pl.io_out_min = std::min(pl.io_out_min, c.out_io[k]); pl.io_out_max = std::max(pl.io_out_max, c.out_io[k]);
@@ -5198,7 +5461,7 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
             auto it = std::find_if(byN.begin(), byN.end(), [&](const auto &e) { return e.first == c.nsec; });
             if (it == byN.end()) { byN.push_back({c.nsec, {}}); it = byN.end() - 1; }
             it->second.push_back(i);
-        } else if (!c.fir_taps) pass.push_back(i);
+        } else if (!c.fir_taps && !mux_stored[i]) pass.push_back(i);
     }
     if (upload_vec(&pl.d_sec_coef, coef) || upload_vec(&pl.d_sec_state, state)) { free_plan(pl); return -1; }
     if (pl.lane_mode && upload_vec(&pl.d_chains, chains)) { free_plan(pl); return -1; }
@@ -5442,6 +5705,48 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     pl.overlap_ok = pl.n_fir > 0 && !pl.bq.empty();
     for (int i = 0; i < d->nchains && pl.overlap_ok; i++)
         if (chains[i].nsec && !chains[i].fir_taps) pl.overlap_ok = false;
+    if (pl.has_mux) {
+        pl.overlap_ok = false;                            /* (the cascades follow the mux stage on the caller's stream: no overlap mode, no ready words) */
+        /* mix groups -> mux_tile's blocks of up to 64 chains (formats 4 and 6); every other chain -> mux_plain */
+        std::vector<char> tiled(d->nchains, 0);
+        std::vector<int> tile_ids, plain, kpads;
+        std::vector<MuxTile> tiles;
+        std::vector<long long> rows;
+        long long g64_len = 0;
+        if (d->format != 2 && d->mux_ngroups > 0 && d->mux_group_start && d->mux_group_chains)
+            for (int g = 0; g < d->mux_ngroups; g++) {
+                const int b = d->mux_group_start[g], e = d->mux_group_start[g + 1];
+                if (b < 0 || e < b || e - b < AVDSP_MUX_GROUP_MIN) { free_plan(pl); return set_err("mix group %d: %d chains", g, e - b); }
+                const int c0 = d->mux_group_chains[b];
+                if (c0 < 0 || c0 >= d->nchains || mux_recs[c0].count < 1) { free_plan(pl); return set_err("mix group %d: chain %d has no list", g, c0); }
+                const int count = mux_recs[c0].count, kpad = (count + 3) & ~3;
+                for (int j = b; j < e; j++) {
+                    const int ci = d->mux_group_chains[j];
+                    /* (the kernel reads the IO numbers from the first chain's list: the host has compared the sequences) */
+                    if (ci < 0 || ci >= d->nchains || tiled[ci] || mux_recs[ci].count != count) { free_plan(pl); return set_err("mix group %d: chain %d is not one of its lists", g, ci); }
+                    tiled[ci] = 1;
+                    if ((j - b) % kMuxRows == 0) tiles.push_back(MuxTile{(int)tile_ids.size(), std::min(kMuxRows, e - j), count, kpad, mux_recs[c0].list_word, g64_len});
+                    tile_ids.push_back(ci); rows.push_back(g64_len); kpads.push_back(kpad);
+                    g64_len += kpad;
+                }
+            }
+        for (int i = 0; i < d->nchains; i++) if (!tiled[i]) plain.push_back(i);
+        pl.n_mux_plain = (int)plain.size(); pl.n_mux_tiles = (int)tiles.size(); pl.n_mux_tiled = (int)tile_ids.size();
+        if (upload_vec(&pl.d_mux_recs, mux_recs) || upload_vec(&pl.d_mux_plain, plain) || upload_vec(&pl.d_mux_tile_ids, tile_ids) ||
+            upload_vec(&pl.d_mux_tiles, tiles)) { free_plan(pl); return -1; }
+        if (hipMalloc((void **)&pl.d_mux_scratch, (size_t)kFirChunk * d->nchains * sizeof(unsigned)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(mux columns of %d chains)", d->nchains); }
+        if (pl.n_mux_tiled) {
+            long long *d_rows = nullptr; int *d_kpads = nullptr;
+            if (hipMalloc((void **)&pl.d_mux_g64, (size_t)g64_len * sizeof(double)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 gains, %lld)", g64_len); }
+            if (upload_vec(&d_rows, rows) || upload_vec(&d_kpads, kpads)) { (void)hipFree(d_rows); free_plan(pl); return -1; }
+            MuxGainArgs ga{prog->d_buf, pl.d_mux_recs, pl.d_mux_tile_ids, d_rows, d_kpads, pl.d_mux_g64};
+            hipLaunchKernelGGL(mux_gains_to_f64, dim3(pl.n_mux_tiled), dim3(kBlock), 0, nullptr, ga);
+            const bool launched = hipGetLastError() == hipSuccess;
+            const bool done = hipDeviceSynchronize() == hipSuccess;
+            (void)hipFree(d_rows); (void)hipFree(d_kpads);
+            if (!launched || !done) { free_plan(pl); return set_err("mux_gains_to_f64 failed"); }
+        }
+    }
     if (pl.overlap_ok) {                                  /* ready words, all at launch number 0 */
         if (hipMalloc((void **)&pl.d_ready, (size_t)d->nchains * sizeof(unsigned)) != hipSuccess ||
             hipMemset(pl.d_ready, 0, (size_t)d->nchains * sizeof(unsigned)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(ready words)"); }
@@ -5955,7 +6260,9 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
     {
         const char *i0 = (const char *)d_in, *i1 = i0 + (size_t)nframes * in_stride * 4;
         const char *o0 = (const char *)d_out, *o1 = o0 + (size_t)nframes * out_stride * 4;
-        const bool direct = pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
+        /* (a plan with LOAD_MUX chains: its cascades and their replays read the stage's scratch columns, never the caller's input -- but
+         * chains the stage stores itself are stored while other workgroups of the stage still read the frame) */
+        const bool direct = pl.has_mux ? pl.n_mux_stored > 0 : pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
         if (direct && nframes > 1 && i0 < o1 && o0 < i1) {
             const size_t words = (size_t)nframes * in_stride;
             /* one copy buffer per caller's stream: a buffer is only ever written and read in that stream's order (two in-place calls on
@@ -6034,6 +6341,15 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         io.nframes = std::min(kFirChunk, nframes - f0);
         io.store_mask = pl.store_mask;
         int rc;
+        if (pl.has_mux) {                                /* the mux stage, then every chain from its scratch column */
+            switch (pl.format) {
+            case 2:  rc = launch_mux<2>(prog, pl, io, (hipStream_t)stream); break;
+            case 4:  rc = launch_mux<4>(prog, pl, io, (hipStream_t)stream); break;
+            default: rc = launch_mux<6>(prog, pl, io, (hipStream_t)stream); break;
+            }
+            if (rc) return rc;
+            io.in = pl.d_mux_scratch; io.in_stride = pl.nchains; io.in_base = 0;
+        }
         switch (pl.format) {
         case 2:  rc = launch_all<2>(prog, pl, io, fir_impl, biquad_impl, (hipStream_t)stream); break;
         case 4:  rc = launch_all<4>(prog, pl, io, fir_impl, biquad_impl, (hipStream_t)stream); break;

@@ -22,6 +22,10 @@ Layout facts restated here (reference file:line):
   * FIR = [op][impOff per rate, rel. to op][dataOff]; the runtime (dsp_runtime.c:928-969) expects
       impOff to address the LENGTH word.  The reference's own dsp_FIR() addresses the section header
       instead (dsp_encoder.c:1311-1313, an encoder bug), so this builder follows the runtime.
+  * LOAD_MUX table inside a PARAM, no alignment: [(36<<16)|n] then n x [IO][gain]
+                                                               dsp_encoder.c:849-867
+  * LOAD_MUX = [op][tableOff rel. to op][dataOff], 2 result words, 8-byte aligned
+                                                               dsp_encoder.c:829-847
   * END_OF_CODE = [0] (+1 pad word to make the length even)    dsp_encoder.c:509-516
   * header.checkSum = sum of head words                        runtime/dsp_header.h:234-251
 Peaking-EQ coefficients follow encoder/dsp_filters.c:94-102,135-143 (a1 is stored minus 1.0).
@@ -37,6 +41,7 @@ import numpy as np
 OP_END, OP_HEADER, OP_NOP, OP_CORE, OP_PARAM = 0, 1, 2, 3, 4
 OP_SWAPXY, OP_COPYXY = 11, 12
 OP_LOAD, OP_LOAD_GAIN, OP_STORE = 34, 35, 37
+OP_LOAD_MUX = 36
 OP_GAIN, OP_SAT0DB = 41, 42
 OP_BIQUADS, OP_FIR = 50, 51
 
@@ -214,6 +219,36 @@ class ProgramWriter:
         self._w(io)
         self._w(3)
         self._param_value(gain)
+
+    def mux_inputs(self, pairs) -> int:
+        """dspLoadMux_Inputs + dspLoadMux_Data per (IO, gain) pair, inside an open PARAM; returns the table's word index.
+        (Written as arrays: a mixing matrix of 4096 x 1024 is eight million words.)"""
+        pairs = list(pairs)
+        n = len(pairs)
+        pos = self._w((OP_LOAD_MUX << 16) | (n & 0xFFFF))
+        ios = np.fromiter((p[0] for p in pairs), dtype=np.int64, count=n)
+        gains = np.fromiter((p[1] for p in pairs), dtype=np.float64, count=n)
+        for io in np.unique(ios[ios < 32]):
+            self._mark_in(int(io))
+        if self.int_mode:                                   # DSP_QM32, see _qm32
+            lim = float(1 << (32 - MANT - 1))
+            q = (gains.clip(-lim, lim) * float(1 << MANT)).astype(np.int64)
+            q = np.where(gains >= lim, 0x7FFFFFFF, np.where(-gains > lim, 0x80000000, q))
+            vals = (q & 0xFFFFFFFF).astype(np.uint32)
+        else:
+            vals = gains.astype(np.float32).view(np.uint32)
+        self.words[self.idx:self.idx + 2 * n:2] = (ios & 0xFFFFFFFF).astype(np.uint32)
+        self.words[self.idx + 1:self.idx + 2 * n:2] = vals
+        self.idx += 2 * n
+        return pos
+
+    def load_mux(self, table: int) -> int:
+        """dsp_LOAD_MUX(table); returns the data offset of the opcode's result word."""
+        base = self._head(OP_LOAD_MUX, 3)
+        self._w(table - base)
+        off = self._data_aligned8(2)
+        self._w(off)
+        return off
 
     def gain_fixed(self, gain: float):
         self._head(OP_GAIN, 3)
@@ -406,6 +441,55 @@ def synth_program(fmt: int, channels: int, nsections: int, ntaps: int = 0,
             pw.fir(imp, ntaps)
         pw.sat0db()
         pw.store(c)
+    return pw.end_of_code()
+
+
+def mixer_gains(o: int, n: int) -> np.ndarray:
+    """Gains of output o's list entries 0 .. n-1 in synth_mixer_program: float32 values in +-[1/32, 1/4] that depend on both."""
+    j = np.arange(n, dtype=np.int64)
+    v = ((o * 2654435761 + j * 40503 + 12345) >> 7) & 0xFFFF
+    g = (1.0 + (v & 0xFF) / 36.5) / 32.0
+    return np.where(v & 0x100, -g, g).astype(np.float32)
+
+
+def synth_mixer_program(fmt: int, outputs: int, inputs: int, nsections: int, ntaps: int = 0,
+                        lists: str = "shared", sat: bool = True, entries: int = 8,
+                        fmin: int = F48000, fmax: int = F48000) -> np.ndarray:
+    """A mixing matrix in front of the chains:
+
+        output o:  PARAM{mux_o [, bank_o] [, impulse_o]}  LOAD_MUX(mux_o)  [BIQUADS(bank_o)]  [FIR(impulse_o)]
+                   [SAT0DB]  STORE(IO=o)                  one CORE, inputs at IO outputs .. outputs+inputs-1.
+
+    lists "shared": every output mixes ALL inputs in IO order (one IO sequence, gains of its own: one mix group);
+    "private": output o mixes `entries` inputs, input (o * 7 + j * step) mod inputs at position j with step = 1 + (o div inputs) mod
+    (inputs - 1): with 7 coprime to `inputs` and entries >= 2 the first inputs * (inputs - 1) outputs all name different sequences
+    (no group).  Gains: mixer_gains(o, entries)."""
+    if lists not in ("shared", "private"):
+        raise ValueError(f"lists: {lists}")
+    nf = fmax - fmin + 1
+    nlist = inputs if lists == "shared" else min(entries, 32767)
+    per_out = 24 + 2 * nlist + nsections * (2 + 6 * nf) + 8 + nf * (ntaps + 3) + 8
+    pw = ProgramWriter(fmt, fmin, fmax, capacity=32 + outputs * per_out)
+    taps = lcg_taps_all(outputs, ntaps) if ntaps else None
+    pw.core()
+    for o in range(outputs):
+        pw.param()
+        if lists == "shared":
+            ios = [outputs + j for j in range(inputs)]
+        else:
+            step = 1 + (o // inputs) % max(inputs - 1, 1)
+            ios = [outputs + (o * 7 + j * step) % inputs for j in range(nlist)]
+        table = pw.mux_inputs(zip(ios, mixer_gains(o, len(ios)).astype(np.float64)))
+        bank = pw.biquad_bank(synth_sections(o, nsections, fmin, fmax)) if nsections else None
+        imp = pw.fir_impulses([taps[o]] * nf) if ntaps else None
+        pw.load_mux(table)
+        if bank is not None:
+            pw.biquads(bank, nsections)
+        if imp is not None:
+            pw.fir(imp, ntaps)
+        if sat:
+            pw.sat0db()
+        pw.store(o)
     return pw.end_of_code()
 
 

@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -124,6 +124,8 @@ def lib() -> C.CDLL:
         L.dspRuntimeStrandInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeFirGroupInfo.restype = i32
         L.dspRuntimeFirGroupInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        L.dspRuntimeMuxInfo.restype = i32
+        L.dspRuntimeMuxInfo.argtypes = [i32, vp] + [C.POINTER(i32)] * 4
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -229,6 +231,14 @@ class Runtime:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeFirGroupInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
         return dict(groups=a.value, grouped_chains=b.value, largest_group=c.value)
+
+    def mux_info(self, core_index: int = 0):
+        """dspRuntimeMuxInfo (host-only): the chains that begin with LOAD_MUX, the mix groups of >= 16 chains on one IO sequence that
+        mux_tile takes, the chains in them and the longest list, at the current shard."""
+        v = [C.c_int() for _ in range(4)]
+        self._check(self.L.dspRuntimeMuxInfo(self.fmt, self.cores[core_index], *[C.byref(x) for x in v]))
+        keys = ("mux_chains", "groups", "grouped_chains", "longest_list")
+        return {k: x.value for k, x in zip(keys, v)}
 
     def tag_output(self, out: np.ndarray, column: int):
         """dspRuntimeTagOutput on a host block [frames][out_stride] of int32, in place (linux/avdsp_plugin.c:133-137)."""

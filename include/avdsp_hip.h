@@ -6,7 +6,7 @@
  * chains) into an avdsp_plan_desc; the device side keeps a mirror of the caller's buffer
  * (program words + state area, same word layout as on the host) and runs
  *
- *     LOAD | LOAD_GAIN  ->  BIQUADS cascade  ->  [FIR]  ->  [SAT0DB]  ->  STORE
+ *     LOAD | LOAD_GAIN | LOAD_MUX  ->  BIQUADS cascade  ->  [FIR]  ->  [SAT0DB]  ->  STORE
  *     (dsp_runtime.c:565-607, 827-849 + dsp_biquadSTD.h:25-119, 928-969 + dsp_firSTD.h:38-52,
  *      464-475, 610-633)
  *
@@ -25,7 +25,7 @@ extern "C" {
 #define AVDSP_MAX_STORES 4
 
 /* how the accumulator is loaded at the head of a chain */
-enum { AVDSP_LOAD_PLAIN = 0, AVDSP_LOAD_GAIN = 1 };
+enum { AVDSP_LOAD_PLAIN = 0, AVDSP_LOAD_GAIN = 1, AVDSP_LOAD_MUX = 3 };     /* (2 is taken inside the kernels: a raw word between two pieces) */
 
 /* One channel chain.  All *_word fields are absolute word indices into the caller's buffer
  * (program words first, state area from word `totalLength`).                                    */
@@ -41,6 +41,11 @@ typedef struct avdsp_chain {
     int32_t  sat;                    /* SAT0DB in front of the stores                            */
     int32_t  n_out;                  /* number of STOREs (same value to each)                    */
     int32_t  out_io[AVDSP_MAX_STORES];
+    /* AVDSP_LOAD_MUX (dsp_runtime.c:871-897): the accumulator is the sum, in list order, of sample[io] x gain over the list's pairs;
+     * in_io is the list's first IO (unused by the kernels) */
+    int32_t  mux_word;               /* first pair of the list: (IO number, gain) x mux_count from this word on */
+    int32_t  mux_count;              /* pairs, >= 1                                              */
+    int32_t  mux_result_word;        /* the 8-byte word the reference leaves the accumulator in every frame (2 words) */
 } avdsp_chain;
 
 /* words between two copies of the mirror (chain instances, avdsp_hip_chain_instances): even, so that state words keep their alignment */
@@ -61,8 +66,14 @@ typedef struct avdsp_plan_desc {
     int32_t  fir_ngroups;
     const int32_t *fir_group_start;  /* [fir_ngroups + 1]: group g is fir_group_chains[start[g] .. start[g + 1])                */
     const int32_t *fir_group_chains; /* indices into chains[]                                                                 */
+    /* AVDSP_LOAD_MUX chains whose lists name the same IO sequence (same length, same IOs, same order; the gains are free),
+     * AVDSP_MUX_GROUP_MIN chains or more per group: mux_tile takes a group as one dense gains x samples contraction.  0 groups: none. */
+    int32_t  mux_ngroups;
+    const int32_t *mux_group_start;  /* [mux_ngroups + 1]                                                                     */
+    const int32_t *mux_group_chains; /* indices into chains[]                                                                 */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
+#define AVDSP_MUX_GROUP_MIN 16
 
 /* A core that is not a set of independent chains runs through the general device interpreter
  * (avdsp_interp.inc: every opcode of dsp_runtime.c:302-1314, formats 2..6, sequential over frames).
@@ -176,7 +187,7 @@ int avdsp_hip_run_block_pcm_host(avdsp_hip_prog *prog, int plan, int pcm, const 
  * the summed duration and the number of launches, and forgets them.  on: 0 = off, 1 = every kind,
  * 2 * mask = only the kinds whose bit is set in mask (an event pair costs a few microseconds of stream
  * time: a benchmark times the kernel it reports and nothing else).                               */
-enum { AVDSP_KERNEL_BIQUAD = 0, AVDSP_KERNEL_FIR = 1, AVDSP_KERNEL_PASS = 2, AVDSP_KERNEL_GENERIC = 3, AVDSP_KERNEL_UNPACK = 4, AVDSP_KERNEL_GENERIC_WAVE = 5, AVDSP_KERNEL_STRANDS = 6 };
+enum { AVDSP_KERNEL_BIQUAD = 0, AVDSP_KERNEL_FIR = 1, AVDSP_KERNEL_PASS = 2, AVDSP_KERNEL_GENERIC = 3, AVDSP_KERNEL_UNPACK = 4, AVDSP_KERNEL_GENERIC_WAVE = 5, AVDSP_KERNEL_STRANDS = 6, AVDSP_KERNEL_MUX = 7 };
 /* N instances of the loaded program side by side (dspRuntimeSetInstances / dspRuntimeBlockAllInstancesDevice): instance i has a copy of
  * the whole device state of its own and its sample blocks at d_in + i * in_inst_words, d_out + i * out_inst_words (32-bit words). */
 int avdsp_hip_set_instances(avdsp_hip_prog *prog, int n);

@@ -85,11 +85,11 @@ int       dspQM32(double x, int m);         /* dsp_header.c:83-85 */
  *
  * Two device paths sit behind these entry points.  A core that is a set of independent
  * LOAD|LOAD_GAIN -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+ chains runs on parallel kernels in every
- * format: 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
+ * format (in 2, 4 and 6 a chain may also begin with LOAD_MUX, see dspRuntimeMuxInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
  * the MFMA FIR (fir_tile); 3 and 5 -- float accumulators and the truncating dspMulFloatFloat -- on
  * chain_rows (a lane per chain and section) and fir_lane (a lane per chain and frame), with
  * chain_lane for single frames and cascades longer than 16 sections.  Any other core -- X/Y
- * arithmetic, TPDF dither, delay lines, LOAD_MUX, RMS ... -- runs through the general device
+ * arithmetic, TPDF dither, delay lines, LOAD_MUX in formats 3 and 5, RMS ... -- runs through the general device
  * interpreter (runs of identical strands on strand_lanes, a lane per strand).
  * Its frame-parallel kernel runs 64 frames of the block side by side (one
  * per lane, opcode by opcode) whenever the core hands nothing from one frame to the next except
@@ -257,7 +257,8 @@ int dspRuntimeGetOption(const char *key);
  * ("profile", 2 * mask) to time only the kinds whose bit is set in mask (each event pair costs the stream a few
  * microseconds);
  * kind 0 = biquad cascade, 1 = FIR, 2 = pass-through, 3 = general interpreter frame by frame,
- * 4 = PCM unpack, 5 = general interpreter frame-parallel.  Returns the summed duration (ms) and launch
+ * 4 = PCM unpack, 5 = general interpreter frame-parallel, 6 = strands on lanes, 7 = the LOAD_MUX stage in front
+ * of the cascades (mux_tile / mux_plain).  Returns the summed duration (ms) and launch
  * count of the launches recorded since the previous read.                                        */
 int dspRuntimeKernelTime(int kind, double *total_ms, int *launches);
 
@@ -269,6 +270,23 @@ int dspRuntimeCoreInfo(int format, opcode_t *core, int *nchains, int *max_sectio
  * among the chains of the core this process runs (dspRuntimeSetShard) -- what "fir_shared" takes.  A core that the interpreter runs, or a
  * format without the chain FIR (2, 3, 5), has none. */
 int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped_chains, int *largest_group);
+/* LOAD_MUX chain heads (dsp_runtime.c:871-897; formats 2, 4 and 6): a chain may begin with a weighted sum of several inputs instead of a
+ * LOAD -- a mixing matrix in front of the chains.  A stage of its own in front of the cascades forms every chain's sum in the list's order,
+ * one addition per entry like the reference (bit-identical, Inf / NaN / subnormal samples included), hands (float)ALU / ALU >> 28 to the
+ * chain's first section or FIR, stores chains without a filter itself from the full accumulator, and leaves the block's last ALU in the
+ * opcode's result word (dspRuntimeSyncState; another core may read it with LOAD_MEM_DATA).  Chains whose lists name the same IO sequence
+ * (same length, same IOs, same order; the gains are free) form a mix group; groups of 16 chains or more run as a dense gains x samples
+ * contraction on v_mfma_f64_16x16x4_f64 in formats 4 and 6 (mux_tile), everything else with a lane per (chain, frame) (mux_plain).
+ * No IO a list names may be stored by a chain of the same core (the core then stays with the interpreter), and a block call's input
+ * window must cover every list IO (dspRuntimeShardInfo's input range spans them).  Formats 3 and 5 keep such cores on the interpreter.
+ * Limits, by design and not silently: a program with LOAD_MUX chains that gets dspRuntimeSetInstances(n > 1) runs every core on the
+ * interpreter while it has instances (the rule of programs that mix chain and interpreter cores: "generic" reads 1 meanwhile); and a
+ * plan with LOAD_MUX chains ignores "overlap" and the ready words -- its cascades follow the mux stage on the caller's stream.
+ * dspRuntimeMuxInfo is host-only, nothing runs on the GPU: among the chains of the core this process runs (dspRuntimeSetShard, the
+ * groups are formed after the cut) the chains that begin with LOAD_MUX, the groups of 16 or more, the chains in them and the longest
+ * list.  A core the interpreter runs reports zeros; a LOAD_MUX whose table is damaged (no entries, an IO number outside the range, a
+ * result word outside the state area) returns -8. */
+int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, int *grouped_chains, int *longest_list);
 
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
