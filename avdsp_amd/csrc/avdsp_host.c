@@ -302,7 +302,7 @@ static int set_option_here(const char *key, int value)
         G.opt_fir_shared = value;
         return 0;
     }
-    if (!strcmp(key, "fir_shared_chains") || !strcmp(key, "fir_shared_groups")) return fail(-1, "%s is read-only", key);
+    if (!strcmp(key, "fir_shared_chains") || !strcmp(key, "fir_shared_groups") || !strcmp(key, "fir_shared_rows")) return fail(-1, "%s is read-only", key);
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -396,6 +396,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
+    if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
     if (!strncmp(key, "timing_pairs_", 13) && key[13] >= '0' && key[13] <= '7' && !key[14])      /* of the latest dspRuntimeKernelTime(kind) */
         return G.dev ? avdsp_hip_profile_last_pairs(G.dev, key[13] - '0') : 0;
     if (!strcmp(key, "ready_timeouts")) { device_current(); return G.dev ? avdsp_hip_ready_timeouts(G.dev) : 0; }

@@ -4155,6 +4155,7 @@ struct avdsp_hip_prog {
     int fir_split = 0;                   /* fir_tile: launches of at most a tile per SIMD cut every tile's taps over two waves (sums within 1e-6, not the reference's bits) */
     int fir_shared = 1;                  /* chains of one impulse bank as the columns of fir_shared; 0: every chain on fir_launch's kernels */
     int sh_chains_now = 0, sh_groups_now = 0;        /* of the latest FIR launch: chains and groups fir_shared took */
+    int sh_rows_now = 0;                             /* ... and the R of the fir_shared<FMT, R> that ran (0: the launch did not take the path) */
     hipStream_t s_bq = nullptr;
     hipStream_t s_fir[2] = {nullptr, nullptr};           /* "overlap" 2: the FIRs of consecutive blocks in turn */
     static constexpr int kAhead = 3;     /* cascade k waits for FIR k - kAhead: it may run under FIR k - 2 and be done before FIR k - 1 ends */
@@ -4642,6 +4643,7 @@ int launch_fir_shared_r(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t 
     a.ring = plan_ring(pl); a.taps64 = pl.d_sh_taps64; a.pitch64 = pl.pitch64; a.io = io;
     const long long nwg = (long long)a.ntiles * a.nfb;
     a.per_xcd = (int)((nwg + 7) / 8);
+    prog->sh_rows_now = R;                            /* ("fir_shared_rows": launch_all sets the chains and groups beside it) */
     return launch_timed(scope, (const void *)fir_shared<FMT, R>, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)SharedGeom<R>::LDS_DOUBLES * sizeof(double), stream, a);
 }
 
@@ -4985,7 +4987,7 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
     const bool under = prog->overlap && pl.overlap_ok && biquad_impl && fir_impl;
     pl.seq++;                                             /* this launch's number in the plan's ready words */
     if (under) {
-        prog->sh_chains_now = prog->sh_groups_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
+        prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
         if (overlap_ready(prog)) return -1;
         const bool own_fir = prog->overlap >= 2 || prog->cu_split > 0;      /* the FIRs on a stream of the library's own */
         if (probe_side_by_side(prog, prog->overlap >= 2 ? prog->s_fir[prog->blk & 1] : prog->cu_split > 0 ? prog->s_fir[0] : stream)) return -1;     /* (remembered per stream) */
@@ -5079,7 +5081,7 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
             prog->sh_chains_now = pl.n_sh_chains; prog->sh_groups_now = pl.n_sh_groups;
         } else if (pl.n_fir) {
             if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, stream)) return -1;
-            prog->sh_chains_now = prog->sh_groups_now = 0;
+            prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;
         }
     }
     if (pl.n_pass) {
@@ -7146,6 +7148,7 @@ int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
     case AVDSP_OPT_FIR_SHARED: return prog->fir_shared;
     case AVDSP_OPT_FIR_SHARED_CHAINS: return prog->sh_chains_now;
     case AVDSP_OPT_FIR_SHARED_GROUPS: return prog->sh_groups_now;
+    case AVDSP_OPT_FIR_SHARED_ROWS: return prog->sh_rows_now;
     }
     return -1;
 }

@@ -255,7 +255,8 @@ enum { AVDSP_OPT_OVERLAP = 0, AVDSP_OPT_PROFILE_STRIDE = 1, AVDSP_OPT_FIR_ROWS =
        AVDSP_OPT_FIR_SHARED = 23,               /* 1 (default): FIR groups of one impulse bank on fir_shared (with fir_impl 1, no overlap mode, no fir_split,
                                                    no chain instances); 0: every FIR chain on the kernels fir_impl names */
        AVDSP_OPT_FIR_SHARED_CHAINS = 24,        /* read-only: chains the latest FIR launch ran on fir_shared */
-       AVDSP_OPT_FIR_SHARED_GROUPS = 25         /* read-only: ... in that many groups */ };
+       AVDSP_OPT_FIR_SHARED_GROUPS = 25,        /* read-only: ... in that many groups */
+       AVDSP_OPT_FIR_SHARED_ROWS = 26           /* read-only: ... with that many row tiles per wave (the R of fir_shared<FMT, R>: 1, 2 or 4; 0: not on fir_shared) */ };
 /* FIR_LEAN: fir_tile's chunk boundary with a third of the vector instructions: -1 by the plan (default), 0 never, 1 always. */
 /* READY_WORDS (under OVERLAP): how a block's FIR finds its cascades' block in the rings: 0 an event between the two queues, 1 per-chain
  * words published by the cascade's waves (write-through stores) and polled by the FIR's, 2 the words set by a kernel behind the

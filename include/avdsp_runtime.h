@@ -248,7 +248,8 @@ int dspRuntimeStrandInfo(int format, opcode_t *core, int *strands, int *ops_per_
  * chains or more, run as the columns of fir_shared's tiles (bit-identical); every other chain keeps fir_tile.  Only with
  * "fir_impl" 1, "overlap" 0, "fir_split" 0 and no chain instances -- everywhere else every chain takes today's path; 0 = every chain on
  * today's path.  Read-only: "fir_shared_chains" / "fir_shared_groups" = the chains / groups fir_shared took in the latest FIR launch of the
- * program (0 before there is one); "fir_rows" forces its row tiles as it does fir_tile's.  dspRuntimeFirGroupInfo tells what the lowering groups.
+ * program (0 before there is one), "fir_shared_rows" = the row tiles per wave (R: 1, 2 or 4) of that launch, 0 when it did not take the path;
+ * "fir_rows" forces its row tiles as it does fir_tile's.  dspRuntimeFirGroupInfo tells what the lowering groups.
  * A program's options are also the defaults of programs loaded later.                                */
 int dspRuntimeSetOption(const char *key, int value);
 int dspRuntimeGetOption(const char *key);

@@ -139,7 +139,7 @@ def test_fir_banks_layout():
 def test_options():
     r = rt.Runtime(6, pb.synth_program(6, 16, 0, 5, fir_banks=1))
     assert r.get_option("fir_shared") == 1
-    assert r.get_option("fir_shared_chains") == 0 and r.get_option("fir_shared_groups") == 0
+    assert r.get_option("fir_shared_chains") == 0 and r.get_option("fir_shared_groups") == 0 and r.get_option("fir_shared_rows") == 0
     r.set_option("fir_shared", 0)
     assert r.get_option("fir_shared") == 0
     r.set_option("fir_shared", 1)
@@ -147,3 +147,5 @@ def test_options():
         r.set_option("fir_shared", 2)
     with pytest.raises(rt.AvdspError):
         r.set_option("fir_shared_chains", 3)
+    with pytest.raises(rt.AvdspError):
+        r.set_option("fir_shared_rows", 2)
