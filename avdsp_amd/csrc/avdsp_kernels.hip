@@ -6265,7 +6265,10 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         /* (a plan with LOAD_MUX chains: its cascades and their replays read the stage's scratch columns, never the caller's input -- but
          * chains the stage stores itself are stored while other workgroups of the stage still read the frame) */
         const bool direct = pl.has_mux ? pl.n_mux_stored > 0 : pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
-        if (direct && nframes > 1 && i0 < o1 && o0 < i1) {
+        /* (one-frame calls of the other plans go without the copy.  Not those of a mux plan: its stage is many waves over that ONE frame,
+         * every chain reads columns that other chains store, and a wave of another workgroup -- in mux_plain of the same one -- may
+         * still walk its list when the first stores.  dspRuntime_N is not in place: its windows are two blocks of the library's own.) */
+        if (direct && (nframes > 1 || pl.has_mux) && i0 < o1 && o0 < i1) {
             const size_t words = (size_t)nframes * in_stride;
             /* one copy buffer per caller's stream: a buffer is only ever written and read in that stream's order (two in-place calls on
              * different streams used to share one -- a race); growing one waits for its own stream, not for the device */

@@ -10,7 +10,9 @@ import pytest
 from avdsp_amd import encoder as enc
 from avdsp_amd import progbuilder as pb
 from avdsp_amd import runtime as rt
-from tests.mux_recipes import mixer_program
+from oracle import pyoracle as po
+from tests.mux_recipes import (EDGE_PROGRAMS, ROW_TAIL_GROUPS, SEAM_LENGTHS, check_seam_lengths, expected_mux_info, live_edit, mixer_program, mux_tables,
+                               several_groups)
 
 
 @pytest.fixture(autouse=True)
@@ -237,3 +239,72 @@ def test_mixer_recipe_is_a_chain_core():
     r = rt.Runtime(4, prog)
     assert r.core_info() == dict(chains=20, max_sections=2, max_taps=9)
     assert r.mux_info() == dict(mux_chains=20, groups=1, grouped_chains=20, longest_list=17)
+
+
+# ---- the programs of tests/test_gpu_mux_edges.py: what dspRuntimeMuxInfo says of them, and a run of the oracle over each ----------------
+
+EDGE_INFO = dict(
+    several_groups=dict(mux_chains=121, groups=3, grouped_chains=103, longest_list=64),
+    list_seams=dict(mux_chains=16 * len(SEAM_LENGTHS), groups=29, grouped_chains=16 * len(SEAM_LENGTHS), longest_list=129),
+    row_tails=dict(mux_chains=sum(ROW_TAIL_GROUPS), groups=12, grouped_chains=sum(ROW_TAIL_GROUPS), longest_list=6),
+    shard_40=dict(mux_chains=40, groups=1, grouped_chains=40, longest_list=12),
+    shard_47=dict(mux_chains=47, groups=1, grouped_chains=47, longest_list=12),
+    live_edit=dict(mux_chains=36, groups=2, grouped_chains=33, longest_list=7),
+    small_mixer=dict(mux_chains=20, groups=1, grouped_chains=20, longest_list=5),
+    small_mixer_fir=dict(mux_chains=20, groups=1, grouped_chains=20, longest_list=5),
+    windows=dict(mux_chains=21, groups=1, grouped_chains=16, longest_list=4),
+    stored=dict(mux_chains=143, groups=1, grouped_chains=136, longest_list=6),
+)
+
+
+def test_the_list_lengths_sit_on_the_seams():
+    check_seam_lengths()
+
+
+def test_every_edge_program_is_listed():
+    assert set(EDGE_INFO) == set(EDGE_PROGRAMS)
+    assert sum(ROW_TAIL_GROUPS) == 627 and len(SEAM_LENGTHS) == 29
+
+
+@pytest.mark.parametrize("fmt", [6, 4, 2])
+@pytest.mark.parametrize("name", sorted(EDGE_PROGRAMS))
+def test_edge_program_groups_and_oracle_run(name, fmt):
+    """every chain of the program is lowered, the groups are the ones its lists spell, and the oracle runs it: every stored IO
+    carries a signal, no other does"""
+    prog, meta = EDGE_PROGRAMS[name](fmt)
+    r = rt.Runtime(fmt, prog)
+    assert r.rc > 0
+    assert r.core_info()["chains"] == meta["nchains"]
+    assert r.mux_info() == EDGE_INFO[name] == expected_mux_info(meta)
+    assert len(mux_tables(prog)) == EDGE_INFO[name]["mux_chains"]
+    o = po.OracleProgram(fmt, prog)
+    assert o.rc == r.rc
+    W, I = meta["width"], meta["inputs"]
+    out = o.run_block(pb.lcg_input(24, I, fmt == 6, seed=7), W, W)
+    stored = sorted(io for ch in meta["chains"] for io in ch["out"])
+    assert len(set(stored)) == len(stored)
+    live = np.nonzero((out != 0).any(axis=0))[0].tolist()
+    assert live == stored, f"{name}: IOs {sorted(set(stored) ^ set(live))[:8]} are stored without a signal, or carry one unstored"
+    assert o.state.any()
+
+
+def test_the_interleaved_groups_scatter_a_tiles_chains():
+    _, meta = several_groups(6)
+    ids = [c for c, ch in enumerate(meta["chains"]) if ch["group"] == 2]
+    assert len(ids) == 70 and ids[:3] == [2, 8, 14] and ids[-1] == meta["nchains"] - 1 == 122
+    assert min(np.diff(ids[:16])) > 1                                                   # no two chains of its first row tile are neighbours
+    gains = {(v, j) for ch in meta["chains"] if ch["group"] == 2 for j, v in enumerate(ch["gains"])}
+    assert len(gains) > 70 * 64 - 3 * 70 * 2                                            # the gains differ by chain and position
+
+
+def test_live_edit_groups_after_the_edits():
+    """the host-only twin of test_gpu_mux_edges.test_live_edits: a list that names another IO leaves its group; a group of 15 is none"""
+    prog, meta = live_edit(6)
+    tabs, W = mux_tables(prog), meta["width"]
+    r = rt.Runtime(6, prog)
+    assert r.mux_info() == dict(mux_chains=36, groups=2, grouped_chains=33, longest_list=7)
+    assert int(r.buf[tabs[5] + 1 + 2 * 3]) == W + 3 and int(r.buf[tabs[20] + 1 + 2 * 1]) == W + 4
+    r.buf[tabs[5] + 1 + 2 * 3] = W + 5
+    assert r.mux_info() == dict(mux_chains=36, groups=2, grouped_chains=32, longest_list=7)
+    r.buf[tabs[20] + 1 + 2 * 1] = W + 3
+    assert r.mux_info() == dict(mux_chains=36, groups=1, grouped_chains=16, longest_list=7)
