@@ -47,8 +47,11 @@
 
 #include "avdsp_hip.h"
 #include "avdsp_format.h"
+#include "avdsp_plan_layout.h"
 
 namespace {
+
+using namespace avdsp_layout;      /* the plan's host-side tables, their records and constants (kFirChunk, kLoadRaw, ...) */
 
 thread_local char g_err[512];
 thread_local bool g_err_ready = false;   /* the latest set_err() was ready_check()'s (avdsp_hip_last_error_is_ready_timeout) */
@@ -69,7 +72,6 @@ int set_err(const char *fmt, ...)
         if (e_ != hipSuccess) return set_err("%s: %s", #expr, hipGetErrorString(e_));          \
     } while (0)
 
-constexpr int kFirChunk   = 1024;     /* frames per launch: 4 MFMA tiles of 256 frames */
 constexpr int kTileFrames = 256;
 constexpr int kBlock      = 256;
 
@@ -364,12 +366,7 @@ __device__ __forceinline__ void emit_out(const BlockIO &io, const avdsp_chain &c
  *           (row_ror:1); after NB steps the NB results sit in NB different lanes, which convert
  *           (SAT0DB/STORE) and store them together.
  * ---------------------------------------------------------------------------------------- */
-/* what biquad_row needs of a chain and of a section, one record per row slot / per lane of a launch group; made with the plan */
-struct RowRec { int cid, in_io, out_io, flags; unsigned gain_bits; int pad[3]; };      /* flags: load_mode | sat << 8 | to_ring << 9 | n_out << 16; pad[0]: the row's section count
-                                                                                            (a launch with BiquadArgs::nsec 0 holds rows of several counts, four-row waves of one
-                                                                                            count each; cid -1: a row that only fills its wave) */
-struct LaneRec { int coef_word, state_word; };                                          /* -1: the lane holds no section */
-
+/* (RowRec, LaneRec -- what biquad_row needs of a chain and of a section -- are made with the plan: avdsp_plan_layout.h) */
 struct BiquadArgs {
     int            *buf;            /* device mirror of the caller's buffer */
     const RowRec   *rows;           /* biquad_row: [ngroup] */
@@ -421,11 +418,7 @@ __device__ __forceinline__ Hand<FMT> hand_from_sample(unsigned raw, int load_mod
     h.y = narrow_stage<FMT>(load_stage<FMT>(raw, load_mode, gain_bits));
     return h;
 }
-/* Pieces of a long cascade (round 5; more than 64 sections: add_plan cuts the chain into pieces of up to 64 that run one launch after the
- * other).  What travels between two sections is a 32-bit word -- (int)(acc >> 28), or the bits of (float)acc -- and between two PIECES the
- * same word goes through a scratch column: kLoadRaw takes a sample word as the first section's input as it is, kStoreRaw (in the chain
- * record's `sat`) stores the last section's result word as it is.  Device-side only; the host's descriptors never hold them. */
-constexpr int kLoadRaw = 2, kStoreRaw = 2;
+/* (kLoadRaw / kStoreRaw, the words between two pieces of a long cascade: avdsp_plan_layout.h) */
 template <int FMT>
 __device__ __forceinline__ Hand<FMT> hand_from_sample_or_raw(unsigned raw, int load_mode, unsigned gain_bits)
 {
@@ -1650,8 +1643,6 @@ struct FirArgs {
  * SIMD, which beats deeper prefetch when the grid fills the GPU (A/B: -3 %); with at most two workgroups per
  * CU there is nothing to interleave and sets of 2 hide more LDS latency.  The images carry the margin of the
  * deeper variant.                                                                                           */
-constexpr int kNG  = 2;
-constexpr int kMaxGpc = 56;          /* 896 tap positions per chunk: <= 27 KB of LDS, 5 workgroups per CU, no spills */
 constexpr int kFirPad = 1024;        /* frames per launch the window image is laid out for (4 tiles) */
 
 /* the operand prefetch runs up to kNG + 1 groups past the end of a chunk: both images carry that margin */
@@ -1841,9 +1832,7 @@ __global__ __launch_bounds__(kBlock, NG == 1 ? 5 : 4) void fir_mfma(const FirArg
  * and is converted while it is staged, 15 R*16 + 4 CK frames per chunk of CK k-steps, into a transposed image
  * pos(u) = (u mod 16R) * row + u / 16R: the 16 lanes of one k read 16 consecutive doubles.
  * ---------------------------------------------------------------------------------------- */
-constexpr int kTapsLead = 64;                /* zeros in front of a chain's taps in the f64 copy */
-constexpr int kTapsTail = 384;               /* zeros behind them (the last k-steps and the operand prefetch read on) */
-__host__ __device__ inline int taps64_pitch(int max_taps) { return (kTapsLead + max_taps + kTapsTail + 1) & ~1; }
+/* (kTapsLead zeros in front of a chain's taps, kTapsTail behind them; taps64_pitch: avdsp_plan_layout.h) */
 
 /* BIG (R = 1 only): chunks twice as long for launches that leave a SIMD one wave at most -- nothing hides a chunk boundary there
  * (2200 cycles each, 16 % of a wave's life on 256 chains x 4096 taps: tools/fir_timeline.py), and a workgroup may have the CU's LDS to
@@ -2325,8 +2314,6 @@ static_assert(SharedGeom<1>::LDS_DOUBLES * 8 <= 64 * 1024 && SharedGeom<2>::LDS_
               SharedGeom<4>::LDS_DOUBLES * 8 <= 64 * 1024, "two fir_shared workgroups per CU");
 static_assert(SharedGeom<4>::HLEN / 128 <= 4, "one taps piece per wave");
 
-/* a column group: chains ids[first .. first + n) (n <= 16) of group `group` (its taps row) */
-struct SharedTile { int group, first, n, taps; };
 struct FirSharedArgs {
     int *buf; const avdsp_chain *chains; const int *ids; const SharedTile *tiles; int ntiles; int nfb; Ring ring; int per_xcd;
     const double *taps64; int pitch64;       /* f64 copy of the groups' taps, [group][pitch64] (taps64_pitch) */
@@ -3098,20 +3085,6 @@ __global__ __launch_bounds__(kBlock) void passthrough(const PassArgs a)
  * (store_stage: SAT0DB and the s.31 store work on the double).  The reference leaves ALU in the opcode's result word every frame:
  * the block's last frame writes it.
  * ---------------------------------------------------------------------------------------- */
-struct MuxRec {                      /* one per chain of a plan that holds LOAD_MUX chains */
-    int list_word, count;            /* first (IO, gain) pair in the mirror and the number of pairs; count 0: a LOAD / LOAD_GAIN chain
-                                        beside them -- its sample word of IO `list_word` is copied into its column as it is */
-    int result_word;                 /* the opcode's 8-byte result word in the mirror */
-    int col;                         /* scratch column; -1: no filter behind the head, the stage stores the chain itself */
-    int sat, n_out, out_io[AVDSP_MAX_STORES];
-};
-/* up to 64 chains of one mix group (lists of one IO sequence): four row tiles of mux_tile's workgroup */
-struct MuxTile {
-    int id0, nrec;                   /* its chains: ids[id0 .. id0 + nrec) */
-    int count, kpad;                 /* list length, and that padded to a multiple of 4 (the pitch of the gains rows) */
-    int list_word;                   /* the list that names the group's IO sequence (its first chain's) */
-    long long g64;                   /* the gains as doubles, mulop(gain): [nrec][kpad] from here, zeros behind `count` */
-};
 struct MuxArgs {
     int *buf;
     const MuxRec *recs;              /* [chain] */
@@ -3194,7 +3167,7 @@ __global__ __launch_bounds__(kBlock) void mux_gains_to_f64(const MuxGainArgs a)
  * 16 w .. 16 w + 15 against four frame tiles (four accumulators), so a gains operand is read once per four MFMAs and a staged
  * sample serves 64 chains.  The list is walked in chunks of 32 positions: A [64][33] and B [32][66] doubles in LDS (pitches of 33 and
  * 66 doubles), 33 792 bytes. */
-constexpr int kMuxKc = 32, kMuxRows = 64, kMuxFrames = 64, kMuxApitch = kMuxKc + 1, kMuxBpitch = kMuxFrames + 2;
+constexpr int kMuxKc = 32, kMuxFrames = 64, kMuxApitch = kMuxKc + 1, kMuxBpitch = kMuxFrames + 2;
 template <int FMT>
 __global__ __launch_bounds__(kBlock) void mux_tile(const MuxArgs a)
 {
@@ -4042,6 +4015,26 @@ __global__ __launch_bounds__(64) void frame_server(const ServerArgs s)
 /* ------------------------------------------------------------------------------------------
  * host side of the thin ABI
  * ---------------------------------------------------------------------------------------- */
+int copy_from_caller(void *d_dst, const void *h_src, size_t bytes);
+
+/* a hipMalloc'd array and its owner: move-only, freed with it.  Launch code reads it as the plain pointer it holds */
+template <typename T> struct DevArr {
+    T *p = nullptr;
+    DevArr() = default;
+    DevArr(DevArr &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevArr() { reset(); }
+    void reset() { (void)hipFree(p); p = nullptr; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n) { reset(); return hipMalloc((void **)&p, n * sizeof(T)); }
+    int upload(const std::vector<T> &v)                  /* (an empty vector: no array) */
+    {
+        if (v.empty()) { reset(); return 0; }
+        HIP_TRY(alloc(v.size()));
+        return copy_from_caller(p, v.data(), v.size() * sizeof(T));
+    }
+};
+
 struct Plan {
     bool generic = false;             /* general interpreter instead of chain kernels */
     GenericArgs ga{};                 /* launch template of the generic path (io filled per block) */
@@ -4051,59 +4044,58 @@ struct Plan {
     size_t ga_lds = 0; bool ga_staged = false;
     int format = 0, nchains = 0, store_mask = -1;
     int instances = 1;                /* > 1: the chains are that many copies of a core's chains (avdsp_plan_desc::instances) */
-    avdsp_chain *d_chains = nullptr;
-    int *d_sec_coef = nullptr, *d_sec_state = nullptr;
+    DevArr<avdsp_chain> d_chains;
+    DevArr<int> d_sec_coef, d_sec_state;
     /* launch groups (device arrays of chain ids) */
-    struct Group { int P; int nsec; int n; int *d_ids; bool all_fir;        /* all_fir: every chain of the group feeds a FIR (its cascade writes the ring) */
-                   RowRec *d_rows; LaneRec *d_lanes;                        /* biquad_row's records (P == 16) */
-                   /* more than 64 sections (round 5): the group as pieces of up to 64, launched one after the other; piece k hands the
-                    * word between its last section and piece k + 1's first through column j (the chain's place in the group) of
-                    * d_scratch[k & 1], [1024 frames][n] words (kLoadRaw / kStoreRaw) */
-                   std::vector<Group> pieces = {}; unsigned *d_scratch[2] = {nullptr, nullptr};
+    struct Group { int P = 0, nsec = 0, n = 0; DevArr<int> d_ids; bool all_fir = false;      /* all_fir: every chain of the group feeds a FIR (its cascade writes the ring) */
+                   DevArr<RowRec> d_rows; DevArr<LaneRec> d_lanes;          /* biquad_row's records (P == 16) */
+                   /* more than 16 sections: the group as pieces of up to 16 (GroupLayout::pieces), launched one after the other; piece k
+                    * hands the word between its last section and piece k + 1's first through column j (the chain's place in the group)
+                    * of d_scratch[k & 1], [1024 frames][n] words (kLoadRaw / kStoreRaw) */
+                   std::vector<Group> pieces; DevArr<unsigned> d_scratch[2];
                    bool raw_out = false; };      /* a piece but the last: it stores its last section's result word as it is (biquad_row<4> can) */
-    /* round 5: the rows of ALL the plan's 16-lane groups in one table -- runs of one section count, each filled up to whole waves (four
-     * rows) with empty rows, the table to whole workgroups -- for ONE biquad_row launch instead of one per section count (nsec 0 in its
-     * arguments: every wave takes its rows' count from their records).  Only made when there are two such groups or more. */
-    RowRec *d_rows_all = nullptr; LaneRec *d_lanes_all = nullptr; int n_rows_all = 0; bool rows_all_fir = true; int n_row_groups = 0;
+    /* the rows of ALL the plan's 16-lane groups in one table (CascadeLayout::all_rows) for ONE biquad_row launch instead of one per section
+     * count: nsec 0 in its arguments (every wave takes its rows' count from their records), no ids.  n 0: not made */
+    Group rows_all;
     std::vector<Group> bq;            /* biquad chains grouped by section count (P = lanes per chain) */
-    int *d_fir_ids = nullptr;  int n_fir = 0, max_taps = 0;
-    int *d_pass_ids = nullptr; int n_pass = 0;
+    DevArr<int> d_fir_ids;  int n_fir = 0, max_taps = 0;
+    DevArr<int> d_pass_ids; int n_pass = 0;
     /* FIR history rings: [nchains][ring_R] floats, frame 0 of the next block goes to index wpos */
-    float *d_ring = nullptr; int ring_R = 0, wpos = 0;
-    double *d_ring64 = nullptr;                          /* fir_stream: the ring as window operands (Ring::wide) */
+    DevArr<float> d_ring; int ring_R = 0, wpos = 0;
+    DevArr<double> d_ring64;                             /* fir_stream: the ring as window operands (Ring::wide) */
     int n_fir_only = 0;                                  /* FIR chains without a cascade in front */
     int fir_gpc = 0;                  /* groups of 16 tap positions per LDS chunk */
     int io_in_min = 0, io_in_max = -1, io_out_min = 0, io_out_max = -1;
     bool wave_ok = false; unsigned carried_io[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* frame-parallel interpreter */
-    int *d_own = nullptr;                                /* owned mirror ranges (pairs), generic plans */
-    double *d_taps64 = nullptr; int pitch64 = 0;         /* fir_tile: the taps as doubles, [chain][pitch64] (a plan whose FIR chains are all
+    DevArr<int> d_own;                                   /* owned mirror ranges (pairs), generic plans */
+    DevArr<double> d_taps64; int pitch64 = 0;            /* fir_tile: the taps as doubles, [chain][pitch64] (a plan whose FIR chains are all
                                                             grouped makes it when a launch first needs it: ensure_private_taps) */
     /* fir_shared: FIR chains grouped by impulse bank (avdsp_plan_desc::fir_group_*), groups of AVDSP_FIR_GROUP_MIN or more */
     int n_sh_groups = 0, n_sh_chains = 0;
-    int *d_sh_ids = nullptr;                             /* the grouped chains, group by group */
-    SharedTile *d_sh_tiles = nullptr; int n_sh_tiles = 0;     /* column groups of <= 16 chains of one group */
-    double *d_sh_taps64 = nullptr;                       /* the taps as doubles, [group][pitch64] */
-    int *d_sh_feed = nullptr; int n_sh_feed = 0;         /* grouped chains without a cascade in front (fir_feed appends their input) */
-    int *d_fir_rest = nullptr; int n_fir_rest = 0;       /* the FIR chains in no group: fir_tile beside fir_shared */
+    DevArr<int> d_sh_ids;                                /* the grouped chains, group by group */
+    DevArr<SharedTile> d_sh_tiles; int n_sh_tiles = 0;        /* column groups of <= 16 chains of one group */
+    DevArr<double> d_sh_taps64;                          /* the taps as doubles, [group][pitch64] */
+    DevArr<int> d_sh_feed; int n_sh_feed = 0;            /* grouped chains without a cascade in front (fir_feed appends their input) */
+    DevArr<int> d_fir_rest; int n_fir_rest = 0;          /* the FIR chains in no group: fir_tile beside fir_shared */
     /* LOAD_MUX chain heads: the stage in front of the cascades.  Every chain of such a plan reads its input from its
      * column of d_mux_scratch ([1024 frames][nchains] words), which the stage fills */
     bool has_mux = false;
-    MuxRec *d_mux_recs = nullptr;                        /* [nchains] */
-    int *d_mux_plain = nullptr; int n_mux_plain = 0;     /* the chains mux_plain takes */
-    int *d_mux_tile_ids = nullptr; MuxTile *d_mux_tiles = nullptr; int n_mux_tiles = 0, n_mux_tiled = 0;      /* mux_tile: blocks of <= 64 chains of one mix group */
-    double *d_mux_g64 = nullptr;                         /* their gains as doubles */
-    unsigned *d_mux_scratch = nullptr;
+    DevArr<MuxRec> d_mux_recs;                           /* [nchains] */
+    DevArr<int> d_mux_plain; int n_mux_plain = 0;        /* the chains mux_plain takes */
+    DevArr<int> d_mux_tile_ids; DevArr<MuxTile> d_mux_tiles; int n_mux_tiles = 0, n_mux_tiled = 0;      /* mux_tile: blocks of <= 64 chains of one mix group */
+    DevArr<double> d_mux_g64;                            /* their gains as doubles */
+    DevArr<unsigned> d_mux_scratch;
     int n_mux_stored = 0;                                /* chains the stage stores itself (no filter behind the head) */
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
-    int *d_lane_rows = nullptr; int n_lane_rows = 0;     /* ... chain_rows' chains (1 .. 16 sections) */
+    DevArr<int> d_lane_rows; int n_lane_rows = 0;        /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
-    int n_lane_fir = 0; unsigned *d_lseq = nullptr; int lseq_pitch = 0;      /* ... and fir_lane's sequence buffer: [nchains][max_taps - 1 + frames of the largest block so far] */
+    int n_lane_fir = 0; DevArr<unsigned> d_lseq; int lseq_pitch = 0;      /* ... and fir_lane's sequence buffer: [nchains][max_taps - 1 + frames of the largest block so far] */
     /* strand plan attached to a generic plan (include/avdsp_hip.h): the stretch as micro-operations, one argument row per strand */
-    avdsp_strand_op *d_sops = nullptr; int *d_sargs = nullptr; int s_nops = 0, s_nargs = 0, s_nstrands = 0, s_nres = 0; bool s_usey = false;
+    DevArr<avdsp_strand_op> d_sops; DevArr<int> d_sargs; int s_nops = 0, s_nargs = 0, s_nstrands = 0, s_nres = 0; bool s_usey = false;
     std::vector<int> s_loaded, s_stored;                 /* the IOs the strands load / store: per call against the windows */
     bool stores_whole_window = false;                    /* every IO of [io_out_min, io_out_max] is stored by some chain */
     bool overlap_ok = false;                             /* every cascade of the plan feeds a FIR: its launches may run under the previous block's FIR */
-    unsigned *d_ready = nullptr; unsigned seq = 0;       /* [nchains] ready words (chain_ready_*): the number of the latest launch whose cascade is through, and the launch counter */
+    DevArr<unsigned> d_ready; unsigned seq = 0;          /* [nchains] ready words (chain_ready_*): the number of the latest launch whose cascade is through, and the launch counter */
 };
 
 }  // namespace
@@ -4158,7 +4150,7 @@ struct avdsp_hip_prog {
     int sh_rows_now = 0;                             /* ... and the R of the fir_shared<FMT, R> that ran (0: the launch did not take the path) */
     hipStream_t s_bq = nullptr;
     hipStream_t s_fir[2] = {nullptr, nullptr};           /* "overlap" 2: the FIRs of consecutive blocks in turn */
-    static constexpr int kAhead = 3;     /* cascade k waits for FIR k - kAhead: it may run under FIR k - 2 and be done before FIR k - 1 ends */
+    static constexpr int kAhead = kRingAhead;     /* cascade k waits for FIR k - kAhead: it may run under FIR k - 2 and be done before FIR k - 1 ends */
     hipEvent_t ev_bq[kAhead] = {nullptr, nullptr, nullptr}, ev_fir[kAhead] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fir_now[kAhead] = {nullptr, nullptr, nullptr};   /* what stands for "FIR of this slot has ended": ev_fir[slot], or the stop event of the kernel timer that rode on that launch (no second event on the stream) */
     hipEvent_t last_ride_stop = nullptr; /* ProfileScope::ride: the stop event the latest timed launch carries */
@@ -4225,8 +4217,6 @@ struct avdsp_hip_prog {
 };
 
 namespace {
-
-int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 /* A FIR wave whose bounded wait for its cascade's ready word ran out (chain_ready_wait) has summed a window its cascade may not
  * have written: the block it belongs to is not the reference's.  The library has long returned 0 for that block (launches are
@@ -4322,39 +4312,6 @@ int copy_to_caller(void *h_dst, const void *d_src, size_t bytes)
         }
     }
     return 0;
-}
-
-template <typename T>
-int upload_vec(T **dst, const std::vector<T> &v)
-{
-    *dst = nullptr;
-    if (v.empty()) return 0;
-    HIP_TRY(hipMalloc((void **)dst, v.size() * sizeof(T)));
-    return copy_from_caller(*dst, v.data(), v.size() * sizeof(T));
-}
-
-void free_plan(Plan &p)
-{
-    (void)hipFree(p.d_chains); (void)hipFree(p.d_sec_coef); (void)hipFree(p.d_sec_state);
-    for (auto &g : p.bq) {
-        (void)hipFree(g.d_ids); (void)hipFree(g.d_rows); (void)hipFree(g.d_lanes); (void)hipFree(g.d_scratch[0]); (void)hipFree(g.d_scratch[1]);
-        for (auto &pc : g.pieces) { (void)hipFree(pc.d_ids); (void)hipFree(pc.d_rows); (void)hipFree(pc.d_lanes); }
-    }
-    (void)hipFree(p.d_rows_all); (void)hipFree(p.d_lanes_all);
-    (void)hipFree(p.d_sops); (void)hipFree(p.d_sargs); (void)hipFree(p.d_lseq); (void)hipFree(p.d_lane_rows);
-    (void)hipFree(p.d_fir_ids); (void)hipFree(p.d_pass_ids); (void)hipFree(p.d_ring); (void)hipFree(p.d_ring64); (void)hipFree(p.d_own); (void)hipFree(p.d_taps64);
-    (void)hipFree(p.d_ready);
-    (void)hipFree(p.d_sh_ids); (void)hipFree(p.d_sh_tiles); (void)hipFree(p.d_sh_taps64); (void)hipFree(p.d_sh_feed); (void)hipFree(p.d_fir_rest);
-    (void)hipFree(p.d_mux_recs); (void)hipFree(p.d_mux_plain); (void)hipFree(p.d_mux_tile_ids); (void)hipFree(p.d_mux_tiles); (void)hipFree(p.d_mux_g64);
-    (void)hipFree(p.d_mux_scratch);
-}
-
-int fir_groups_per_chunk(int max_taps)
-{
-    const int G = (max_taps + 15 + 15) >> 4;
-    const int nc = (G + kMaxGpc - 1) / kMaxGpc;
-    const int gpc = (G + nc - 1) / nc;
-    return std::min((gpc + kNG - 1) / kNG * kNG, kMaxGpc);
 }
 
 size_t fir_lds_bytes(int gpc, int *hs_cap, int *row)
@@ -4456,7 +4413,7 @@ int launch_biquad(avdsp_hip_prog *prog, Plan &pl, const Plan::Group &g, const in
     BiquadArgs a{};
     a.buf = prog->d_buf; a.chains = pl.d_chains; a.sec_coef = pl.d_sec_coef; a.sec_state = pl.d_sec_state;
     a.group = ids; a.ngroup = n; a.nsec = g.nsec; a.ring = plan_ring(pl); a.io = io;
-    a.ready = with_ready ? pl.d_ready : nullptr; a.seq = pl.seq;
+    a.ready = with_ready ? pl.d_ready.get() : nullptr; a.seq = pl.seq;
       /* (a launch whose FIR waits for the words; its ring stores are then write-through) */
 #ifdef AVDSP_BQ_STAMPS
     {
@@ -4473,22 +4430,16 @@ int launch_biquad(avdsp_hip_prog *prog, Plan &pl, const Plan::Group &g, const in
     } else if (biquad_impl == 1 && g.P == 16 && g.d_rows) {
         /* one 16-lane row per chain: biquad_row (format 4 only where the cascade feeds a FIR -- a format-4 STORE needs all of the
          * accumulator, biquad_row hands on its float), biquad_row_i64 */
-        if constexpr (FMT == 2) {
-            const int nblk = (n + 15) / 16;
-            a.rows = g.d_rows; a.lanes = g.d_lanes;
-            a.per_xcd = (nblk + 7) / 8;
-            if (launch_timed(scope, (const void *)biquad_row_i64, dim3(a.per_xcd * 8), dim3(kBlock), 0, stream, a, stop)) return -1;
-        } else {
-            const int nblk = (n + 15) / 16;
-            a.rows = g.d_rows; a.lanes = g.d_lanes;
-            a.per_xcd = (nblk + 7) / 8;
-            /* (under "overlap" `stop` rides on the kernel's own completion signal instead of a marker packet behind it: 7.1 instead of
-             * 8.3 us to the start of the kernel that waits for it on another stream, tools/stream_handover_bench.hip) */
-            /* (format 4: rows that store int samples need the accumulator itself -- the ACC form; FIR-feeding chains and pieces hand a float on) */
-            const void *fn = (const void *)biquad_row<FMT>;
-            if constexpr (FMT == 4) { if (!(g.all_fir || g.raw_out)) fn = (const void *)biquad_row<4, true>; }
-            if (launch_timed(scope, fn, dim3(a.per_xcd * 8), dim3(kBlock), 0, stream, a, stop)) return -1;
-        }
+        const int nblk = (n + 15) / 16;
+        a.rows = g.d_rows; a.lanes = g.d_lanes;
+        a.per_xcd = (nblk + 7) / 8;
+        /* (under "overlap" `stop` rides on the kernel's own completion signal instead of a marker packet behind it: 7.1 instead of
+         * 8.3 us to the start of the kernel that waits for it on another stream, tools/stream_handover_bench.hip) */
+        /* (format 4: rows that store int samples need the accumulator itself -- the ACC form; FIR-feeding chains and pieces hand a float on) */
+        const void *fn = (const void *)biquad_row_i64;
+        if constexpr (FMT != 2) fn = (const void *)biquad_row<FMT>;
+        if constexpr (FMT == 4) { if (!(g.all_fir || g.raw_out)) fn = (const void *)biquad_row<4, true>; }
+        if (launch_timed(scope, fn, dim3(a.per_xcd * 8), dim3(kBlock), 0, stream, a, stop)) return -1;
     } else {
         const int cpb = kBlock / g.P;
         const int nblk = (n + cpb - 1) / cpb;
@@ -4514,97 +4465,87 @@ extern "C" int avdsp_hip_debug_fir_stamps(unsigned long long *host_out, int max_
 }
 #endif
 
-template <int FMT, int R, bool BIG = false, bool SPLIT = false>
-int launch_fir_tile(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, hipStream_t stream, ProfileScope &scope, bool wait_ready, hipEvent_t stop = nullptr, bool lean = true)
+/* ---- the FIR kernels' variants of a format: every instantiation a launch can take, with its dynamic LDS.  Plan creation opts all of
+ * them in (fir_opt_in; nothing in the launch path may touch function attributes: stream capture), a launch finds its function here
+ * from the struct fir_choice returned (fir_variant): what can be chosen is in the table, and what is in the table is opted in ---- */
+struct FirVariant { FirChoice c; const void *fn; int lds; int fw, wpc; };    /* lds -1: fir_lds_bytes of the plan's gpc; fw, wpc: its geometry's frames per wave (fir_shared:
+                                                                                per workgroup) and waves per chain */
+template <int FMT, int R, bool BIG, bool SPLIT>
+void add_fir_tile(std::vector<FirVariant> &v)
 {
-    FirTileArgs a{};
-    a.buf = prog->d_buf; a.chains = pl.d_chains; a.group = ids; a.ngroup = n;
-    a.ring = plan_ring(pl); a.io = io; a.taps64 = pl.d_taps64; a.pitch64 = pl.pitch64;
-    if (wait_ready) { a.ready = pl.d_ready; a.seq = pl.seq; a.timeouts = prog->d_ready_timeouts; a.ready_acquire = prog->ready_mode_now != 2 || prog->overlap >= 2; }
-    /* the tiles a chain has in this launch (a power of two, so that a chain's waves sit in one workgroup): a short block is fewer tiles
-     * than the TileGeom's 1024 frames, and waves without a tile would only hold their workgroup's LDS */
-    constexpr int kWpc = TileGeom<R, BIG>::WPC;
-    const int tiles = (io.nframes + TileGeom<R, BIG>::FW - 1) / TileGeom<R, BIG>::FW;
-    /* (BIG -- at most a wave per SIMD -- keeps the four-quarters arrangement: there a wave that leaves at once frees nothing anybody waits
-     * for, and its workgroup's other waves sit on CUs of their own: 256 chains x 4096 taps at 64 .. 512 frames 36.3-37.6 us against
-     * 38.1-38.8 regrouped) */
-    /* ... as long as its workgroups -- one per chain, one per CU: 140 KB of LDS -- fit the chip at once.  512 or 1024 chains at 256 frames
-     * are 512 / 1024 workgroups of ONE live wave each, two or four rounds of 36 us (a 512-chain shard's 256-frame block took 91 us,
-     * longer than its 1024-frame block): those regroup like everybody else. */
-    const bool quarters = SPLIT || (BIG && n <= (prog->num_cus > 0 ? prog->num_cus : 256));
-    const int wpc = quarters ? kWpc : tiles <= 1 ? 1 : tiles <= 2 ? std::min(2, kWpc) : kWpc;
-    a.wpc_shift = wpc == 4 ? 2 : wpc == 2 ? 1 : 0;
-    a.all_cascaded = pl.n_fir_only == 0;
-    const int nwg = (n * wpc * (SPLIT ? 2 : 1) + 3) / 4;
-    a.per_xcd = (nwg + 7) / 8;
-    const size_t lds = (size_t)4 * TileGeom<R, BIG>::LDS_DOUBLES * sizeof(double) + 64;      /* + the four words the waves exchange at the end */
-#ifdef AVDSP_FIR_STAMPS
-    static unsigned long long *d_stamps = nullptr;
-    if (!d_stamps) { HIP_TRY(hipMalloc((void **)&d_stamps, (size_t)8192 * 4 * 32 * 8)); }
-    HIP_TRY(hipMemsetAsync(d_stamps, 0, (size_t)8192 * 4 * 32 * 8, stream));
-    a.stamps = d_stamps;
-    g_fir_stamps = d_stamps; g_fir_stamp_waves = a.per_xcd * 8 * 4;
-#endif
-    return launch_timed(scope, lean ? (const void *)fir_tile<FMT, R, BIG, SPLIT, true> : (const void *)fir_tile<FMT, R, BIG, SPLIT, false>,
-                        dim3(a.per_xcd * 8), dim3(kBlock), lds, stream, a, stop);
+    const int lds = 4 * TileGeom<R, BIG>::LDS_DOUBLES * 8 + 64;              /* + the four words the waves exchange at the end */
+    v.push_back({{kFirTile, R, BIG, SPLIT, true}, (const void *)fir_tile<FMT, R, BIG, SPLIT, true>, lds, TileGeom<R, BIG>::FW, TileGeom<R, BIG>::WPC});
+    v.push_back({{kFirTile, R, BIG, SPLIT, false}, (const void *)fir_tile<FMT, R, BIG, SPLIT, false>, lds, TileGeom<R, BIG>::FW, TileGeom<R, BIG>::WPC});
 }
-
-
 template <int FMT, int R>
-int launch_fir_stream(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, hipStream_t stream)
+void add_fir_rows(std::vector<FirVariant> &v)
 {
-    if (!pl.d_ring64) {
-        /* first use: the operand ring (8 bytes per ring entry) is made from the float ring; every ring writer keeps it up from here on */
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMalloc((void **)&pl.d_ring64, (size_t)pl.nchains * 2 * pl.ring_R * sizeof(double)));      /* (every operand twice: Ring) */
-        RingConvArgs ca{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
-        hipLaunchKernelGGL(ring_widen, dim3(pl.n_fir), dim3(kBlock), 0, stream, ca);
-        HIP_TRY(hipGetLastError());
+    add_fir_tile<FMT, R, false, false>(v);
+    v.push_back({{kFirStream, R, false, false, false}, (const void *)fir_stream<FMT, R>, 4 * StreamGeom<R>::LDS_DOUBLES * 8 + 64, StreamGeom<R>::FW, 0});
+    v.push_back({{kFirFlow, R, false, false, false}, (const void *)fir_flow<FMT, R>, 4 * FlowGeom<R>::LDS_DOUBLES * 8 + 64, FlowGeom<R>::FW, FlowGeom<R>::WPC});
+    /* (format 4 stops at two row tiles of fir_shared: fir_shared_choice) */
+    if constexpr (FMT != 4 || R < 4) v.push_back({{kFirShared, R, false, false, false}, (const void *)fir_shared<FMT, R>, SharedGeom<R>::LDS_DOUBLES * 8, SharedGeom<R>::FW, 0});
+}
+template <int FMT>
+const std::vector<FirVariant> &fir_variants()
+{
+    static const std::vector<FirVariant> table = [] {
+        std::vector<FirVariant> v;
+        if constexpr (FMT == 4 || FMT == 6) {
+            add_fir_rows<FMT, 1>(v); add_fir_rows<FMT, 2>(v); add_fir_rows<FMT, 4>(v);
+            add_fir_tile<FMT, 1, true, false>(v); add_fir_tile<FMT, 1, false, true>(v);
+            v.push_back({{kFirFlow, 1, true, false, false}, (const void *)fir_flow<FMT, 1, true>, 4 * FlowGeom<1, true>::LDS_DOUBLES * 8 + 64, FlowGeom<1, true>::FW, FlowGeom<1, true>::WPC});
+            v.push_back({{kFirMfma, 1, false, false, false}, (const void *)fir_mfma<FMT, 1>, -1, 0, 0});
+            v.push_back({{kFirMfma, 2, false, false, false}, (const void *)fir_mfma<FMT, 2>, -1, 0, 0});
+            v.push_back({{kFirPlain, 1, false, false, false}, (const void *)fir_plain<FMT>, 0, 0, 0});
+        }
+        return v;
+    }();
+    return table;
+}
+template <int FMT>
+const FirVariant *fir_variant(const FirChoice &c)
+{
+    for (const FirVariant &v : fir_variants<FMT>()) if (v.c == c) return &v;
+    set_err("no FIR kernel of family %d with %d row tiles (%d %d %d) in format %d", c.family, c.R, c.BIG, c.SPLIT, c.LEAN, FMT);
+    return nullptr;
+}
+int fir_opt_in(int format, int gpc)
+{
+    int hs_cap, row;
+    for (const FirVariant &v : format == 4 ? fir_variants<4>() : fir_variants<6>()) {
+        const int lds = v.lds < 0 ? (int)fir_lds_bytes(gpc, &hs_cap, &row) : v.lds;
+        if (!lds) continue;
+        const hipError_t e = hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return set_err("hipFuncSetAttribute(FIR family %d, %d row tiles, LDS %d): %s", v.c.family, v.c.R, lds, hipGetErrorString(e));
     }
-    FirTileArgs a{};
-    a.buf = prog->d_buf; a.chains = pl.d_chains; a.group = ids; a.ngroup = n;
-    a.ring = plan_ring(pl); a.io = io; a.taps64 = pl.d_taps64; a.pitch64 = pl.pitch64;
-    if (pl.n_fir_only) {
-        const long long total = (long long)n * io.nframes;
-        hipLaunchKernelGGL(fir_feed<FMT>, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    /* one wave per SIMD at most: 256 workgroups of four waves, each wave takes its units in turn */
-    const int tiles = (io.nframes + StreamGeom<R>::FW - 1) / StreamGeom<R>::FW;
-    const int nwg = std::min((n * tiles + 3) / 4, prog->num_cus > 0 ? prog->num_cus : 256);
-    a.per_xcd = (nwg + 7) / 8;
-    const size_t lds = (size_t)4 * StreamGeom<R>::LDS_DOUBLES * sizeof(double) + 64;
-#ifdef AVDSP_FIR_STAMPS
-    static unsigned long long *d_stamps = nullptr;
-    if (!d_stamps) { HIP_TRY(hipMalloc((void **)&d_stamps, (size_t)8192 * 4 * 32 * 8)); }
-    HIP_TRY(hipMemsetAsync(d_stamps, 0, (size_t)8192 * 4 * 32 * 8, stream));
-    a.stamps = d_stamps;
-    g_fir_stamps = d_stamps; g_fir_stamp_waves = a.per_xcd * 8 * 4;
-#endif
-    hipLaunchKernelGGL((fir_stream<FMT, R>), dim3(a.per_xcd * 8), dim3(kStreamBlock), lds, stream, a);
-    HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <int FMT, int R, bool BIG = false>
-int launch_fir_flow(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, hipStream_t stream, ProfileScope &scope, bool wait_ready, hipEvent_t stop)
+/* what the launches of fir_tile, fir_stream and fir_flow share: the arguments ... */
+FirTileArgs fir_tile_args(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, bool wait_ready)
 {
-    if (!pl.d_ring64) {
-        /* first use: the operand ring is made from the float ring; every ring writer keeps it up from here on */
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMalloc((void **)&pl.d_ring64, (size_t)pl.nchains * 2 * pl.ring_R * sizeof(double)));
-        RingConvArgs ca{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
-        hipLaunchKernelGGL(ring_widen, dim3(pl.n_fir), dim3(kBlock), 0, stream, ca);
-        HIP_TRY(hipGetLastError());
-    }
     FirTileArgs a{};
     a.buf = prog->d_buf; a.chains = pl.d_chains; a.group = ids; a.ngroup = n;
     a.ring = plan_ring(pl); a.io = io; a.taps64 = pl.d_taps64; a.pitch64 = pl.pitch64;
     if (wait_ready) { a.ready = pl.d_ready; a.seq = pl.seq; a.timeouts = prog->d_ready_timeouts; a.ready_acquire = prog->ready_mode_now != 2 || prog->overlap >= 2; }
-    a.wpc_shift = FlowGeom<R, BIG>::WPC == 4 ? 2 : FlowGeom<R, BIG>::WPC == 2 ? 1 : 0;      /* (fir_flow keeps the 1024-frame arrangement) */
-    const int nwg = (n * FlowGeom<R, BIG>::WPC + 3) / 4;
-    a.per_xcd = (nwg + 7) / 8;
-    const size_t lds = (size_t)4 * FlowGeom<R, BIG>::LDS_DOUBLES * sizeof(double) + 64;
+    return a;
+}
+/* ... the operand ring of the latter two (8 bytes per ring entry, every operand twice: Ring), made from the float ring at first use;
+ * every ring writer keeps it up from there on ... */
+int ensure_operand_ring(avdsp_hip_prog *prog, Plan &pl, hipStream_t stream)
+{
+    if (pl.d_ring64) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(pl.d_ring64.alloc((size_t)pl.nchains * 2 * pl.ring_R));
+    RingConvArgs ca{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
+    hipLaunchKernelGGL(ring_widen, dim3(pl.n_fir), dim3(kBlock), 0, stream, ca);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* ... and, in a diagnostic build, the waves' stamps (a.per_xcd is set) */
+int fir_stamp_buffer([[maybe_unused]] FirTileArgs &a, [[maybe_unused]] hipStream_t stream)
+{
 #ifdef AVDSP_FIR_STAMPS
     static unsigned long long *d_stamps = nullptr;
     if (!d_stamps) { HIP_TRY(hipMalloc((void **)&d_stamps, (size_t)8192 * 4 * 32 * 8)); }
@@ -4612,7 +4553,14 @@ int launch_fir_flow(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, Block
     a.stamps = d_stamps;
     g_fir_stamps = d_stamps; g_fir_stamp_waves = a.per_xcd * 8 * 4;
 #endif
-    return launch_timed(scope, (const void *)fir_flow<FMT, R, BIG>, dim3(a.per_xcd * 8), dim3(kBlock), lds, stream, a, stop);
+    return 0;
+}
+int launch_fir_feed(const void *fn, FirTileArgs f, hipStream_t stream)     /* fir_feed<FMT>: chains without a cascade, their input into the rings */
+{
+    const long long total = (long long)f.ngroup * f.io.nframes;
+    void *kargs[] = {(void *)&f};
+    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096)), dim3(kBlock), kargs, 0, stream));
+    return 0;
 }
 
 /* The per-chain f64 taps of a plan whose FIR chains are all grouped are made when a launch first needs them (a fallback of the shared
@@ -4620,7 +4568,7 @@ int launch_fir_flow(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, Block
 int ensure_private_taps(avdsp_hip_prog *prog, Plan &pl, hipStream_t stream)
 {
     if (pl.d_taps64 || !pl.n_fir) return 0;
-    HIP_TRY(hipMalloc((void **)&pl.d_taps64, (size_t)pl.nchains * pl.pitch64 * sizeof(double)));
+    HIP_TRY(pl.d_taps64.alloc((size_t)pl.nchains * pl.pitch64));
     Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};
     hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, stream, ta);
     HIP_TRY(hipGetLastError());
@@ -4633,60 +4581,30 @@ bool shared_path(const avdsp_hip_prog *prog, const Plan &pl, int fir_impl)
     return pl.n_sh_groups > 0 && prog->fir_shared && fir_impl == 1 && !prog->overlap && !prog->fir_split && pl.instances <= 1;
 }
 
-/* fir_shared over every group of the plan: R by launch_fir's cost rule on this kernel's waves, ceil(C / 16) x ceil(B / 16 R) */
-template <int FMT, int R>
-int launch_fir_shared_r(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream, ProfileScope &scope)
-{
-    FirSharedArgs a{};
-    a.buf = prog->d_buf; a.chains = pl.d_chains; a.ids = pl.d_sh_ids; a.tiles = pl.d_sh_tiles; a.ntiles = pl.n_sh_tiles;
-    a.nfb = (io.nframes + SharedGeom<R>::FW - 1) / SharedGeom<R>::FW;
-    a.ring = plan_ring(pl); a.taps64 = pl.d_sh_taps64; a.pitch64 = pl.pitch64; a.io = io;
-    const long long nwg = (long long)a.ntiles * a.nfb;
-    a.per_xcd = (int)((nwg + 7) / 8);
-    prog->sh_rows_now = R;                            /* ("fir_shared_rows": launch_all sets the chains and groups beside it) */
-    return launch_timed(scope, (const void *)fir_shared<FMT, R>, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)SharedGeom<R>::LDS_DOUBLES * sizeof(double), stream, a);
-}
-
+/* fir_shared over every group of the plan: ceil(C / 16) x ceil(B / 16 R) workgroups */
 template <int FMT>
 int launch_fir_shared(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
 {
     if constexpr (FMT != 4 && FMT != 6) { (void)prog; (void)pl; (void)io; (void)stream; return set_err("fir_shared: formats 4 and 6 only"); }
     else {
-        if (pl.n_sh_feed) {                               /* grouped chains without a cascade: their input into the rings first (a chain's frames span workgroups) */
-            FirTileArgs f{};
-            f.buf = prog->d_buf; f.chains = pl.d_chains; f.group = pl.d_sh_feed; f.ngroup = pl.n_sh_feed; f.ring = plan_ring(pl); f.io = io;
-            const long long total = (long long)pl.n_sh_feed * io.nframes;
-            hipLaunchKernelGGL(fir_feed<FMT>, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, stream, f);
-            HIP_TRY(hipGetLastError());
-        }
+        /* grouped chains without a cascade: their input into the rings first (a chain's frames span workgroups) */
+        if (pl.n_sh_feed && launch_fir_feed((const void *)fir_feed<FMT>, fir_tile_args(prog, pl, pl.d_sh_feed, pl.n_sh_feed, io, false), stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
-        int rows = prog->fir_rows;
-        if (rows != 1 && rows != 2 && rows != 4) {
-            /* (launch_fir's rule: the chip holds 2048 such waves at a time -- two 64-KB workgroups per CU --, a wave of R row tiles lasts R
-             * units, the launch is over when its last round is; 0.90 / 0.84 / 0.79 of the pipe at 4 / 2 / 1 row tiles) */
-            double best = 1e30;
-            rows = 1;
-            for (int r : {4, 2, 1}) {
-                if (r > 1 && 32 * r >= io.nframes) continue;               /* a workgroup of twice the block would multiply zeros */
-                const long long waves = (long long)pl.n_sh_tiles * 4 * ((io.nframes + 64 * r - 1) / (64 * r));
-                const double cost = (double)((waves + 2047) / 2048) * r / (r == 4 ? 0.90 : r == 2 ? 0.84 : 0.79);
-                if (cost < best - 1e-9) { best = cost; rows = r; }
-            }
-        }
-        while (rows > 1 && 32 * rows >= io.nframes) rows >>= 1;
-        if constexpr (FMT == 4) {
-            /* (format 4 stops at two row tiles: with four, store_word_f4's epilogue takes the kernel to 256 VGPRs and spills) */
-            return rows >= 2 ? launch_fir_shared_r<FMT, 2>(prog, pl, io, stream, scope) : launch_fir_shared_r<FMT, 1>(prog, pl, io, stream, scope);
-        } else {
-            return rows == 4 ? launch_fir_shared_r<FMT, 4>(prog, pl, io, stream, scope)
-                 : rows == 2 ? launch_fir_shared_r<FMT, 2>(prog, pl, io, stream, scope)
-                             : launch_fir_shared_r<FMT, 1>(prog, pl, io, stream, scope);
-        }
+        const FirVariant *v = fir_variant<FMT>(fir_shared_choice(FMT, pl.n_sh_tiles, io.nframes, prog->fir_rows));
+        if (!v) return -1;
+        FirSharedArgs a{};
+        a.buf = prog->d_buf; a.chains = pl.d_chains; a.ids = pl.d_sh_ids; a.tiles = pl.d_sh_tiles; a.ntiles = pl.n_sh_tiles;
+        a.nfb = (io.nframes + v->fw - 1) / v->fw;
+        a.ring = plan_ring(pl); a.taps64 = pl.d_sh_taps64; a.pitch64 = pl.pitch64; a.io = io;
+        const long long nwg = (long long)a.ntiles * a.nfb;
+        a.per_xcd = (int)((nwg + 7) / 8);
+        prog->sh_rows_now = v->c.R;                       /* ("fir_shared_rows": launch_all sets the chains and groups beside it) */
+        return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, a);
     }
 }
 
 /* fir_impl: 0 = fir_plain (the reference's loop), 1 = fir_tile (default), 2 = fir_mfma (round 1's workgroup-per-channel kernel),
- * 3 = fir_stream, 4 = fir_flow */
+ * 3 = fir_stream, 4 = fir_flow; which variant of it: fir_choice (avdsp_plan_layout.h) */
 template <int FMT>
 int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, int fir_impl, hipStream_t stream, bool wait_ready = false, hipEvent_t stop = nullptr)
 {
@@ -4694,58 +4612,47 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
     else {
         if (ensure_private_taps(prog, pl, stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
-        if (fir_impl == 4) {
-            int rows = prog->fir_rows;
-            if (rows != 1 && rows != 2 && rows != 4) rows = n >= 2048 ? 4 : n >= 1024 ? 2 : 1;
-            while (rows > 1 && 128 * rows >= io.nframes) rows >>= 1;
-            if (rows == 1 && (long long)n * ((io.nframes + 255) / 256) <= 1024 && prog->fir_rows != 1)     /* at most a wave per SIMD: long chunks, two window images */
-                return launch_fir_flow<FMT, 1, true>(prog, pl, ids, n, io, stream, scope, wait_ready, stop);
-            return rows == 4 ? launch_fir_flow<FMT, 4>(prog, pl, ids, n, io, stream, scope, wait_ready, stop)
-                 : rows == 2 ? launch_fir_flow<FMT, 2>(prog, pl, ids, n, io, stream, scope, wait_ready, stop)
-                             : launch_fir_flow<FMT, 1>(prog, pl, ids, n, io, stream, scope, wait_ready, stop);
-        }
-        if (fir_impl != 1) scope.begin();
-        if (fir_impl == 3) {
-            /* row tiles per wave: as many as leave every SIMD a wave (1024) */
-            int rows = prog->fir_rows;
-            const int tiles1 = (io.nframes + 255) / 256;
-            if (rows != 1 && rows != 2 && rows != 4) rows = (long long)n * tiles1 >= 4 * 1024 ? 4 : (long long)n * tiles1 >= 2 * 1024 ? 2 : 1;
-            while (rows > 1 && 128 * rows >= io.nframes) rows >>= 1;
-            return rows == 4 ? launch_fir_stream<FMT, 4>(prog, pl, ids, n, io, stream)
-                 : rows == 2 ? launch_fir_stream<FMT, 2>(prog, pl, ids, n, io, stream)
-                             : launch_fir_stream<FMT, 1>(prog, pl, ids, n, io, stream);
-        }
-        if (fir_impl == 1) {
-            /* row tiles per wave: as many as leave the chip two waves per SIMD (2048) -- a bigger tile reads fewer operands per MFMA */
-            int rows = prog->fir_rows;
-            if (rows != 1 && rows != 2 && rows != 4) {
-                /* Round 5 (tools/regime_scan.sh): the chip holds 2048 of these waves at a time, a wave of R row tiles lasts R units, and a launch
-                 * is over when its LAST round of waves is -- 3000 chains at four row tiles were 1.46 rounds, i.e. two: 480 us, as long as 4096
-                 * chains.  So: the R with the fewest units, rounds(R) x R / efficiency(R) (0.90 / 0.84 / 0.79 of the matrix pipe at 4 / 2 / 1 row
-                 * tiles).  For 512 / 1024 / 2048 / 4096 / 16384 chains that is what the thresholds chose (1 / 2 / 4 / 4 / 4). */
-                double best = 1e30;
-                rows = 1;
-                for (int r : {4, 2, 1}) {
-                    if (r > 1 && 128 * r >= io.nframes) continue;           /* a tile twice the block would multiply zeros */
-                    const long long waves = (long long)n * ((io.nframes + 256 * r - 1) / (256 * r));
-                    const double cost = (double)((waves + 2047) / 2048) * r / (r == 4 ? 0.90 : r == 2 ? 0.84 : 0.79);
-                    if (cost < best - 1e-9) { best = cost; rows = r; }
-                }
+        const FirChoice c = fir_choice(fir_impl, n, io.nframes, FirOptions{prog->fir_rows, prog->fir_split, prog->fir_lean}, !pl.bq.empty(), (long long)pl.n_fir * pl.max_taps);
+        const FirVariant *v = fir_variant<FMT>(c);
+        if (!v) return -1;
+        if (c.family != kFirTile && c.family != kFirFlow) scope.begin();
+        const int cus = prog->num_cus > 0 ? prog->num_cus : 256;
+        if (c.family == kFirTile || c.family == kFirFlow) {
+            if (c.family == kFirFlow && ensure_operand_ring(prog, pl, stream)) return -1;
+            FirTileArgs a = fir_tile_args(prog, pl, ids, n, io, wait_ready);
+            int wpc = v->wpc;                             /* (fir_flow keeps the 1024-frame arrangement) */
+            if (c.family == kFirTile) {
+                /* the tiles a chain has in this launch (a power of two, so that a chain's waves sit in one workgroup): a short block is fewer
+                 * tiles than the TileGeom's 1024 frames, and waves without a tile would only hold their workgroup's LDS */
+                const int tiles = (io.nframes + v->fw - 1) / v->fw;
+                /* (BIG -- at most a wave per SIMD -- keeps the four-quarters arrangement: there a wave that leaves at once frees nothing anybody
+                 * waits for, and its workgroup's other waves sit on CUs of their own: 256 chains x 4096 taps at 64 .. 512 frames 36.3-37.6 us
+                 * against 38.1-38.8 regrouped) */
+                /* ... as long as its workgroups -- one per chain, one per CU: 140 KB of LDS -- fit the chip at once.  512 or 1024 chains at 256
+                 * frames are 512 / 1024 workgroups of ONE live wave each, two or four rounds of 36 us (a 512-chain shard's 256-frame block took
+                 * 91 us, longer than its 1024-frame block): those regroup like everybody else. */
+                const bool quarters = c.SPLIT || (c.BIG && n <= cus);
+                if (!quarters) wpc = tiles <= 1 ? 1 : tiles <= 2 ? std::min(2, wpc) : wpc;
+                a.all_cascaded = pl.n_fir_only == 0;
             }
-            while (rows > 1 && 128 * rows >= io.nframes) rows >>= 1;       /* a tile twice the block would multiply zeros */
-            /* one row tile and at most a wave per SIMD (1024): chunks twice as long -- nothing hides a boundary there */
-            const long long waves1 = (long long)n * ((io.nframes + 255) / 256);
-            /* "fir_split" (opt-in, not the reference's summation order): such a launch with two waves per tile instead */
-            /* the lean chunk boundary (fir_tile, LEAN) where it was measured to win (tools/fir_boundary_lab.sh, one box, long / lean):
-             * plans without cascades in front (256 chains x 4096 taps: 40.9 -> 39.4 us per step) and launches of more than one round of
-             * waves (4096 chains: 0.511 -> 0.506 ms).  In between, the next blocks' cascades run beside the FIR and live on the long
-             * boundary's bubbles: 2048 chains 0.259 -> 0.269 ms, 1024 chains 0.147 -> 0.154, 512 chains 0.0876 -> 0.0966. */
-            const bool lean = prog->fir_lean >= 0 ? prog->fir_lean != 0 : (pl.bq.empty() || (long long)pl.n_fir * pl.max_taps >= 12000000ll);
-            if (rows == 1 && waves1 <= 1024 && prog->fir_split) return launch_fir_tile<FMT, 1, false, true>(prog, pl, ids, n, io, stream, scope, wait_ready, stop, lean);
-            if (rows == 1 && waves1 <= 1024 && prog->fir_rows != 1) return launch_fir_tile<FMT, 1, true>(prog, pl, ids, n, io, stream, scope, wait_ready, stop, lean);
-            return rows == 4 ? launch_fir_tile<FMT, 4>(prog, pl, ids, n, io, stream, scope, wait_ready, stop, lean)
-                 : rows == 2 ? launch_fir_tile<FMT, 2>(prog, pl, ids, n, io, stream, scope, wait_ready, stop, lean)
-                             : launch_fir_tile<FMT, 1>(prog, pl, ids, n, io, stream, scope, wait_ready, stop, lean);
+            a.wpc_shift = wpc == 4 ? 2 : wpc == 2 ? 1 : 0;
+            const int nwg = (n * wpc * (c.SPLIT ? 2 : 1) + 3) / 4;
+            a.per_xcd = (nwg + 7) / 8;
+            if (fir_stamp_buffer(a, stream)) return -1;
+            return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, a, stop);
+        }
+        if (c.family == kFirStream) {
+            if (ensure_operand_ring(prog, pl, stream)) return -1;
+            FirTileArgs a = fir_tile_args(prog, pl, ids, n, io, false);
+            if (pl.n_fir_only && launch_fir_feed((const void *)fir_feed<FMT>, a, stream)) return -1;
+            /* one wave per SIMD at most: 256 workgroups of four waves, each wave takes its units in turn */
+            const int tiles = (io.nframes + v->fw - 1) / v->fw;
+            const int nwg = std::min((n * tiles + 3) / 4, cus);
+            a.per_xcd = (nwg + 7) / 8;
+            if (fir_stamp_buffer(a, stream)) return -1;
+            void *kargs[] = {(void *)&a};
+            HIP_TRY(hipLaunchKernel(v->fn, dim3(a.per_xcd * 8), dim3(kStreamBlock), kargs, (size_t)v->lds, stream));
+            return 0;
         }
         FirArgs a{};
         a.buf = prog->d_buf; a.chains = pl.d_chains; a.group = ids; a.ngroup = n;
@@ -4754,11 +4661,9 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
         const int nwaves = 4;                            /* always 4: idle tiles' waves still stage */
         a.gpc = pl.fir_gpc;
         size_t lds = 0;
-        if (fir_impl) lds = fir_lds_bytes(a.gpc, &a.hs_cap, &a.win_row);
-        /* LDS opt-in was done at plan creation.  Few workgroups per CU: the deeper operand sets */
-        auto kern = !fir_impl ? fir_plain<FMT> : (n <= 2 * 256 ? fir_mfma<FMT, 2> : fir_mfma<FMT, 1>);
-        hipLaunchKernelGGL(kern, dim3(a.per_xcd * 8), dim3(64 * nwaves), lds, stream, a);
-        HIP_TRY(hipGetLastError());
+        if (c.family == kFirMfma) lds = fir_lds_bytes(a.gpc, &a.hs_cap, &a.win_row);
+        void *kargs[] = {(void *)&a};
+        HIP_TRY(hipLaunchKernel(v->fn, dim3(a.per_xcd * 8), dim3(64 * nwaves), kargs, lds, stream));
         return 0;
     }
 }
@@ -4900,11 +4805,11 @@ static int overlap_ready(avdsp_hip_prog *prog)
 template <int FMT>
 int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, hipStream_t st, hipEvent_t last_stop, bool with_ready)
 {
-    /* (i) every cascade of up to 16 sections in ONE biquad_row launch, whatever their lengths (the table of all rows, Plan::d_rows_all):
+    /* (i) every cascade of up to 16 sections in ONE biquad_row launch, whatever their lengths (the table of all rows, Plan::rows_all):
      * 1024 chains with 1 .. 8 sections 248 -> 33 us.  (ii) what that does not cover -- 17 sections and more, or the options that take
      * biquad_row out -- as before, one launch per length, side by side over the streams. */
-    const bool merged = prog->group_fanout && biquad_impl == 1 && pl.d_rows_all;
-    /* one group on one stream: a launch -- or, for cascades of more than 64 sections, the group's pieces one after the other, the words
+    const bool merged = prog->group_fanout && biquad_impl == 1 && pl.rows_all.n;
+    /* one group on one stream: a launch -- or, for cascades of more than 16 sections, the group's pieces one after the other, the words
      * between them through the group's scratch columns */
     auto launch_group = [&](const Plan::Group &g, hipStream_t s, hipEvent_t stop) -> int {
         if (g.pieces.empty()) return launch_biquad<FMT>(prog, pl, g, g.d_ids, g.n, io, biquad_impl, s, stop, with_ready);
@@ -4921,7 +4826,7 @@ int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl,
     std::vector<const Plan::Group *> todo;
     for (auto &g : pl.bq) if (!(merged && g.P == 16 && g.d_rows)) todo.push_back(&g);
     if (merged) {
-        const Plan::Group m{16, 0, pl.n_rows_all, nullptr, pl.rows_all_fir, pl.d_rows_all, pl.d_lanes_all};
+        const Plan::Group &m = pl.rows_all;
         if (launch_biquad<FMT>(prog, pl, m, nullptr, m.n, io, biquad_impl, st, todo.empty() ? last_stop : nullptr, with_ready)) return -1;
         if (todo.empty()) return 0;
     }
@@ -5339,7 +5244,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
     if (!p) return;
     (void)fs_stop(p);
     (void)hipDeviceSynchronize();
-    for (auto &pl : p->plans) free_plan(pl);
+    p->plans.clear();
     for (auto &sp : p->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto e : p->free_events) (void)hipEventDestroy(e);
     (void)hipFree(p->d_table); (void)hipHostFree(p->h_table);
@@ -5373,389 +5278,136 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
     delete p;
 }
 
+/* device copies of a launch group's tables */
+static int upload_group(Plan::Group &g, const GroupLayout &l)
+{
+    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out;
+    return g.d_ids.upload(l.ids) || g.d_rows.upload(l.rows) || g.d_lanes.upload(l.lanes);
+}
+
+/* The tables are avdsp_plan_layout.h's, stage by stage; here they are uploaded, the plan's device memory is allocated, the FIR kernels
+ * are opted in and the conversion kernels run.  Whatever exit is taken, `pl` frees what it holds. */
 int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
 {
     FS_STOP(prog);
     if (d->format < 2 || d->format > 6) return set_err("format %d has no device kernels", d->format);
+    if (d->instances > 1 && d->instances != prog->chain_inst) return set_err("a plan of %d instances, the device holds %d copies of the program", d->instances, prog->chain_inst);
+#define STAGE(err) do { const std::string e_ = (err); if (!e_.empty()) return set_err("%s", e_.c_str()); } while (0)
+    /* every word index the kernels will touch must lie inside the mirror (chain instances: inside the copies, all of them) */
+    const long long buf_words = mirror_words(d, prog->total_words);
+    ChainTables t;
+    STAGE(check_heads(d, buf_words, t));
+    if (t.has_mux) {
+        std::vector<int> words((size_t)(t.mux_hi - t.mux_lo));
+        HIP_TRY(hipDeviceSynchronize());
+        if (copy_to_caller(words.data(), prog->d_buf + t.mux_lo, words.size() * 4)) return -1;
+        STAGE(mux_records(words, t));
+    }
+    STAGE(check_chains(d, buf_words, t));
     Plan pl;
     pl.format = d->format; pl.nchains = d->nchains; pl.store_mask = d->store_mask;
     pl.lane_mode = d->format == 3 || d->format == 5;
-    std::vector<avdsp_chain> chains(d->chains, d->chains + d->nchains);
-    std::vector<int> coef(d->sec_coef_word, d->sec_coef_word + d->nsections);
-    std::vector<int> state(d->sec_state_word, d->sec_state_word + d->nsections);
-    /* every word index the kernels will touch must lie inside the mirror (chain instances: inside the copies, all of them) */
-    const long long buf_words = d->instances > 1 ? (long long)AVDSP_INSTANCE_STRIDE(prog->total_words) * d->instances : (long long)prog->total_words;
-    if (d->instances > 1 && d->instances != prog->chain_inst) return set_err("a plan of %d instances, the device holds %d copies of the program", d->instances, prog->chain_inst);
     pl.instances = d->instances > 1 ? d->instances : 1;
-    for (int i = 0; i < d->nsections; i++)
-        if (coef[i] < 0 || coef[i] + 5 > buf_words || state[i] < 0 || state[i] + 6 > buf_words || (state[i] & 1))
-            return set_err("section %d addresses words outside the loaded buffer", i);
-    std::vector<std::pair<int, std::vector<int>>> byN;   /* (section count, chain ids) in first-seen order */
-    std::vector<int> fir, pass;
-    pl.io_in_min = pl.io_out_min = 0x7FFFFFFF; pl.io_in_max = pl.io_out_max = -1;
-    /* LOAD_MUX chain heads: the stage's records; every chain of the plan then reads column i of the stage's scratch block -- a chain with
-     * a filter the word the stage has formed (kLoadRaw), a LOAD / LOAD_GAIN chain beside them its sample word, copied there */
-    std::vector<MuxRec> mux_recs;
-    std::vector<char> mux_stored(d->nchains, 0);
-    for (int i = 0; i < d->nchains; i++) {
-        if (chains[i].load_mode != AVDSP_LOAD_PLAIN && chains[i].load_mode != AVDSP_LOAD_GAIN && chains[i].load_mode != AVDSP_LOAD_MUX)
-            return set_err("chain %d: load mode %d", i, chains[i].load_mode);
-        pl.has_mux = pl.has_mux || chains[i].load_mode == AVDSP_LOAD_MUX;
-    }
-    if (pl.has_mux) {
-        if (pl.lane_mode) return set_err("LOAD_MUX chains have no kernels in format %d", d->format);
-        if (d->instances > 1) return set_err("LOAD_MUX chains have no chain instances");
-        int lo = 0x7FFFFFFF, hi = 0;                     /* the mirror words that hold the lists */
-        for (int i = 0; i < d->nchains; i++) {
-            const avdsp_chain &c = chains[i];
-            if (c.load_mode != AVDSP_LOAD_MUX) continue;
-            if (c.mux_count < 1 || c.mux_count > 32767 || c.mux_word < 0 || (long long)c.mux_word + 2ll * c.mux_count > buf_words ||
-                c.mux_result_word < 0 || (long long)c.mux_result_word + 2 > buf_words)
-                return set_err("chain %d: LOAD_MUX list or result word outside the loaded buffer", i);
-            lo = std::min(lo, c.mux_word); hi = std::max(hi, c.mux_word + 2 * c.mux_count);
-        }
-        std::vector<int> words((size_t)(hi - lo));
-        HIP_TRY(hipDeviceSynchronize());
-        if (copy_to_caller(words.data(), prog->d_buf + lo, words.size() * 4)) return -1;
-        mux_recs.resize(d->nchains);
-        for (int i = 0; i < d->nchains; i++) {
-            avdsp_chain &c = chains[i];
-            MuxRec r{};
-            r.sat = c.sat; r.n_out = c.n_out;
-            for (int k = 0; k < AVDSP_MAX_STORES; k++) r.out_io[k] = c.out_io[k];
-            if (c.load_mode == AVDSP_LOAD_MUX) {
-                for (int k = 0; k < c.mux_count; k++) {
-                    const int io = words[(size_t)(c.mux_word - lo) + 2 * k];
-                    if (io < 0) return set_err("chain %d: LOAD_MUX entry %d names IO %d", i, k, io);
-                    pl.io_in_min = std::min(pl.io_in_min, io); pl.io_in_max = std::max(pl.io_in_max, io);
-                }
-                r.list_word = c.mux_word; r.count = c.mux_count; r.result_word = c.mux_result_word;
-                r.col = (c.nsec || c.fir_taps) ? i : -1;
-                if (r.col < 0) { mux_stored[i] = 1; pl.n_mux_stored++; }
-                c.load_mode = kLoadRaw;
-            } else {
-                if (c.in_io < 0) return set_err("chain %d: bad IO", i);
-                pl.io_in_min = std::min(pl.io_in_min, c.in_io); pl.io_in_max = std::max(pl.io_in_max, c.in_io);
-                r.list_word = c.in_io; r.count = 0; r.col = i;
-            }
-            c.in_io = i;
-            mux_recs[i] = r;
-        }
-    }
-    for (int i = 0; i < d->nchains; i++) {
-        const avdsp_chain &c = chains[i];
-        if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return set_err("chain %d: bad section range", i);
-        if (c.n_out < 1 || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return set_err("chain %d: bad IO", i);
-        if (!pl.has_mux) { pl.io_in_min = std::min(pl.io_in_min, c.in_io); pl.io_in_max = std::max(pl.io_in_max, c.in_io); }
-        for (int k = 0; k < c.n_out; k++) {
-            if (c.out_io[k] < 0) return set_err("chain %d: bad IO", i);
-            pl.io_out_min = std::min(pl.io_out_min, c.out_io[k]); pl.io_out_max = std::max(pl.io_out_max, c.out_io[k]);
-        }
-        if (c.fir_taps) {
-            if (d->format == 2) return set_err("chain %d: FIR has no int64 definition", i);
-            if (c.fir_coef_word < 0 || c.fir_coef_word + c.fir_taps > buf_words ||
-                c.fir_state_word < 0 || c.fir_state_word + c.fir_taps > buf_words)
-                return set_err("chain %d: FIR addresses words outside the loaded buffer", i);
-            fir.push_back(i);
-            pl.max_taps = std::max(pl.max_taps, c.fir_taps);
-        }
-        if (c.nsec) {
-            auto it = std::find_if(byN.begin(), byN.end(), [&](const auto &e) { return e.first == c.nsec; });
-            if (it == byN.end()) { byN.push_back({c.nsec, {}}); it = byN.end() - 1; }
-            it->second.push_back(i);
-        } else if (!c.fir_taps && !mux_stored[i]) pass.push_back(i);
-    }
-    if (upload_vec(&pl.d_sec_coef, coef) || upload_vec(&pl.d_sec_state, state)) { free_plan(pl); return -1; }
-    if (pl.lane_mode && upload_vec(&pl.d_chains, chains)) { free_plan(pl); return -1; }
-    std::vector<avdsp_chain> dev_chains = chains;        /* what the kernels see: the host's records + the pieces of long cascades (below) */
+    pl.has_mux = t.has_mux; pl.n_mux_stored = t.n_mux_stored; pl.max_taps = t.max_taps;
+    pl.io_in_min = t.io_in_min; pl.io_in_max = t.io_in_max; pl.io_out_min = t.io_out_min; pl.io_out_max = t.io_out_max;
+    if (pl.d_sec_coef.upload(t.coef) || pl.d_sec_state.upload(t.state)) return -1;
     if (pl.lane_mode) {                                  /* no launch groups, no rings: chain_lane walks the chain list itself */
-        pl.n_lane_fir = (int)fir.size();             /* (n_fir stays 0: that one counts chains with a ring) */
+        pl.n_lane_fir = (int)t.fir.size();               /* (n_fir stays 0: that one counts chains with a ring) */
         std::vector<int> rows;
-        for (int i = 0; i < d->nchains; i++) if (chains[i].nsec >= 1 && chains[i].nsec <= 16) rows.push_back(i);
+        for (int i = 0; i < d->nchains; i++) if (t.chains[i].nsec >= 1 && t.chains[i].nsec <= 16) rows.push_back(i);
         pl.n_lane_rows = (int)rows.size();
-        for (int i = 0; i < d->nchains; i++) pl.n_lane_feed += chains[i].nsec == 0 && chains[i].fir_taps != 0;
-        if (upload_vec(&pl.d_lane_rows, rows)) { free_plan(pl); return -1; }
-        prog->plans.push_back(pl);
+        for (int i = 0; i < d->nchains; i++) pl.n_lane_feed += t.chains[i].nsec == 0 && t.chains[i].fir_taps != 0;
+        if (pl.d_chains.upload(t.chains) || pl.d_lane_rows.upload(rows)) return -1;
+        prog->plans.push_back(std::move(pl));
         return (int)prog->plans.size() - 1;
     }
-    std::vector<RowRec> all_rows; std::vector<LaneRec> all_lanes;
-    for (auto &e : byN) {                                /* > 64 sections (P = 128): pieces of up to 64, below */
-        /* lanes per chain: the next power of two -- but a 16-lane row per chain while the chip has SIMDs to spare
-         * (<= 1024 waves): its step is shorter (one input batch per 16 steps, no mid-row section-0 lanes: cfg5's
-         * 8-section cascades 85 -> 62 us) and idle lanes cost nothing there */
-        int P = e.first > 64 ? 128 : pow2ceil(e.first);
-        if (P < 16 && (long long)e.second.size() * 16 <= 65536) P = 16;
-        bool all_fir = true;
-        for (int id : e.second) all_fir = all_fir && chains[id].fir_taps != 0;
-        Plan::Group g{P, e.first, (int)e.second.size(), nullptr, all_fir, nullptr, nullptr};
-        if (upload_vec(&g.d_ids, e.second)) { free_plan(pl); return -1; }
-        /* ... and in format 6 every cascade of more than 16 sections runs as pieces of up to 16, each a biquad_row launch: the word between two
-         * sections is a float there and a plain LOAD / STORE pair moves it unchanged, so biquad_row takes the pieces as they are; a 16-lane row
-         * per chain wastes no lanes on lengths like 17 or 33 (biquad_pipe: 32 / 64 lanes per chain) and its step is the shorter one --
-         * 4096 chains x 17 / 33 / 48 / 65 / 200 sections: see DESIGN.md 4.1.  (Formats 2 and 4: pieces only beyond 64 sections, through biquad_pipe.) */
-        const int piece_max = 16;
-        if (e.first > piece_max) {
-            /* A cascade of more than 64 sections does not fit a wave's lanes.  biquad_simple (a lane per chain, state in memory) took 81 ms
-             * for 4096 chains x 65 sections against 136 us for 64: the chain is CUT instead, into pieces of equal length (+- 1) that run as
-             * launches of biquad_pipe one after the other.  The pieces but the last are chain records of their own behind the host's
-             * (no FIR, no SAT0DB, one raw store into the scratch column); the last piece is the chain's own record with its input moved
-             * to the scratch column (its ring, stores and ready word are the chain's). */
-            const int np = (e.first + piece_max - 1) / piece_max, base = e.first / np, extra = e.first % np, n = (int)e.second.size();
-            int at = 0;
-            for (int k = 0; k < np; k++) {
-                const int len = base + (k < extra ? 1 : 0);
-                std::vector<int> ids(n);
-                for (int j = 0; j < n; j++) {
-                    const avdsp_chain &c = chains[e.second[j]];
-                    avdsp_chain pc = c;
-                    pc.sec_base = c.sec_base + at; pc.nsec = len;
-                    if (k > 0) { pc.in_io = j; pc.load_mode = kLoadRaw; }
-                    if (k + 1 < np) {
-                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j;
-                        ids[j] = (int)dev_chains.size(); dev_chains.push_back(pc);
-                    } else { ids[j] = e.second[j]; dev_chains[e.second[j]] = pc; }
-                }
-                Plan::Group pg{len <= 16 ? 16 : pow2ceil(len), len, n, nullptr, k + 1 == np && all_fir, nullptr, nullptr};
-                pg.raw_out = k + 1 < np;
-                auto drop = [&]() { (void)hipFree(g.d_ids); (void)hipFree(pg.d_ids); (void)hipFree(pg.d_rows); (void)hipFree(pg.d_lanes);
-                                    for (auto &x : g.pieces) { (void)hipFree(x.d_ids); (void)hipFree(x.d_rows); (void)hipFree(x.d_lanes); } free_plan(pl); };
-                if (upload_vec(&pg.d_ids, ids)) { drop(); return -1; }
-                if (pg.P == 16) {                        /* biquad_row's records of the piece (format 6: kLoadRaw reads as a plain load there, and is one) */
-                    std::vector<RowRec> rows(n);
-                    std::vector<LaneRec> lanes((size_t)n * 16, LaneRec{-1, -1});
-                    for (int j = 0; j < n; j++) {
-                        const avdsp_chain &c = dev_chains[ids[j]];
-                        /* bit 8: SAT0DB in front of the store -- in the int64 kernel "the stored word is acc >> 28", which is also what a piece
-                         * hands on (bit 10 then takes the dither mask off); in the double kernels a piece's word is the float as it is: no bit 8 */
-                        const bool raw = c.sat == kStoreRaw;
-                        rows[j] = RowRec{ids[j], c.in_io, c.out_io[0], (c.load_mode & 0xFF) | ((c.sat == 1 || (raw && d->format == 2)) ? 1 << 8 : 0) | (c.fir_taps ? 1 << 9 : 0) |
-                                         (raw ? 1 << 10 : 0) | (c.n_out << 16), c.gain_bits, {c.nsec, 0, 0}};
-                        for (int q = 0; q < c.nsec; q++) lanes[(size_t)j * 16 + (16 - c.nsec) + q] = LaneRec{coef[c.sec_base + q], state[c.sec_base + q]};
-                    }
-                    if (upload_vec(&pg.d_rows, rows) || upload_vec(&pg.d_lanes, lanes)) { drop(); return -1; }
-                }
-                g.pieces.push_back(pg);
-                at += len;
-            }
-            for (int k = 0; k < 2; k++)
-                if (hipMalloc((void **)&g.d_scratch[k], (size_t)kFirChunk * n * sizeof(unsigned)) != hipSuccess) {
-                    (void)hipFree(g.d_ids); (void)hipFree(g.d_scratch[0]); for (auto &x : g.pieces) { (void)hipFree(x.d_ids); (void)hipFree(x.d_rows); (void)hipFree(x.d_lanes); } free_plan(pl);
-                    return set_err("hipMalloc(scratch of %d long cascades)", n);
-                }
-        }
-        if (P == 16 && g.pieces.empty()) {               /* what biquad_row loads instead of walking group -> chain -> section tables */
-            std::vector<RowRec> rows(e.second.size());
-            std::vector<LaneRec> lanes(e.second.size() * 16, LaneRec{-1, -1});
-            for (size_t i = 0; i < e.second.size(); i++) {
-                const avdsp_chain &c = chains[e.second[i]];
-                rows[i] = RowRec{e.second[i], c.in_io, c.out_io[0], (c.load_mode & 0xFF) | (c.sat ? 1 << 8 : 0) | (c.fir_taps ? 1 << 9 : 0) | (c.n_out << 16),
-                                 c.gain_bits, {c.nsec, 0, 0}};
-                for (int k = 0; k < c.nsec; k++) lanes[i * 16 + (16 - c.nsec) + k] = LaneRec{coef[c.sec_base + k], state[c.sec_base + k]};
-            }
-            if (upload_vec(&g.d_rows, rows) || upload_vec(&g.d_lanes, lanes)) { (void)hipFree(g.d_ids); (void)hipFree(g.d_rows); free_plan(pl); return -1; }
-            /* ... and the same rows in the table of all lengths: this run, filled up to whole waves */
-            all_rows.insert(all_rows.end(), rows.begin(), rows.end());
-            all_lanes.insert(all_lanes.end(), lanes.begin(), lanes.end());
-            /* (an empty row is a copy of a real one with no chain behind it: every lane of a wave FETCHES, section or not -- its input
-             * column must be one the block has; nothing of it is stored) */
-            RowRec empty = rows[0]; empty.cid = -1;
-            while (all_rows.size() % 4) { all_rows.push_back(empty); all_lanes.insert(all_lanes.end(), 16, LaneRec{-1, -1}); }
-            pl.n_row_groups++;
-            pl.rows_all_fir = pl.rows_all_fir && all_fir;
-        }
-        pl.bq.push_back(g);
+    const CascadeLayout L = cascade_groups(d->format, t);
+    const SharedLayout S = shared_fir_layout(d, t);
+    STAGE(S.err);
+    const MuxLayout M = t.has_mux ? mux_tiles(d, t) : MuxLayout{};
+    STAGE(M.err);
+#undef STAGE
+    for (const GroupLayout &l : L.groups) {
+        Plan::Group g;
+        if (upload_group(g, l)) return -1;
+        for (const GroupLayout &pc : l.pieces) { g.pieces.emplace_back(); if (upload_group(g.pieces.back(), pc)) return -1; }
+        if (!l.pieces.empty())
+            for (auto &sc : g.d_scratch) if (sc.alloc((size_t)kFirChunk * l.n) != hipSuccess) return set_err("hipMalloc(scratch of %d long cascades)", l.n);
+        pl.bq.push_back(std::move(g));
     }
-    if (upload_vec(&pl.d_chains, dev_chains)) { free_plan(pl); return -1; }
-    if (pl.n_row_groups >= 2) {
-        RowRec empty = all_rows.back(); empty.cid = -1;
-        while (all_rows.size() % 16) { all_rows.push_back(empty); all_lanes.insert(all_lanes.end(), 16, LaneRec{-1, -1}); }
-        pl.n_rows_all = (int)all_rows.size();
-        if (upload_vec(&pl.d_rows_all, all_rows) || upload_vec(&pl.d_lanes_all, all_lanes)) { free_plan(pl); return -1; }
+    if (pl.d_chains.upload(L.dev_chains)) return -1;
+    if (!L.all_rows.empty()) {
+        pl.rows_all.P = 16; pl.rows_all.n = (int)L.all_rows.size(); pl.rows_all.all_fir = L.rows_all_fir;
+        if (pl.rows_all.d_rows.upload(L.all_rows) || pl.rows_all.d_lanes.upload(L.all_lanes)) return -1;
     }
-    pl.n_fir = (int)fir.size(); pl.n_pass = (int)pass.size();
-    if (upload_vec(&pl.d_fir_ids, fir) || upload_vec(&pl.d_pass_ids, pass)) { free_plan(pl); return -1; }
+    pl.n_fir = (int)t.fir.size(); pl.n_pass = (int)t.pass.size();
+    if (pl.d_fir_ids.upload(t.fir) || pl.d_pass_ids.upload(t.pass)) return -1;
     if (pl.n_fir) {
         pl.fir_gpc = fir_groups_per_chunk(pl.max_taps);
-        {   /* nothing in the launch path may touch function attributes (stream capture) */
-            int hs_cap, row;
-            const int lds = (int)fir_lds_bytes(pl.fir_gpc, &hs_cap, &row);
-            const void *variants[2] = { d->format == 4 ? (const void *)fir_mfma<4, 1> : (const void *)fir_mfma<6, 1>,
-                                        d->format == 4 ? (const void *)fir_mfma<4, 2> : (const void *)fir_mfma<6, 2> };
-            for (const void *fn : variants) {
-                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                if (e != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(LDS %d): %s", lds, hipGetErrorString(e)); }
-            }
-        }
-        /* + one more launch of frames: under "overlap" the cascade appends block k+1 while the FIR still reads block k's window */
-        pl.ring_R = pow2ceil(pl.max_taps + avdsp_hip_prog::kAhead * kFirChunk + 16 * pl.fir_gpc + 16 * (kNG + 4) + 64);
+        pl.ring_R = ring_length(pl.max_taps);
+        pl.pitch64 = taps64_pitch(pl.max_taps);
         static_assert(kFirChunk == kFirPad, "one FIR launch covers exactly the frames the window image is laid out for");
-        hipError_t e = hipMalloc((void **)&pl.d_ring, (size_t)d->nchains * 2 * pl.ring_R * sizeof(float));      /* (every sample twice: Ring) */
-        if (e != hipSuccess) { free_plan(pl); return set_err("hipMalloc(FIR rings, %d x %d): %s", d->nchains, pl.ring_R, hipGetErrorString(e)); }
+        if (fir_opt_in(d->format, pl.fir_gpc)) return -1;
+        hipError_t e = pl.d_ring.alloc((size_t)d->nchains * 2 * pl.ring_R);      /* (every sample twice: Ring) */
+        if (e != hipSuccess) return set_err("hipMalloc(FIR rings, %d x %d): %s", d->nchains, pl.ring_R, hipGetErrorString(e));
         pl.wpos = 0;
-        for (int i = 0; i < d->nchains; i++) pl.n_fir_only += chains[i].fir_taps && !chains[i].nsec;
-        {
-            const void *fns[3] = { d->format == 4 ? (const void *)fir_stream<4, 1> : (const void *)fir_stream<6, 1>,
-                                   d->format == 4 ? (const void *)fir_stream<4, 2> : (const void *)fir_stream<6, 2>,
-                                   d->format == 4 ? (const void *)fir_stream<4, 4> : (const void *)fir_stream<6, 4> };
-            const int flds[3] = { 4 * StreamGeom<1>::LDS_DOUBLES * 8 + 64, 4 * StreamGeom<2>::LDS_DOUBLES * 8 + 64, 4 * StreamGeom<4>::LDS_DOUBLES * 8 + 64 };
-            for (int v = 0; v < 3; v++) {
-                hipError_t e2 = hipFuncSetAttribute(fns[v], hipFuncAttributeMaxDynamicSharedMemorySize, flds[v]);
-                if (e2 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_stream LDS %d): %s", flds[v], hipGetErrorString(e2)); }
-            }
-            const void *ffn[4] = { d->format == 4 ? (const void *)fir_flow<4, 1> : (const void *)fir_flow<6, 1>,
-                                   d->format == 4 ? (const void *)fir_flow<4, 2> : (const void *)fir_flow<6, 2>,
-                                   d->format == 4 ? (const void *)fir_flow<4, 4> : (const void *)fir_flow<6, 4>,
-                                   d->format == 4 ? (const void *)fir_flow<4, 1, true> : (const void *)fir_flow<6, 1, true> };
-            const int fl[4] = { 4 * FlowGeom<1>::LDS_DOUBLES * 8 + 64, 4 * FlowGeom<2>::LDS_DOUBLES * 8 + 64, 4 * FlowGeom<4>::LDS_DOUBLES * 8 + 64,
-                                4 * FlowGeom<1, true>::LDS_DOUBLES * 8 + 64 };
-            for (int v = 0; v < 4; v++) {
-                hipError_t e2 = hipFuncSetAttribute(ffn[v], hipFuncAttributeMaxDynamicSharedMemorySize, fl[v]);
-                if (e2 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_flow LDS %d): %s", fl[v], hipGetErrorString(e2)); }
-            }
+        for (int i = 0; i < d->nchains; i++) pl.n_fir_only += t.chains[i].fir_taps && !t.chains[i].nsec;
+        /* the taps as doubles: a row per group of fir_shared ... */
+        pl.n_sh_groups = (int)S.reps.size(); pl.n_sh_chains = (int)S.ids.size(); pl.n_sh_tiles = (int)S.tiles.size();
+        pl.n_sh_feed = (int)S.feed.size(); pl.n_fir_rest = (int)S.rest.size();
+        if (pl.n_sh_groups) {
+            if (pl.d_sh_ids.upload(S.ids) || pl.d_sh_tiles.upload(S.tiles) || pl.d_sh_feed.upload(S.feed) || pl.d_fir_rest.upload(S.rest)) return -1;
+            e = pl.d_sh_taps64.alloc((size_t)pl.n_sh_groups * pl.pitch64);
+            if (e != hipSuccess) return set_err("hipMalloc(f64 taps of %d groups): %s", pl.n_sh_groups, hipGetErrorString(e));
+            DevArr<int> d_reps;
+            if (d_reps.upload(S.reps)) return -1;
+            Taps64Args tg{prog->d_buf, pl.d_chains, d_reps, pl.d_sh_taps64, pl.pitch64, 1};
+            hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_sh_groups), dim3(kBlock), 0, nullptr, tg);
+            const bool launched = hipGetLastError() == hipSuccess;
+            (void)hipDeviceSynchronize();
+            if (!launched) return set_err("taps_to_f64 (groups) failed to launch");
         }
-        {   /* fir_tile: LDS opt-in per variant, and the taps as doubles */
-            {
-                const bool f4 = d->format == 4;
-                const void *more[6] = { f4 ? (const void *)fir_tile<4, 1, false, true> : (const void *)fir_tile<6, 1, false, true>,
-                                        f4 ? (const void *)fir_tile<4, 1, false, true, false> : (const void *)fir_tile<6, 1, false, true, false>,
-                                        f4 ? (const void *)fir_tile<4, 1, false, false, false> : (const void *)fir_tile<6, 1, false, false, false>,
-                                        f4 ? (const void *)fir_tile<4, 2, false, false, false> : (const void *)fir_tile<6, 2, false, false, false>,
-                                        f4 ? (const void *)fir_tile<4, 4, false, false, false> : (const void *)fir_tile<6, 4, false, false, false>,
-                                        f4 ? (const void *)fir_tile<4, 1, true, false, false> : (const void *)fir_tile<6, 1, true, false, false> };
-                const int mlds[6] = { 4 * TileGeom<1>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<1>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<1>::LDS_DOUBLES * 8 + 64,
-                                      4 * TileGeom<2>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<4>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<1, true>::LDS_DOUBLES * 8 + 64 };
-                for (int v = 0; v < 6; v++) {
-                    hipError_t e3 = hipFuncSetAttribute(more[v], hipFuncAttributeMaxDynamicSharedMemorySize, mlds[v]);
-                    if (e3 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_tile LDS): %s", hipGetErrorString(e3)); }
-                }
-            }
-            const void *tiles[4] = { d->format == 4 ? (const void *)fir_tile<4, 1> : (const void *)fir_tile<6, 1>,
-                                     d->format == 4 ? (const void *)fir_tile<4, 2> : (const void *)fir_tile<6, 2>,
-                                     d->format == 4 ? (const void *)fir_tile<4, 4> : (const void *)fir_tile<6, 4>,
-                                     d->format == 4 ? (const void *)fir_tile<4, 1, true> : (const void *)fir_tile<6, 1, true> };
-            const int tlds[4] = { 4 * TileGeom<1>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<2>::LDS_DOUBLES * 8 + 64, 4 * TileGeom<4>::LDS_DOUBLES * 8 + 64,
-                                  4 * TileGeom<1, true>::LDS_DOUBLES * 8 + 64 };
-            for (int v = 0; v < 4; v++) {
-                hipError_t e2 = hipFuncSetAttribute(tiles[v], hipFuncAttributeMaxDynamicSharedMemorySize, tlds[v]);
-                if (e2 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_tile LDS %d): %s", tlds[v], hipGetErrorString(e2)); }
-            }
-            pl.pitch64 = taps64_pitch(pl.max_taps);
-            /* fir_shared: the host's groups of chains on one impulse bank -- a taps row per group, column groups of <= 16 chains */
-            if (d->fir_ngroups > 0 && d->fir_group_start && d->fir_group_chains && pl.instances <= 1 && (d->format == 4 || d->format == 6)) {
-                std::vector<int> sh_ids, feed, rest, reps;
-                std::vector<SharedTile> tiles;
-                std::vector<char> in_group(d->nchains, 0);
-                for (int g = 0; g < d->fir_ngroups; g++) {
-                    const int b = d->fir_group_start[g], e = d->fir_group_start[g + 1];
-                    if (b < 0 || e < b || e - b < AVDSP_FIR_GROUP_MIN) { free_plan(pl); return set_err("FIR group %d: %d chains", g, e - b); }
-                    const int c0 = d->fir_group_chains[b];
-                    for (int j = b; j < e; j++) {
-                        const int ci = d->fir_group_chains[j];
-                        if (ci < 0 || ci >= d->nchains || in_group[ci] || !chains[ci].fir_taps || chains[ci].fir_taps != chains[c0].fir_taps ||
-                            chains[ci].fir_coef_word != chains[c0].fir_coef_word) { free_plan(pl); return set_err("FIR group %d: chain %d is not one of its bank", g, ci); }
-                        in_group[ci] = 1;
-                        if (!chains[ci].nsec) feed.push_back(ci);
-                    }
-                    const int gi = (int)reps.size();
-                    reps.push_back(c0);
-                    for (int j = b; j < e; j += 16)
-                        tiles.push_back(SharedTile{gi, (int)sh_ids.size() + (j - b), std::min(16, e - j), chains[c0].fir_taps});
-                    sh_ids.insert(sh_ids.end(), d->fir_group_chains + b, d->fir_group_chains + e);
-                }
-                for (int ci : fir) if (!in_group[ci]) rest.push_back(ci);
-                pl.n_sh_groups = (int)reps.size(); pl.n_sh_chains = (int)sh_ids.size(); pl.n_sh_tiles = (int)tiles.size();
-                pl.n_sh_feed = (int)feed.size(); pl.n_fir_rest = (int)rest.size();
-                if (upload_vec(&pl.d_sh_ids, sh_ids) || upload_vec(&pl.d_sh_tiles, tiles) || upload_vec(&pl.d_sh_feed, feed) ||
-                    upload_vec(&pl.d_fir_rest, rest)) { free_plan(pl); return -1; }
-                int *d_reps = nullptr;
-                hipError_t e4 = hipMalloc((void **)&pl.d_sh_taps64, (size_t)pl.n_sh_groups * pl.pitch64 * sizeof(double));
-                if (e4 != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 taps of %d groups): %s", pl.n_sh_groups, hipGetErrorString(e4)); }
-                if (upload_vec(&d_reps, reps)) { free_plan(pl); return -1; }
-                Taps64Args tg{prog->d_buf, pl.d_chains, d_reps, pl.d_sh_taps64, pl.pitch64, 1};
-                hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_sh_groups), dim3(kBlock), 0, nullptr, tg);
-                const bool launched = hipGetLastError() == hipSuccess;
-                (void)hipDeviceSynchronize();
-                (void)hipFree(d_reps);
-                if (!launched) { free_plan(pl); return set_err("taps_to_f64 (groups) failed to launch"); }
-                const void *sfn[3] = { d->format == 4 ? (const void *)fir_shared<4, 1> : (const void *)fir_shared<6, 1>,
-                                       d->format == 4 ? (const void *)fir_shared<4, 2> : (const void *)fir_shared<6, 2>,
-                                       (const void *)fir_shared<6, 4> };
-                const int slds[3] = { SharedGeom<1>::LDS_DOUBLES * 8, SharedGeom<2>::LDS_DOUBLES * 8, SharedGeom<4>::LDS_DOUBLES * 8 };
-                for (int v = 0; v < (d->format == 4 ? 2 : 3); v++) {
-                    hipError_t e5 = hipFuncSetAttribute(sfn[v], hipFuncAttributeMaxDynamicSharedMemorySize, slds[v]);
-                    if (e5 != hipSuccess) { free_plan(pl); return set_err("hipFuncSetAttribute(fir_shared LDS %d): %s", slds[v], hipGetErrorString(e5)); }
-                }
-            }
-            /* the per-chain rows: today's, unless every FIR chain is grouped and the shared path is on (then ensure_private_taps, if ever) */
-            if (!(pl.n_sh_groups > 0 && pl.n_fir_rest == 0 && prog->fir_shared)) {
-                hipError_t e2 = hipMalloc((void **)&pl.d_taps64, (size_t)d->nchains * pl.pitch64 * sizeof(double));
-                if (e2 != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 taps, %d x %d): %s", d->nchains, pl.pitch64, hipGetErrorString(e2)); }
-                Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};
-                hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ta);
-                if (hipGetLastError() != hipSuccess) { free_plan(pl); return set_err("taps_to_f64 failed to launch"); }
-            }
+        /* ... and the per-chain rows, unless every FIR chain is grouped and the shared path is on (then ensure_private_taps, if ever) */
+        if (!(pl.n_sh_groups > 0 && pl.n_fir_rest == 0 && prog->fir_shared)) {
+            e = pl.d_taps64.alloc((size_t)d->nchains * pl.pitch64);
+            if (e != hipSuccess) return set_err("hipMalloc(f64 taps, %d x %d): %s", d->nchains, pl.pitch64, hipGetErrorString(e));
+            Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};
+            hipLaunchKernelGGL(taps_to_f64, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ta);
+            if (hipGetLastError() != hipSuccess) return set_err("taps_to_f64 failed to launch");
         }
         RingConvArgs ca{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
         hipLaunchKernelGGL(state_to_ring, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ca);   /* history the caller's buffer holds */
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { free_plan(pl); return set_err("state_to_ring failed"); }
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return set_err("state_to_ring failed");
     }
-    {
-        long long nout = 0;
-        for (int i = 0; i < d->nchains; i++) nout += chains[i].n_out;           /* check_independent (host): no IO is stored twice */
-        pl.stores_whole_window = pl.io_out_max >= pl.io_out_min && nout == (long long)pl.io_out_max - pl.io_out_min + 1;
-    }
-    pl.overlap_ok = pl.n_fir > 0 && !pl.bq.empty();
-    for (int i = 0; i < d->nchains && pl.overlap_ok; i++)
-        if (chains[i].nsec && !chains[i].fir_taps) pl.overlap_ok = false;
+    pl.stores_whole_window = stores_whole_window(t);
+    pl.overlap_ok = overlap_ok(t);
     if (pl.has_mux) {
-        pl.overlap_ok = false;                            /* (the cascades follow the mux stage on the caller's stream: no overlap mode, no ready words) */
-        /* mix groups -> mux_tile's blocks of up to 64 chains (formats 4 and 6); every other chain -> mux_plain */
-        std::vector<char> tiled(d->nchains, 0);
-        std::vector<int> tile_ids, plain, kpads;
-        std::vector<MuxTile> tiles;
-        std::vector<long long> rows;
-        long long g64_len = 0;
-        if (d->format != 2 && d->mux_ngroups > 0 && d->mux_group_start && d->mux_group_chains)
-            for (int g = 0; g < d->mux_ngroups; g++) {
-                const int b = d->mux_group_start[g], e = d->mux_group_start[g + 1];
-                if (b < 0 || e < b || e - b < AVDSP_MUX_GROUP_MIN) { free_plan(pl); return set_err("mix group %d: %d chains", g, e - b); }
-                const int c0 = d->mux_group_chains[b];
-                if (c0 < 0 || c0 >= d->nchains || mux_recs[c0].count < 1) { free_plan(pl); return set_err("mix group %d: chain %d has no list", g, c0); }
-                const int count = mux_recs[c0].count, kpad = (count + 3) & ~3;
-                for (int j = b; j < e; j++) {
-                    const int ci = d->mux_group_chains[j];
-                    /* (the kernel reads the IO numbers from the first chain's list: the host has compared the sequences) */
-                    if (ci < 0 || ci >= d->nchains || tiled[ci] || mux_recs[ci].count != count) { free_plan(pl); return set_err("mix group %d: chain %d is not one of its lists", g, ci); }
-                    tiled[ci] = 1;
-                    if ((j - b) % kMuxRows == 0) tiles.push_back(MuxTile{(int)tile_ids.size(), std::min(kMuxRows, e - j), count, kpad, mux_recs[c0].list_word, g64_len});
-                    tile_ids.push_back(ci); rows.push_back(g64_len); kpads.push_back(kpad);
-                    g64_len += kpad;
-                }
-            }
-        for (int i = 0; i < d->nchains; i++) if (!tiled[i]) plain.push_back(i);
-        pl.n_mux_plain = (int)plain.size(); pl.n_mux_tiles = (int)tiles.size(); pl.n_mux_tiled = (int)tile_ids.size();
-        if (upload_vec(&pl.d_mux_recs, mux_recs) || upload_vec(&pl.d_mux_plain, plain) || upload_vec(&pl.d_mux_tile_ids, tile_ids) ||
-            upload_vec(&pl.d_mux_tiles, tiles)) { free_plan(pl); return -1; }
-        if (hipMalloc((void **)&pl.d_mux_scratch, (size_t)kFirChunk * d->nchains * sizeof(unsigned)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(mux columns of %d chains)", d->nchains); }
-        if (pl.n_mux_tiled) {
-            long long *d_rows = nullptr; int *d_kpads = nullptr;
-            if (hipMalloc((void **)&pl.d_mux_g64, (size_t)g64_len * sizeof(double)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(f64 gains, %lld)", g64_len); }
-            if (upload_vec(&d_rows, rows) || upload_vec(&d_kpads, kpads)) { (void)hipFree(d_rows); free_plan(pl); return -1; }
+        pl.n_mux_plain = (int)M.plain.size(); pl.n_mux_tiles = (int)M.tiles.size(); pl.n_mux_tiled = (int)M.tile_ids.size();
+        if (pl.d_mux_recs.upload(t.mux_recs) || pl.d_mux_plain.upload(M.plain) || pl.d_mux_tile_ids.upload(M.tile_ids) || pl.d_mux_tiles.upload(M.tiles)) return -1;
+        if (pl.d_mux_scratch.alloc((size_t)kFirChunk * d->nchains) != hipSuccess) return set_err("hipMalloc(mux columns of %d chains)", d->nchains);
+        if (pl.n_mux_tiled) {                             /* the tiles' gains as doubles */
+            DevArr<long long> d_rows; DevArr<int> d_kpads;
+            if (pl.d_mux_g64.alloc((size_t)M.g64_len) != hipSuccess) return set_err("hipMalloc(f64 gains, %lld)", M.g64_len);
+            if (d_rows.upload(M.rows) || d_kpads.upload(M.kpads)) return -1;
             MuxGainArgs ga{prog->d_buf, pl.d_mux_recs, pl.d_mux_tile_ids, d_rows, d_kpads, pl.d_mux_g64};
             hipLaunchKernelGGL(mux_gains_to_f64, dim3(pl.n_mux_tiled), dim3(kBlock), 0, nullptr, ga);
             const bool launched = hipGetLastError() == hipSuccess;
             const bool done = hipDeviceSynchronize() == hipSuccess;
-            (void)hipFree(d_rows); (void)hipFree(d_kpads);
-            if (!launched || !done) { free_plan(pl); return set_err("mux_gains_to_f64 failed"); }
+            if (!launched || !done) return set_err("mux_gains_to_f64 failed");
         }
     }
     if (pl.overlap_ok) {                                  /* ready words, all at launch number 0 */
-        if (hipMalloc((void **)&pl.d_ready, (size_t)d->nchains * sizeof(unsigned)) != hipSuccess ||
-            hipMemset(pl.d_ready, 0, (size_t)d->nchains * sizeof(unsigned)) != hipSuccess) { free_plan(pl); return set_err("hipMalloc(ready words)"); }
+        if (pl.d_ready.alloc((size_t)d->nchains) != hipSuccess ||
+            hipMemset(pl.d_ready, 0, (size_t)d->nchains * sizeof(unsigned)) != hipSuccess) return set_err("hipMalloc(ready words)");
     }
-    prog->plans.push_back(pl);
+    prog->plans.push_back(std::move(pl));
     return (int)prog->plans.size() - 1;
 }
+
+/* kernel<FMT, ...> of a format 2 .. 6 as a function pointer */
+#define KERNEL_OF_FORMAT(fmt, kernel, ...)                                                                                                        \
+    ((fmt) == 2 ? (const void *)kernel<2, ##__VA_ARGS__> : (fmt) == 3 ? (const void *)kernel<3, ##__VA_ARGS__> : (fmt) == 4 ? (const void *)kernel<4, ##__VA_ARGS__> \
+     : (fmt) == 5 ? (const void *)kernel<5, ##__VA_ARGS__> : (const void *)kernel<6, ##__VA_ARGS__>)
 
 /* LDS budget of the generic path: frame (when small) + staged mirror, one workgroup per CU at most */
 static const int kGenericFrameLds = 4096;            /* words */
@@ -5822,7 +5474,7 @@ int avdsp_hip_prog_add_generic(avdsp_hip_prog *prog, const avdsp_generic_desc *d
         for (int i = 0; i < d->nown; i++)
             if (own[2 * i] < 0 || own[2 * i + 1] < own[2 * i] || own[2 * i + 1] > prog->total_words)
                 return set_err("generic plan: owned range %d outside the mirror", i);
-        if (upload_vec(&pl.d_own, own)) return -1;
+        if (pl.d_own.upload(own)) return -1;
         a.own = pl.d_own; a.nown = d->nown;
         for (int k = 0; k < 8; k++) a.written_io[k] = d->written_io[k];
         int nrd = 0, nwr = 0;
@@ -5838,30 +5490,17 @@ int avdsp_hip_prog_add_generic(avdsp_hip_prog *prog, const avdsp_generic_desc *d
         a.nvm = d->nvm;
         for (int k = 0; k < d->nvm; k++) a.vm_word[k] = d->vm_word[k];
         a.seq_words = std::max(d->seq_words, 256);      /* also parks the persistent frame (<= 256 slots) at start */
-        const void *fn = d->format == 2 ? (const void *)interp_wave<2> : d->format == 3 ? (const void *)interp_wave<3>
-                       : d->format == 4 ? (const void *)interp_wave<4> : d->format == 5 ? (const void *)interp_wave<5>
-                                                                                        : (const void *)interp_wave<6>;
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
-        if (e != hipSuccess) { (void)hipFree(pl.d_own); return set_err("hipFuncSetAttribute(frame-parallel LDS): %s", hipGetErrorString(e)); }
-        const void *gfn = d->format == 2 ? (const void *)interp_wave_grid<2> : d->format == 3 ? (const void *)interp_wave_grid<3>
-                        : d->format == 4 ? (const void *)interp_wave_grid<4> : d->format == 5 ? (const void *)interp_wave_grid<5>
-                                                                                          : (const void *)interp_wave_grid<6>;
-        e = hipFuncSetAttribute(gfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
-        if (e != hipSuccess) { (void)hipFree(pl.d_own); return set_err("hipFuncSetAttribute(frame-parallel LDS): %s", hipGetErrorString(e)); }
-        const void *ifn = d->format == 2 ? (const void *)interp_wave_instances<2> : d->format == 3 ? (const void *)interp_wave_instances<3>
-                        : d->format == 4 ? (const void *)interp_wave_instances<4> : d->format == 5 ? (const void *)interp_wave_instances<5>
-                                                                                          : (const void *)interp_wave_instances<6>;
-        e = hipFuncSetAttribute(ifn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
-        if (e != hipSuccess) { (void)hipFree(pl.d_own); return set_err("hipFuncSetAttribute(frame-parallel LDS): %s", hipGetErrorString(e)); }
+        const void *fns[3] = {KERNEL_OF_FORMAT(d->format, interp_wave), KERNEL_OF_FORMAT(d->format, interp_wave_grid), KERNEL_OF_FORMAT(d->format, interp_wave_instances)};
+        for (const void *fn : fns) {
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
+            if (e != hipSuccess) return set_err("hipFuncSetAttribute(frame-parallel LDS): %s", hipGetErrorString(e));
+        }
     }
     if (pl.ga_staged) {   /* per plan creation, like the FIR: nothing in the launch path may touch function attributes */
-        const void *fn = d->format == 2 ? (const void *)interp_core<2, true> : d->format == 3 ? (const void *)interp_core<3, true>
-                       : d->format == 4 ? (const void *)interp_core<4, true> : d->format == 5 ? (const void *)interp_core<5, true>
-                                                                                              : (const void *)interp_core<6, true>;
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
-        if (e != hipSuccess) { (void)hipFree(pl.d_own); return set_err("hipFuncSetAttribute(generic LDS): %s", hipGetErrorString(e)); }
+        const hipError_t e = hipFuncSetAttribute(KERNEL_OF_FORMAT(d->format, interp_core, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGenericLdsMax);
+        if (e != hipSuccess) return set_err("hipFuncSetAttribute(generic LDS): %s", hipGetErrorString(e));
     }
-    prog->plans.push_back(pl);
+    prog->plans.push_back(std::move(pl));
     return (int)prog->plans.size() - 1;
 }
 
@@ -5877,8 +5516,7 @@ int avdsp_hip_plan_add_strands(avdsp_hip_prog *prog, int plan, const avdsp_stran
     Plan &pl = prog->plans[plan];
     const int rc = plan_add_strands(prog, pl, d);
     if (rc) {
-        (void)hipFree(pl.d_sops); (void)hipFree(pl.d_sargs);
-        pl.d_sops = nullptr; pl.d_sargs = nullptr;
+        pl.d_sops.reset(); pl.d_sargs.reset();
         pl.s_loaded.clear(); pl.s_stored.clear();
         pl.s_nops = pl.s_nargs = pl.s_nstrands = pl.s_nres = 0; pl.s_usey = false;
     }
@@ -5922,7 +5560,7 @@ static int plan_add_strands(avdsp_hip_prog *prog, Plan &pl, const avdsp_strand_d
             if (!ok) return set_err("strand plan: strand %d addresses words or IOs outside the loaded buffer", r);
         }
     }
-    if (upload_vec(&pl.d_sops, ops) || upload_vec(&pl.d_sargs, args)) return -1;
+    if (pl.d_sops.upload(ops) || pl.d_sargs.upload(args)) return -1;
     {
         int nres = 0;
         for (auto &o : ops) { if (o.rcol != nres) return set_err("strand plan: resolved columns are not laid out in order"); nres += avdsp_strand_rcols(o.op, o.imm, aw); }
@@ -6158,27 +5796,18 @@ static int check_range(avdsp_hip_prog *p, int first, int n)
 
 /* The FIR delay lines live in rings on the device; the mirror's state words are brought up to date
  * before they are read back, and the rings are rebuilt after the mirror's state words were written. */
-static int rings_to_mirror(avdsp_hip_prog *p)
+static int convert_rings(avdsp_hip_prog *p, void (*kernel)(const RingConvArgs))
 {
     for (auto &pl : p->plans)
         if (pl.n_fir) {
             RingConvArgs ca{p->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
-            hipLaunchKernelGGL(ring_to_state, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ca);
+            hipLaunchKernelGGL(kernel, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ca);
             HIP_TRY(hipGetLastError());
         }
     return 0;
 }
-
-static int mirror_to_rings(avdsp_hip_prog *p)
-{
-    for (auto &pl : p->plans)
-        if (pl.n_fir) {
-            RingConvArgs ca{p->d_buf, pl.d_chains, pl.d_fir_ids, pl.n_fir, plan_ring(pl)};
-            hipLaunchKernelGGL(state_to_ring, dim3(pl.n_fir), dim3(kBlock), 0, nullptr, ca);
-            HIP_TRY(hipGetLastError());
-        }
-    return 0;
-}
+static int rings_to_mirror(avdsp_hip_prog *p) { return convert_rings(p, ring_to_state); }
+static int mirror_to_rings(avdsp_hip_prog *p) { return convert_rings(p, state_to_ring); }
 
 int avdsp_hip_prog_clear_plans(avdsp_hip_prog *p)
 {
@@ -6186,7 +5815,6 @@ int avdsp_hip_prog_clear_plans(avdsp_hip_prog *p)
     HIP_TRY(hipDeviceSynchronize());
     if (rings_to_mirror(p)) return -1;
     HIP_TRY(hipDeviceSynchronize());
-    for (auto &pl : p->plans) free_plan(pl);
     p->plans.clear();
     return 0;
 }
@@ -6299,8 +5927,8 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
             const int pitch = (pl.max_taps - 1 + nframes + 63) / 64 * 64;
             if (pitch > pl.lseq_pitch) {
                 HIP_TRY(hipDeviceSynchronize());
-                (void)hipFree(pl.d_lseq); pl.d_lseq = nullptr; pl.lseq_pitch = 0;
-                HIP_TRY(hipMalloc((void **)&pl.d_lseq, (size_t)pl.nchains * pitch * sizeof(unsigned)));
+                pl.lseq_pitch = 0;
+                HIP_TRY(pl.d_lseq.alloc((size_t)pl.nchains * pitch));
                 pl.lseq_pitch = pitch;
             }
             a.seq = pl.d_lseq; a.pitch = pl.lseq_pitch; a.hist = pl.max_taps - 1;

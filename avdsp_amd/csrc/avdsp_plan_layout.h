@@ -1,0 +1,453 @@
+/*
+ * avdsp_plan_layout.h -- the host-side tables of a chain plan, computed from an avdsp_plan_desc, and the choice of the FIR kernel
+ * of a launch.  Plain C++17: no HIP header, no HIP call, nothing of the device -- avdsp_kernels.hip includes it, and so does the
+ * stand-alone driver of tests/test_plan_layout.py, which runs every check below (they are what keeps a kernel from following a
+ * word index out of the mirror) without a GPU.
+ *
+ * avdsp_hip_prog_add_plan runs the stages in this order; each returns its tables, or an error text for set_err:
+ *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
+ *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads
+ *     check_chains     section ranges, IOs, FIR words, the IO spans, max_taps, the `fir` and `pass` lists
+ *     cascade_groups   launch groups by section count, pieces of long cascades, biquad_row's records, the merged row table
+ *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
+ */
+#ifndef AVDSP_PLAN_LAYOUT_H_
+#define AVDSP_PLAN_LAYOUT_H_
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "avdsp_hip.h"
+
+namespace avdsp_layout {
+
+constexpr int kFirChunk = 1024;      /* frames per launch: 4 MFMA tiles of 256 frames */
+constexpr int kRingAhead = 3;        /* launches of frames a FIR ring holds beside the longest history ("overlap": cascade k waits for FIR k - 3) */
+constexpr int kNG = 2;
+constexpr int kMaxGpc = 56;          /* 896 tap positions per chunk: <= 27 KB of LDS, 5 workgroups per CU, no spills */
+constexpr int kTapsLead = 64;        /* zeros in front of a chain's taps in the f64 copy */
+constexpr int kTapsTail = 384;       /* zeros behind them (the last k-steps and the operand prefetch read on) */
+/* Pieces of a long cascade: what travels between two sections is a 32-bit word -- (int)(acc >> 28), or the bits of (float)acc -- and
+ * between two PIECES the same word goes through a scratch column: kLoadRaw takes a sample word as the first section's input as it is,
+ * kStoreRaw (in the chain record's `sat`) stores the last section's result word as it is.  Device-side only; the host's descriptors
+ * never hold them (check_heads refuses the load mode). */
+constexpr int kLoadRaw = 2, kStoreRaw = 2;
+constexpr int kPieceMax = 16;        /* sections per piece: a cascade of more is cut into pieces that are each one biquad_row launch */
+constexpr int kMuxRows = 64;         /* chains per mux_tile workgroup */
+
+/* what biquad_row needs of a chain and of a section, one record per row slot / per lane of a launch group */
+struct RowRec { int cid, in_io, out_io, flags; unsigned gain_bits; int pad[3]; };      /* flags: load_mode | sat << 8 | to_ring << 9 | raw << 10 | n_out << 16; pad[0]: the row's section count
+                                                                                            (a launch with BiquadArgs::nsec 0 holds rows of several counts, four-row waves of one
+                                                                                            count each; cid -1: a row that only fills its wave) */
+struct LaneRec { int coef_word, state_word; };                                          /* -1: the lane holds no section */
+/* a column group of fir_shared: chains ids[first .. first + n) (n <= 16) of group `group` (its taps row) */
+struct SharedTile { int group, first, n, taps; };
+struct MuxRec {                      /* one per chain of a plan that holds LOAD_MUX chains */
+    int list_word, count;            /* first (IO, gain) pair in the mirror and the number of pairs; count 0: a LOAD / LOAD_GAIN chain
+                                        beside them -- its sample word of IO `list_word` is copied into its column as it is */
+    int result_word;                 /* the opcode's 8-byte result word in the mirror */
+    int col;                         /* scratch column; -1: no filter behind the head, the stage stores the chain itself */
+    int sat, n_out, out_io[AVDSP_MAX_STORES];
+};
+/* up to 64 chains of one mix group (lists of one IO sequence): four row tiles of mux_tile's workgroup */
+struct MuxTile {
+    int id0, nrec;                   /* its chains: ids[id0 .. id0 + nrec) */
+    int count, kpad;                 /* list length, and that padded to a multiple of 4 (the pitch of the gains rows) */
+    int list_word;                   /* the list that names the group's IO sequence (its first chain's) */
+    long long g64;                   /* the gains as doubles, mulop(gain): [nrec][kpad] from here, zeros behind `count` */
+};
+
+inline std::string text(const char *fmt, ...)
+{
+    char b[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(b, sizeof b, fmt, ap);
+    va_end(ap);
+    return b;
+}
+
+inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+
+/* words every index of the plan must lie inside: the mirror, or all its copies (chain instances) */
+inline long long mirror_words(const avdsp_plan_desc *d, int total_words) { return d->instances > 1 ? (long long)AVDSP_INSTANCE_STRIDE(total_words) * d->instances : total_words; }
+
+/* ---- the chains ---- */
+struct ChainTables {
+    std::vector<avdsp_chain> chains;     /* the host's records; in a plan with LOAD_MUX chains every chain reads column i of the stage's
+                                            scratch block -- a chain with a filter the word the stage has formed (kLoadRaw), a LOAD /
+                                            LOAD_GAIN chain beside them its sample word, copied there */
+    std::vector<int> coef, state;        /* per section: the word of b0 and of the six state words */
+    bool has_mux = false;
+    int mux_lo = 0x7FFFFFFF, mux_hi = 0; /* the mirror words that hold the lists */
+    std::vector<MuxRec> mux_recs;
+    std::vector<char> mux_stored;        /* chains the mux stage stores itself (no filter behind the head) */
+    int n_mux_stored = 0;
+    int io_in_min = 0x7FFFFFFF, io_in_max = -1, io_out_min = 0x7FFFFFFF, io_out_max = -1, max_taps = 0;
+    std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
+};
+
+inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
+{
+    t.chains.assign(d->chains, d->chains + d->nchains);
+    t.coef.assign(d->sec_coef_word, d->sec_coef_word + d->nsections);
+    t.state.assign(d->sec_state_word, d->sec_state_word + d->nsections);
+    t.mux_stored.assign(d->nchains, 0);
+    for (int i = 0; i < d->nsections; i++)
+        if (t.coef[i] < 0 || t.coef[i] + 5 > buf_words || t.state[i] < 0 || t.state[i] + 6 > buf_words || (t.state[i] & 1))
+            return text("section %d addresses words outside the loaded buffer", i);
+    for (int i = 0; i < d->nchains; i++) {
+        const int m = t.chains[i].load_mode;
+        if (m != AVDSP_LOAD_PLAIN && m != AVDSP_LOAD_GAIN && m != AVDSP_LOAD_MUX) return text("chain %d: load mode %d", i, m);
+        t.has_mux = t.has_mux || m == AVDSP_LOAD_MUX;
+    }
+    if (!t.has_mux) return "";
+    if (d->format == 3 || d->format == 5) return text("LOAD_MUX chains have no kernels in format %d", d->format);
+    if (d->instances > 1) return "LOAD_MUX chains have no chain instances";
+    for (int i = 0; i < d->nchains; i++) {
+        const avdsp_chain &c = t.chains[i];
+        if (c.load_mode != AVDSP_LOAD_MUX) continue;
+        if (c.mux_count < 1 || c.mux_count > 32767 || c.mux_word < 0 || (long long)c.mux_word + 2ll * c.mux_count > buf_words ||
+            c.mux_result_word < 0 || (long long)c.mux_result_word + 2 > buf_words)
+            return text("chain %d: LOAD_MUX list or result word outside the loaded buffer", i);
+        t.mux_lo = std::min(t.mux_lo, c.mux_word); t.mux_hi = std::max(t.mux_hi, c.mux_word + 2 * c.mux_count);
+    }
+    return "";
+}
+
+/* `words`: the mirror's words [mux_lo, mux_hi) */
+inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
+{
+    const int n = (int)t.chains.size();
+    t.mux_recs.resize(n);
+    for (int i = 0; i < n; i++) {
+        avdsp_chain &c = t.chains[i];
+        MuxRec r{};
+        r.sat = c.sat; r.n_out = c.n_out;
+        for (int k = 0; k < AVDSP_MAX_STORES; k++) r.out_io[k] = c.out_io[k];
+        if (c.load_mode == AVDSP_LOAD_MUX) {
+            for (int k = 0; k < c.mux_count; k++) {
+                const int io = words[(size_t)(c.mux_word - t.mux_lo) + 2 * k];
+                if (io < 0) return text("chain %d: LOAD_MUX entry %d names IO %d", i, k, io);
+                t.io_in_min = std::min(t.io_in_min, io); t.io_in_max = std::max(t.io_in_max, io);
+            }
+            r.list_word = c.mux_word; r.count = c.mux_count; r.result_word = c.mux_result_word;
+            r.col = (c.nsec || c.fir_taps) ? i : -1;
+            if (r.col < 0) { t.mux_stored[i] = 1; t.n_mux_stored++; }
+            c.load_mode = kLoadRaw;
+        } else {
+            if (c.in_io < 0) return text("chain %d: bad IO", i);
+            t.io_in_min = std::min(t.io_in_min, c.in_io); t.io_in_max = std::max(t.io_in_max, c.in_io);
+            r.list_word = c.in_io; r.count = 0; r.col = i;
+        }
+        c.in_io = i;
+        t.mux_recs[i] = r;
+    }
+    return "";
+}
+
+inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
+{
+    for (int i = 0; i < d->nchains; i++) {
+        const avdsp_chain &c = t.chains[i];
+        if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return text("chain %d: bad section range", i);
+        if (c.n_out < 1 || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return text("chain %d: bad IO", i);
+        if (!t.has_mux) { t.io_in_min = std::min(t.io_in_min, c.in_io); t.io_in_max = std::max(t.io_in_max, c.in_io); }
+        for (int k = 0; k < c.n_out; k++) {
+            if (c.out_io[k] < 0) return text("chain %d: bad IO", i);
+            t.io_out_min = std::min(t.io_out_min, c.out_io[k]); t.io_out_max = std::max(t.io_out_max, c.out_io[k]);
+        }
+        if (c.fir_taps) {
+            if (d->format == 2) return text("chain %d: FIR has no int64 definition", i);
+            if (c.fir_coef_word < 0 || c.fir_coef_word + c.fir_taps > buf_words ||
+                c.fir_state_word < 0 || c.fir_state_word + c.fir_taps > buf_words)
+                return text("chain %d: FIR addresses words outside the loaded buffer", i);
+            t.fir.push_back(i);
+            t.max_taps = std::max(t.max_taps, c.fir_taps);
+        }
+        if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) t.pass.push_back(i);
+    }
+    return "";
+}
+
+/* ---- the cascades ---- */
+/* one launch: the chains of one section count, or one piece of them */
+struct GroupLayout {
+    int P = 0, nsec = 0, n = 0;          /* lanes per chain, sections, chains */
+    bool all_fir = false;                /* every chain of the group feeds a FIR (its cascade writes the ring) */
+    bool raw_out = false;                /* a piece but the last: it stores its last section's result word as it is */
+    std::vector<int> ids;                /* the chains' records in `dev_chains` */
+    std::vector<RowRec> rows; std::vector<LaneRec> lanes;      /* biquad_row's records (P == 16), sections right-aligned in the row */
+    std::vector<GroupLayout> pieces;     /* a cascade of more than kPieceMax sections: launched one after the other; piece k hands the
+                                            word between its last section and piece k + 1's first through column j (the chain's place
+                                            in the group) of a scratch block */
+};
+struct CascadeLayout {
+    std::vector<avdsp_chain> dev_chains; /* what the kernels see: the host's records + the pieces of long cascades behind them */
+    std::vector<GroupLayout> groups;     /* by section count, in first-seen order */
+    /* the rows of ALL the 16-lane groups in one table -- runs of one section count, each filled up to whole waves (four rows) with
+     * empty rows, the table to whole workgroups (16) -- for ONE biquad_row launch instead of one per section count.  Only made when
+     * there are two such groups or more. */
+    std::vector<RowRec> all_rows; std::vector<LaneRec> all_lanes;
+    bool rows_all_fir = true; int n_row_groups = 0;
+};
+
+/* biquad_row's records of the chains `ids` (records of `chains`), all of one section count */
+inline void row_records(int format, const std::vector<avdsp_chain> &chains, const ChainTables &t, GroupLayout &g)
+{
+    g.rows.resize(g.ids.size());
+    g.lanes.assign(g.ids.size() * 16, LaneRec{-1, -1});
+    for (size_t j = 0; j < g.ids.size(); j++) {
+        const avdsp_chain &c = chains[g.ids[j]];
+        /* bit 8: SAT0DB in front of the store -- in the int64 kernel "the stored word is acc >> 28", which is also what a piece
+         * hands on (bit 10 then takes the dither mask off); in the double kernels a piece's word is the float as it is: no bit 8 */
+        const bool raw = c.sat == kStoreRaw;
+        const bool sat = raw ? format == 2 : c.sat != 0;
+        g.rows[j] = RowRec{g.ids[j], c.in_io, c.out_io[0], (c.load_mode & 0xFF) | (sat ? 1 << 8 : 0) | (c.fir_taps ? 1 << 9 : 0) | (raw ? 1 << 10 : 0) | (c.n_out << 16),
+                           c.gain_bits, {c.nsec, 0, 0}};
+        for (int q = 0; q < c.nsec; q++) g.lanes[j * 16 + (16 - c.nsec) + q] = LaneRec{t.coef[c.sec_base + q], t.state[c.sec_base + q]};
+    }
+}
+
+inline CascadeLayout cascade_groups(int format, const ChainTables &t)
+{
+    CascadeLayout L;
+    L.dev_chains = t.chains;
+    for (int i = 0; i < (int)t.chains.size(); i++) {
+        const int nsec = t.chains[i].nsec;
+        if (!nsec) continue;
+        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec; });
+        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; }
+        it->ids.push_back(i);
+    }
+    for (GroupLayout &g : L.groups) {
+        g.n = (int)g.ids.size();
+        /* lanes per chain: the next power of two -- but a 16-lane row per chain while the chip has SIMDs to spare (<= 1024 waves): its
+         * step is shorter (one input batch per 16 steps, no mid-row section-0 lanes) and idle lanes cost nothing there */
+        g.P = g.nsec > 64 ? 128 : pow2ceil(g.nsec);
+        if (g.P < 16 && (long long)g.n * 16 <= 65536) g.P = 16;
+        g.all_fir = true;
+        for (int id : g.ids) g.all_fir = g.all_fir && t.chains[id].fir_taps != 0;
+        if (g.nsec > kPieceMax) {
+            /* A cascade of more than 16 sections runs as pieces of equal length (+- 1), each a biquad_row launch, one after the other:
+             * a 16-lane row per chain wastes no lanes on lengths like 17 or 33, and a cascade of more than 64 sections fits no wave at
+             * all.  The pieces but the last are chain records of their own behind the host's (no FIR, no SAT0DB, one raw
+             * store into the scratch column); the last piece is the chain's own record with its input moved to the scratch column (its
+             * ring, stores and ready word are the chain's). */
+            const int np = (g.nsec + kPieceMax - 1) / kPieceMax, base = g.nsec / np, extra = g.nsec % np;
+            int at = 0;
+            for (int k = 0; k < np; k++) {
+                GroupLayout pg;
+                pg.nsec = base + (k < extra ? 1 : 0); pg.P = 16; pg.n = g.n;
+                pg.all_fir = k + 1 == np && g.all_fir; pg.raw_out = k + 1 < np;
+                pg.ids.resize(g.n);
+                for (int j = 0; j < g.n; j++) {
+                    const avdsp_chain &c = t.chains[g.ids[j]];
+                    avdsp_chain pc = c;
+                    pc.sec_base = c.sec_base + at; pc.nsec = pg.nsec;
+                    if (k > 0) { pc.in_io = j; pc.load_mode = kLoadRaw; }
+                    if (k + 1 < np) {
+                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j;
+                        pg.ids[j] = (int)L.dev_chains.size(); L.dev_chains.push_back(pc);
+                    } else { pg.ids[j] = g.ids[j]; L.dev_chains[g.ids[j]] = pc; }
+                }
+                row_records(format, L.dev_chains, t, pg);
+                g.pieces.push_back(std::move(pg));
+                at += base + (k < extra ? 1 : 0);
+            }
+        } else if (g.P == 16) {
+            row_records(format, t.chains, t, g);
+            /* ... and the same rows in the table of all lengths: this run, filled up to whole waves.  (An empty row is a copy of a real
+             * one with no chain behind it: every lane of a wave FETCHES, section or not -- its input column must be one the block has;
+             * nothing of it is stored) */
+            L.all_rows.insert(L.all_rows.end(), g.rows.begin(), g.rows.end());
+            L.all_lanes.insert(L.all_lanes.end(), g.lanes.begin(), g.lanes.end());
+            RowRec empty = g.rows[0]; empty.cid = -1;
+            while (L.all_rows.size() % 4) { L.all_rows.push_back(empty); L.all_lanes.insert(L.all_lanes.end(), 16, LaneRec{-1, -1}); }
+            L.n_row_groups++;
+            L.rows_all_fir = L.rows_all_fir && g.all_fir;
+        }
+    }
+    if (L.n_row_groups >= 2) {
+        RowRec empty = L.all_rows.back(); empty.cid = -1;
+        while (L.all_rows.size() % 16) { L.all_rows.push_back(empty); L.all_lanes.insert(L.all_lanes.end(), 16, LaneRec{-1, -1}); }
+    } else { L.all_rows.clear(); L.all_lanes.clear(); }
+    return L;
+}
+
+/* ---- fir_shared: the host's groups of chains on one impulse bank -- a taps row per group, column groups of <= 16 chains ---- */
+struct SharedLayout {
+    std::string err;
+    std::vector<int> ids;                /* the grouped chains, group by group */
+    std::vector<int> feed;               /* ... those without a cascade in front (fir_feed appends their input) */
+    std::vector<int> rest;               /* the FIR chains in no group: fir_tile beside fir_shared */
+    std::vector<int> reps;               /* per group: the chain whose taps are the group's */
+    std::vector<SharedTile> tiles;
+};
+inline SharedLayout shared_fir_layout(const avdsp_plan_desc *d, const ChainTables &t)
+{
+    SharedLayout S;
+    if (t.fir.empty() || !(d->fir_ngroups > 0 && d->fir_group_start && d->fir_group_chains && d->instances <= 1 && (d->format == 4 || d->format == 6))) return S;
+    std::vector<char> in_group(d->nchains, 0);
+    for (int g = 0; g < d->fir_ngroups; g++) {
+        const int b = d->fir_group_start[g], e = d->fir_group_start[g + 1];
+        if (b < 0 || e < b || e - b < AVDSP_FIR_GROUP_MIN) { S.err = text("FIR group %d: %d chains", g, e - b); return S; }
+        const int c0 = d->fir_group_chains[b];
+        for (int j = b; j < e; j++) {
+            const int ci = d->fir_group_chains[j];
+            if (ci < 0 || ci >= d->nchains || in_group[ci] || !t.chains[ci].fir_taps || t.chains[ci].fir_taps != t.chains[c0].fir_taps ||
+                t.chains[ci].fir_coef_word != t.chains[c0].fir_coef_word) { S.err = text("FIR group %d: chain %d is not one of its bank", g, ci); return S; }
+            in_group[ci] = 1;
+            if (!t.chains[ci].nsec) S.feed.push_back(ci);
+        }
+        const int gi = (int)S.reps.size();
+        S.reps.push_back(c0);
+        for (int j = b; j < e; j += 16)
+            S.tiles.push_back(SharedTile{gi, (int)S.ids.size() + (j - b), std::min(16, e - j), t.chains[c0].fir_taps});
+        S.ids.insert(S.ids.end(), d->fir_group_chains + b, d->fir_group_chains + e);
+    }
+    for (int ci : t.fir) if (!in_group[ci]) S.rest.push_back(ci);
+    return S;
+}
+
+/* ---- mix groups -> mux_tile's blocks of up to kMuxRows chains (formats 4 and 6); every other chain -> mux_plain ---- */
+struct MuxLayout {
+    std::string err;
+    std::vector<int> tile_ids, plain, kpads;     /* the tiles' chains (kpads: each one's padded list length); the chains mux_plain takes */
+    std::vector<MuxTile> tiles;
+    std::vector<long long> rows;                 /* per tiled chain: where its gains row starts */
+    long long g64_len = 0;                       /* doubles of all gains rows */
+};
+inline MuxLayout mux_tiles(const avdsp_plan_desc *d, const ChainTables &t)
+{
+    MuxLayout M;
+    std::vector<char> tiled(d->nchains, 0);
+    if (d->format != 2 && d->mux_ngroups > 0 && d->mux_group_start && d->mux_group_chains)
+        for (int g = 0; g < d->mux_ngroups; g++) {
+            const int b = d->mux_group_start[g], e = d->mux_group_start[g + 1];
+            if (b < 0 || e < b || e - b < AVDSP_MUX_GROUP_MIN) { M.err = text("mix group %d: %d chains", g, e - b); return M; }
+            const int c0 = d->mux_group_chains[b];
+            if (c0 < 0 || c0 >= d->nchains || t.mux_recs[c0].count < 1) { M.err = text("mix group %d: chain %d has no list", g, c0); return M; }
+            const int count = t.mux_recs[c0].count, kpad = (count + 3) & ~3;
+            for (int j = b; j < e; j++) {
+                const int ci = d->mux_group_chains[j];
+                /* (the kernel reads the IO numbers from the first chain's list: the host has compared the sequences) */
+                if (ci < 0 || ci >= d->nchains || tiled[ci] || t.mux_recs[ci].count != count) { M.err = text("mix group %d: chain %d is not one of its lists", g, ci); return M; }
+                tiled[ci] = 1;
+                if ((j - b) % kMuxRows == 0) M.tiles.push_back(MuxTile{(int)M.tile_ids.size(), std::min(kMuxRows, e - j), count, kpad, t.mux_recs[c0].list_word, M.g64_len});
+                M.tile_ids.push_back(ci); M.rows.push_back(M.g64_len); M.kpads.push_back(kpad);
+                M.g64_len += kpad;
+            }
+        }
+    for (int i = 0; i < d->nchains; i++) if (!tiled[i]) M.plain.push_back(i);
+    return M;
+}
+
+/* ---- scalars ---- */
+/* fir_mfma: groups of 16 tap positions per LDS chunk */
+inline int fir_groups_per_chunk(int max_taps)
+{
+    const int G = (max_taps + 15 + 15) >> 4;
+    const int nc = (G + kMaxGpc - 1) / kMaxGpc;
+    const int gpc = (G + nc - 1) / nc;
+    return std::min((gpc + kNG - 1) / kNG * kNG, kMaxGpc);
+}
+/* floats of a chain's FIR history ring: the longest history, kRingAhead launches of frames (under "overlap" the cascade appends block
+ * k + 1 while the FIR still reads block k's window) and a chunk */
+inline int ring_length(int max_taps) { return pow2ceil(max_taps + kRingAhead * kFirChunk + 16 * fir_groups_per_chunk(max_taps) + 16 * (kNG + 4) + 64); }
+/* doubles of a chain's row in the f64 copy of the taps */
+constexpr int taps64_pitch(int max_taps) { return (kTapsLead + max_taps + kTapsTail + 1) & ~1; }
+/* every IO of [io_out_min, io_out_max] is stored by some chain (check_independent, host: no IO is stored twice) */
+inline bool stores_whole_window(const ChainTables &t)
+{
+    long long nout = 0;
+    for (const avdsp_chain &c : t.chains) nout += c.n_out;
+    return t.io_out_max >= t.io_out_min && nout == (long long)t.io_out_max - t.io_out_min + 1;
+}
+/* every cascade of the plan feeds a FIR: its launches may run under the previous block's FIR.  (Not behind a mux stage: the cascades
+ * follow it on the caller's stream.) */
+inline bool overlap_ok(const ChainTables &t)
+{
+    bool any = false;
+    for (const avdsp_chain &c : t.chains) { if (c.nsec && !c.fir_taps) return false; any = any || c.nsec; }
+    return any && !t.fir.empty() && !t.has_mux;
+}
+
+/* ---- which FIR kernel a launch takes ---- */
+/* fir_impl's values, and fir_shared, which launch_all takes for the grouped chains of a plan (shared_path) */
+enum FirFamily { kFirPlain = 0, kFirTile = 1, kFirMfma = 2, kFirStream = 3, kFirFlow = 4, kFirShared = 5 };
+struct FirChoice { int family, R; bool BIG, SPLIT, LEAN; };       /* R: row tiles per wave (fir_mfma: its NG); the flags are fir_tile's / fir_flow's, else false */
+inline bool operator==(const FirChoice &a, const FirChoice &b) { return a.family == b.family && a.R == b.R && a.BIG == b.BIG && a.SPLIT == b.SPLIT && a.LEAN == b.LEAN; }
+struct FirOptions { int fir_rows, fir_split, fir_lean; };         /* the options of those names: 0 = by the rules below, 0 = off, -1 = by the plan */
+
+/* Row tiles per wave by cost.  The chip holds 2048 of these waves at a time, a wave of R row tiles lasts R units, and a launch is over
+ * when its LAST round of waves is -- 3000 chains at four row tiles were 1.46 rounds, i.e. two: 480 us, as long as 4096 chains.  So: the R
+ * with the fewest units, rounds(R) x R / efficiency(R) (0.90 / 0.84 / 0.79 of the matrix pipe at 4 / 2 / 1 row tiles).
+ * `tile_frames`: the frames one row tile covers per wave (fir_tile 256; fir_shared 64, `waves_per_unit` 4 waves per column group).
+ * A tile of twice the block would multiply zeros: such an R is out, whoever chose it. */
+inline int fir_rows_for(int fir_rows, long long units, int waves_per_unit, int frames, int tile_frames)
+{
+    int rows = fir_rows;
+    if (rows != 1 && rows != 2 && rows != 4) {
+        double best = 1e30;
+        rows = 1;
+        for (int r : {4, 2, 1}) {
+            if (r > 1 && tile_frames / 2 * r >= frames) continue;
+            const long long waves = units * waves_per_unit * ((frames + tile_frames * r - 1) / (tile_frames * r));
+            const double cost = (double)((waves + 2047) / 2048) * r / (r == 4 ? 0.90 : r == 2 ? 0.84 : 0.79);
+            if (cost < best - 1e-9) { best = cost; rows = r; }
+        }
+    }
+    while (rows > 1 && tile_frames / 2 * rows >= frames) rows >>= 1;
+    return rows;
+}
+
+/* fir_shared over a plan's `ntiles` column groups.  Format 4 stops at two row tiles: with four, store_word_f4's epilogue takes the
+ * kernel to 256 VGPRs and spills -- that variant does not exist. */
+inline FirChoice fir_shared_choice(int format, int ntiles, int frames, int fir_rows)
+{
+    const int rows = fir_rows_for(fir_rows, ntiles, 4, frames, 64);
+    return FirChoice{kFirShared, format == 4 ? std::min(rows, 2) : rows, false, false, false};
+}
+
+/* a launch of `n` chains over `frames` frames with fir_impl `impl`; `cascades`: the plan has cascades in front of its FIRs;
+ * `plan_taps`: the plan's FIR chains x its longest FIR */
+inline FirChoice fir_choice(int impl, long long n, int frames, const FirOptions &o, bool cascades, long long plan_taps)
+{
+    const bool rows_set = o.fir_rows == 1 || o.fir_rows == 2 || o.fir_rows == 4;
+    const long long waves1 = n * ((frames + 255) / 256);         /* waves of one row tile */
+    auto halved = [&](int rows) { while (rows > 1 && 128 * rows >= frames) rows >>= 1; return rows; };
+    switch (impl) {
+    case kFirFlow: {
+        const int rows = halved(rows_set ? o.fir_rows : n >= 2048 ? 4 : n >= 1024 ? 2 : 1);
+        /* at most a wave per SIMD: long chunks, two window images */
+        return FirChoice{kFirFlow, rows, rows == 1 && waves1 <= 1024 && o.fir_rows != 1, false, false};
+    }
+    case kFirStream:      /* row tiles per wave: as many as leave every SIMD a wave (1024) */
+        return FirChoice{kFirStream, halved(rows_set ? o.fir_rows : waves1 >= 4 * 1024 ? 4 : waves1 >= 2 * 1024 ? 2 : 1), false, false, false};
+    case kFirTile: {
+        const int rows = fir_rows_for(o.fir_rows, n, 1, frames, 256);
+        /* the lean chunk boundary (fir_tile, LEAN) where it was measured to win (tools/fir_boundary_lab.sh, one box, long / lean):
+         * plans without cascades in front (256 chains x 4096 taps: 40.9 -> 39.4 us per step) and launches of more than one round of
+         * waves (4096 chains: 0.511 -> 0.506 ms).  In between, the next blocks' cascades run beside the FIR and live on the long
+         * boundary's bubbles: 2048 chains 0.259 -> 0.269 ms, 1024 chains 0.147 -> 0.154, 512 chains 0.0876 -> 0.0966. */
+        const bool lean = o.fir_lean >= 0 ? o.fir_lean != 0 : (!cascades || plan_taps >= 12000000ll);
+        /* one row tile and at most a wave per SIMD (1024): chunks twice as long (BIG) -- nothing hides a boundary there -- or, with
+         * "fir_split" (opt-in, not the reference's summation order), two waves per tile instead */
+        const bool few = rows == 1 && waves1 <= 1024;
+        const bool split = few && o.fir_split;
+        return FirChoice{kFirTile, rows, few && !split && o.fir_rows != 1, split, lean};
+    }
+    case kFirPlain: return FirChoice{kFirPlain, 1, false, false, false};
+    default:              /* fir_mfma.  Few workgroups per CU: the deeper operand sets */
+        return FirChoice{kFirMfma, n <= 2 * 256 ? 2 : 1, false, false, false};
+    }
+}
+
+}  // namespace avdsp_layout
+
+#endif

@@ -224,7 +224,7 @@ def test_chain_instances_under_the_overlap_mode():
 
 @pytest.mark.parametrize("ready_words", [-1, 0, 1, 2])
 def test_long_cascades_in_pieces_under_the_overlap_mode(ready_words):
-    """70 sections in front of a 300-tap FIR: the cascade runs as two pieces (more than 64 sections do not fit a wave), on the cascades'
+    """70 sections in front of a 300-tap FIR: the cascade runs as five pieces of 14 sections (more than 16: cascade_groups), on the cascades'
     stream, under the previous block's FIR; only the LAST piece's launch appends to the rings and publishes the chains' ready words"""
     prog = pb.synth_program(6, 3, 70, 300)
     r = _chain_instances_vs_oracle(6, prog, 3, 1, [1024, 1024, 1024, 333, 1024], options={"overlap": 1, "ready_words": ready_words})

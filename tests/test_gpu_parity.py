@@ -654,7 +654,8 @@ def test_cascades_of_many_lengths_in_one_launch(fmt, fanout):
 @pytest.mark.parametrize("biquad_impl", [1, 0])
 def test_cascades_longer_than_a_wave_run_as_pieces(fmt, biquad_impl):
     """More than 64 sections in one chain do not fit a wave's lanes: until round 5 such a chain fell to biquad_simple (a lane per chain,
-    state in memory -- 4096 chains x 65 sections 81 ms against 136 us for 64).  Now add_plan cuts it into pieces of up to 64 sections that
+    state in memory -- 4096 chains x 65 sections 81 ms against 136 us for 64).  Now every cascade of more than 16 sections is cut into
+    pieces of up to 16 (equal lengths +- 1: 65 -> 5 x 13, 200 -> 5 x 16 + 8 x 15; avdsp_plan_layout.h, cascade_groups) that
     run as launches one after the other, the 32-bit word between two sections going through a scratch column.  Chains of 65, 100, 128, 129
     and 200 sections beside short ones, plain and gain loads, with and without SAT0DB, two of them in front of a FIR, ragged blocks (one
     of more than 1024 frames) against the oracle, outputs and state; in format 6 then an Inf and a NaN sample (the pieces' replay in the
