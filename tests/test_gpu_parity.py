@@ -201,6 +201,11 @@ def test_checkpoint_restore(fmt):
     rest2 = r2.run_block(x[150:], 5, 5)
     assert (rest.view(np.uint32) == rest2.view(np.uint32)).all()
     assert first.shape == (150, 5)
+    o = po.OracleProgram(fmt, prog)
+    assert (o.run_block(x[:150], 5, 5).view(np.uint32) == first.view(np.uint32)).all()
+    assert (saved == o.state).all(), "the checkpoint is the reference's state"
+    assert (o.run_block(x[150:], 5, 5).view(np.uint32) == rest.view(np.uint32)).all()
+    assert (r2.sync_state() == o.state).all()
 
 
 def test_bypass_and_multi_bank_and_plain_load():

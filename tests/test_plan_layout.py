@@ -215,6 +215,8 @@ def test_ring_length(driver):
     assert run(driver, "ring", 4096).split() == ["8192", "52", "4544"]         # ring floats, fir_gpc, pitch64 (see the module's docstring)
     assert run(driver, "ring", 8192).split()[0] == "16384"
     assert run(driver, "ring", 300).split() == ["4096", "20", "748"]
+    assert run(driver, "ring", 416).split()[:2] == ["4096", "28"]              # 416 + 3072 + 16 * 28 + 96 + 64 = 4096: the fullest ring of 4096
+    assert run(driver, "ring", 417).split()[:2] == ["8192", "28"]
 
 
 # ---------------------------------------------------------------- refusals
