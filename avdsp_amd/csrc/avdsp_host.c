@@ -114,6 +114,7 @@ typedef struct avdsp_ctx {
     int             chain_inst_win[5];                     /* the windows the cores' IOs were last checked against (format, in base, in stride, out base, out stride); [0] = 0: none */
     int             opt_frame_server, opt_frame_server_idle_us;      /* "frame_server" (AVDSP_OPT_FRAME_SERVER), "frame_server_idle_us" */
     int             opt_fir_shared;                        /* "fir_shared" (AVDSP_OPT_FIR_SHARED), default 1 */
+    int             opt_chain_finish;                      /* "chain_finish": dressed SAT0DB finishes and a head TPDF_CALC lowered to the chain kernels (default 0) */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
@@ -303,6 +304,11 @@ static int set_option_here(const char *key, int value)
         return 0;
     }
     if (!strcmp(key, "fir_shared_chains") || !strcmp(key, "fir_shared_groups") || !strcmp(key, "fir_shared_rows")) return fail(-1, "%s is read-only", key);
+    if (!strcmp(key, "chain_finish")) {                  /* SAT0DB_TPDF / _GAIN / _TPDF_GAIN and a head TPDF_CALC on the chain kernels; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "chain_finish: 0 or 1");
+        G.opt_chain_finish = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -394,6 +400,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_lean"))    return G.opt_fir_lean_set ? G.opt_fir_lean : -1;
     if (!strcmp(key, "ring_wait"))   return G.opt_ring_wait;
     if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
+    if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -533,7 +540,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -680,6 +687,8 @@ static int ensure_encoding(int format)
 typedef struct {
     avdsp_chain *chains; int nchains, cap_chains;
     int32_t *coef_word, *state_word; int nsec, cap_sec;
+    int tpdf_calc, tpdf_calc_arg, tpdf_calc_word;         /* "chain_finish": the core begins with a DSP_TPDF_CALC; its width word and result word */
+    int ndressed;                                         /* ... chains with a dressed finish */
 } lowered;
 
 static void lowered_free(lowered *L) { free(L->chains); free(L->coef_word); free(L->state_word); memset(L, 0, sizeof *L); }
@@ -744,7 +753,23 @@ static int check_independent(const lowered *L)
 
 #define GENERIC_IO_LIMIT 65536            /* IO numbers a program may use (the reference's hosts use well under 100) */
 
+/* "chain_finish": the dither width of the program's globals is one constant -- every DSP_TPDF_CALC of every core asks for the default
+ * (0, or its value).  Else a core elsewhere changes the store mask and the addend's scale between two blocks of a dressed core. */
+static int dither_width_constant(void)
+{
+    const int prog_words = dspHeaderPtr->totalLength;
+    for (int at = 0; at < prog_words; ) {
+        const opcode_t *p = G.code + at;
+        const unsigned skip = p->op.skip;
+        if (skip == 0 || (long long)at + skip > prog_words) break;
+        if (p->op.opcode == DSP_TPDF_CALC && (skip < 3 || (p[1].i32 != 0 && p[1].i32 != G.dither))) return 0;
+        at += (int)skip;
+    }
+    return 1;
+}
+
 /* mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used (dspRuntimeMuxInfo tells it from the others) */
+static int lowered_has_mux(const lowered *L);
 static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damaged)
 {
     int damaged_ = 0;
@@ -754,9 +779,12 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
     const int prog_words = dspHeaderPtr->totalLength;
     opcode_t *p = dspFindCoreBegin(core);
     avdsp_chain cur;
-    int open = 0;
+    int open = 0, fir_op = 0;                                /* fir_op: the open chain holds a DSP_FIR opcode (with taps or bypassed) */
     memset(&cur, 0, sizeof cur);
     memset(L, 0, sizeof *L);
+    /* dressed finishes and the head TPDF_CALC: opt-in, formats 2, 4 and 6, not while the program has instances (each has a generator
+     * of its own on the interpreter) */
+    const int finish_on = G.opt_chain_finish && G.ninst <= 1 && (format == 2 || format == 4 || format == 6);
 
     if (ensure_encoding(format)) return g_err_code;
 
@@ -787,7 +815,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                 if (push_chain(L, &cur)) return fail(-9, "out of memory");
             }
             memset(&cur, 0, sizeof cur);
-            open = 1;
+            open = 1; fir_op = 0;
             cur.in_io = a[0];
             cur.sec_base = L->nsec;
             if (op == DSP_LOAD_GAIN) {
@@ -817,7 +845,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                 if (push_chain(L, &cur)) return fail(-9, "out of memory");
             }
             memset(&cur, 0, sizeof cur);
-            open = 1;
+            open = 1; fir_op = 0;
             cur.in_io = t[1].i32;
             cur.sec_base = L->nsec;
             cur.load_mode = AVDSP_LOAD_MUX;
@@ -850,6 +878,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                 return fail(-8, "word %d: DSP_FIR in int64 mode is undefined behaviour in the reference "
                                 "(dsp_firSTD.h:8-35) and is not provided", at);
             LC_NEED(G.num_freq + 1);
+            fir_op = 1;
             int off = a[G.freq_index];
             if (off) {
                 LC_PROG(off, 1);
@@ -872,6 +901,31 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (!open || cur.n_out) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
             cur.sat = 1;
             break;
+        case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:      /* :478-534, "chain_finish" */
+            if (!finish_on) goto not_lowered;
+            if (!open || cur.n_out || cur.sat) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
+            if (fir_op || cur.load_mode == AVDSP_LOAD_MUX)
+                return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
+            if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
+            cur.finish = op == DSP_SAT0DB_TPDF ? AVDSP_FINISH_TPDF : op == DSP_SAT0DB_GAIN ? AVDSP_FINISH_GAIN : AVDSP_FINISH_TPDF_GAIN;
+            if (op != DSP_SAT0DB_TPDF) {
+                LC_NEED(1);
+                LC_PROG(a[0], 1);
+                cur.finish_gain_bits = p[a[0]].u32;
+            }
+            cur.sat = 1;
+            L->ndressed++;
+            break;
+        case DSP_TPDF_CALC:                                   /* :537-545, "chain_finish": once, in front of the first chain */
+            if (!finish_on) goto not_lowered;
+            if (open || L->nchains || L->tpdf_calc) return fail(-8, "word %d: TPDF_CALC behind the head of the core is not lowered to the HIP path", at);
+            LC_NEED(2);
+            if (a[0] != 0 && a[0] != G.dither) return fail(-8, "word %d: TPDF_CALC of width %d under the default %d is not lowered to the HIP path", at, a[0], G.dither);
+            if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
+            if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
+                return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
+            L->tpdf_calc = 1; L->tpdf_calc_arg = a[0]; L->tpdf_calc_word = prog_words + a[1];
+            break;
         case DSP_STORE:                                       /* :610-633 */
             LC_NEED(1);
             if (a[0] < 0 || a[0] >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", at, a[0], GENERIC_IO_LIMIT);
@@ -879,7 +933,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (cur.n_out == AVDSP_MAX_STORES) return fail(-8, "word %d: more than %d STOREs in a chain", at, AVDSP_MAX_STORES);
             cur.out_io[cur.n_out++] = a[0];
             break;
-        default:
+        default: not_lowered:
             return fail(-8, "word %d: opcode %d (%s) is not lowered to the HIP path", at, op,
                         (op >= 0 && op < DSP_MAX_OPCODE) ? dspOpcodeText[op] + (dspOpcodeText[op][0] == '\n') : "?");
         }
@@ -892,6 +946,8 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
 #undef LC_NEED
 #undef LC_PROG
     if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
+    if ((L->ndressed || L->tpdf_calc) && lowered_has_mux(L))
+        return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
     return check_independent(L);
 }
 
@@ -1549,6 +1605,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.nchains = hi - lo; d.chains = L.chains + lo;
         d.nsections = sec1 - sec0; d.sec_coef_word = L.coef_word + sec0; d.sec_state_word = L.state_word + sec0;
         d.store_mask = G.store_mask;
+        d.tpdf_calc = L.tpdf_calc; d.tpdf_calc_arg = L.tpdf_calc_arg; d.tpdf_calc_result_word = L.tpdf_calc_word;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -1728,6 +1785,34 @@ int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, 
     if (groups) *groups = ng;
     if (grouped_chains) *grouped_chains = nc;
     if (longest_list) *longest_list = big;
+    return 0;
+}
+
+/* Host-only: what "chain_finish" makes of the core -- the chains with a dressed finish (SAT0DB_TPDF / _GAIN / _TPDF_GAIN) among the
+ * chains this process runs (dspRuntimeSetShard) and whether the core begins with a DSP_TPDF_CALC that dither_block runs (DESIGN.md
+ * 4.2f).  No device is touched.  A core that is not a set of chains has neither. */
+int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *tpdf_calc)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nd = 0, calc = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0) {
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            for (int i = lo; i < hi; i++) nd += L.chains[i].finish != 0;
+            calc = L.tpdf_calc;
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (dressed_chains) *dressed_chains = nd;
+    if (tpdf_calc) *tpdf_calc = calc;
     return 0;
 }
 
@@ -2549,6 +2634,8 @@ int dspRuntimeSetInstances(int n)
     }
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
+    /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
+    if (G.opt_chain_finish && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

@@ -53,6 +53,27 @@ namespace {
 
 using namespace avdsp_layout;      /* the plan's host-side tables, their records and constants (kFirChunk, kLoadRaw, ...) */
 
+/* The chain record as the kernels read it: avdsp_chain (include/avdsp_hip.h) without its dressed finish, which only the kernels of
+ * dressed chains look at -- in a table of its own (FinishRec, indexed like the records).  The record every other kernel copies into
+ * its registers, and into the stack frame of its replay, stays the 17 words it was. */
+struct DevChain {
+    int32_t  in_io, load_mode; uint32_t gain_bits; int32_t nsec, sec_base, fir_taps, fir_coef_word, fir_state_word, sat, n_out;
+    int32_t  out_io[AVDSP_MAX_STORES];
+    int32_t  mux_word, mux_count, mux_result_word;
+};
+struct FinishRec { int finish; unsigned gain_bits; };      /* avdsp_chain::finish, ::finish_gain_bits */
+inline std::vector<DevChain> dev_records(const std::vector<avdsp_chain> &v)
+{
+    std::vector<DevChain> o(v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+        const avdsp_chain &c = v[i];
+        o[i] = DevChain{c.in_io, c.load_mode, c.gain_bits, c.nsec, c.sec_base, c.fir_taps, c.fir_coef_word, c.fir_state_word, c.sat, c.n_out,
+                        {c.out_io[0], c.out_io[1], c.out_io[2], c.out_io[3]}, c.mux_word, c.mux_count, c.mux_result_word};
+    }
+    return o;
+}
+static_assert(AVDSP_MAX_STORES == 4 && sizeof(DevChain) == 17 * 4, "DevChain is avdsp_chain's first 17 words");
+
 thread_local char g_err[512];
 thread_local bool g_err_ready = false;   /* the latest set_err() was ready_check()'s (avdsp_hip_last_error_is_ready_timeout) */
 
@@ -245,6 +266,13 @@ __device__ __forceinline__ unsigned store_stage(typename Alu<FMT>::type X, int s
     }
 }
 
+/* Dressed finishes ("chain_finish"): what stands in a chain's SAT0DB slot when it is DSP_SAT0DB_TPDF, _GAIN or
+ * _TPDF_GAIN (dsp_runtime.c:478-534) and the STORE behind it (:610-633), from the last section's whole accumulator: [gain], [+ the
+ * frame's dither addend, as dither_block left it], SAT0DB, the format's store word.  Defined behind the interpreter's device
+ * functions (avdsp_interp.inc), whose restatements of the reference's arithmetic it shares. */
+template <int FMT>
+__device__ __forceinline__ unsigned finish_stage(typename Alu<FMT>::type X, int finish, unsigned gain_bits, unsigned long long addend, int mask);
+
 /* XCD-aware block index: hardware deals consecutive workgroups round-robin over the 8 XCDs, so
  * giving XCD x the x-th contiguous eighth of the work keeps neighbouring channels (which share
  * 128-byte lines of the interleaved sample block) in the same L2.  Speed only, never correctness. */
@@ -342,7 +370,7 @@ struct BlockIO {
 };
 
 /* final stores of one chain for frame n */
-__device__ __forceinline__ void emit_out(const BlockIO &io, const avdsp_chain &c, int n, unsigned word)
+__device__ __forceinline__ void emit_out(const BlockIO &io, const DevChain &c, int n, unsigned word)
 {
 #pragma unroll
     for (int k = 0; k < AVDSP_MAX_STORES; k++)          /* static indices keep the chain record in registers */
@@ -371,7 +399,7 @@ struct BiquadArgs {
     int            *buf;            /* device mirror of the caller's buffer */
     const RowRec   *rows;           /* biquad_row: [ngroup] */
     const LaneRec  *lanes;          /* biquad_row: [ngroup][16], sections right-aligned in the row */
-    const avdsp_chain *chains;
+    const DevChain *chains;
     const int      *sec_coef, *sec_state;
     const int      *group;          /* chain ids handled by this launch (all with `nsec` sections) */
     int             ngroup;
@@ -385,6 +413,12 @@ struct BiquadArgs {
     unsigned long long *stamps;     /* diagnostic build (tools/cascade_timeline.py): 32 s_memtime stamps per wave */
 #endif
 };
+/* launches of dressed chains (the WIDE forms below) */
+struct BiquadArgsWide : BiquadArgs {
+    const unsigned long long *addend;      /* the dither addend of every frame of this launch (dither_block) */
+    const FinishRec *finish;               /* [chain record] */
+};
+template <bool WIDE> using BqArgs = std::conditional_t<WIDE, BiquadArgsWide, BiquadArgs>;
 #ifdef AVDSP_BQ_STAMPS
 #define BQ_STAMP(i) do { if ((threadIdx.x & 63) == 0 && (i) < 32) a.stamps[(size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -438,8 +472,9 @@ __device__ __forceinline__ Hand<FMT> hand_rotate(Hand<FMT> h)
  * (dsp_biquadSTD.h:37-74, 87-117), every product through mulop(), i.e. with the bit-field reading of exponent 255.
  * Slow and obviously sequential: biquad_simple runs it for every chain (cross-check path; until round 5 cascades longer than 64
  * sections), biquad_pipe for a chain whose block turned up an Inf or NaN.                                        */
-template <int FMT>
-__device__ void cascade_in_reference_order(const BiquadArgs &a, int cid, const avdsp_chain &c)
+/* WIDE: the chains of the launch have a dressed finish (finish_stage takes the last section's accumulator) */
+template <int FMT, bool WIDE = false>
+__device__ void cascade_in_reference_order(const BqArgs<WIDE> &a, int cid, const DevChain &c)
 {
     using alu_t = typename Alu<FMT>::type;
     const unsigned *inp = a.io.in + (c.in_io - a.io.in_base);
@@ -483,12 +518,17 @@ __device__ void cascade_in_reference_order(const BiquadArgs &a, int cid, const a
         }
         if (c.fir_taps) ring_put(a.ring, cid, n, narrow_stage<FMT>(X), a.ready != nullptr);
         else if (c.sat == kStoreRaw) emit_out(a.io, c, n, xin);      /* (a piece of a long cascade: the last section's result word) */
+        else if constexpr (WIDE) emit_out(a.io, c, n, finish_stage<FMT>(X, a.finish[cid].finish, a.finish[cid].gain_bits, a.addend[n], a.io.store_mask));
         else emit_out(a.io, c, n, store_stage<FMT>(X, c.sat, a.io.store_mask));
     }
 }
 
-template <int FMT, int P>
-__global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
+/* WIDE ("chain_finish"): chains with a dressed finish.  The output batch carries the last section's whole accumulator in every format
+ * (format 6 otherwise hands on its float, format 2 acc >> 28 -- not enough for a gain or an addend in front of SAT0DB), format 6 takes
+ * the C++ step instead of the hand-scheduled one (whose output register is the float), and a lane finishes the accumulator it ends up
+ * holding with finish_stage.  WIDE false is the kernel as it was. */
+template <int FMT, int P, bool WIDE = false>
+__global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     BQ_STAMP(0);
@@ -503,12 +543,14 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
     const int s = tid % P;
     const Ring ring_l = a.ring;                         /* by value: the lambdas below must not make the kernel arguments addressable */
     const BlockIO io_l = a.io;
+    [[maybe_unused]] const unsigned long long *addend_l = nullptr;
+    if constexpr (WIDE) addend_l = a.addend;
     const int nsec = a.nsec, B = io_l.nframes;
     const bool have_chain = slot < a.ngroup;
     /* (lanes without a chain fetch like the others -- see below -- so they take the launch's FIRST chain, whose input column the launch's
      * block has: chain 0 of the plan may be a piece of a long cascade with a column in another launch's scratch block) */
     const int cid = a.group[have_chain ? slot : 0];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const bool lane_on = have_chain && s < nsec;
     const bool first = s == 0;
     const bool last = lane_on && s == nsec - 1;
@@ -528,7 +570,9 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
     }
     owner = owner && oslot < a.ngroup;
     const int ocid = a.group[owner ? oslot : 0];
-    const avdsp_chain oc = a.chains[ocid];
+    const DevChain oc = a.chains[ocid];
+    [[maybe_unused]] FinishRec ofin{0, 0u};
+    if constexpr (WIDE) ofin = a.finish[ocid];
     const int ostep = NB - 1 - d;                       /* step of the batch whose result this lane stores */
     [[maybe_unused]] const unsigned long long lastmask = __ballot(last);   /* lanes whose results leave the cascade */
 
@@ -593,7 +637,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
         }
         ib = ibr;
         ob_lo = dpp_mov<kRowRor1>(ob_lo, ob_lo);
-        if constexpr (FMT == 4) ob_hi = dpp_mov<kRowRor1>(ob_hi, ob_hi);
+        if constexpr (FMT == 4 || WIDE) ob_hi = dpp_mov<kRowRor1>(ob_hi, ob_hi);
         bool act = true;
         if constexpr (decltype(masked)::value) { const int n = u - 1 - 2 * s; act = lane_on && n >= 0 && n < B; }
         if (act) {
@@ -636,7 +680,10 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
                  * into the int sample); the float sample of format 6 is a function of (float)acc alone -- SAT0DB
                  * before or after the rounding gives the same float -- and the int64 store is either the low word
                  * of acc or, behind SAT0DB, acc >> 28, which the section has just formed.                     */
-                if constexpr (FMT == 4) {
+                if constexpr (WIDE && FMT == 2) {
+                    const unsigned long long bits = (unsigned long long)acc;
+                    ob_lo = (unsigned)bits; ob_hi = (unsigned)(bits >> 32);
+                } else if constexpr (FMT == 4 || WIDE) {
                     const unsigned long long bits = (unsigned long long)__double_as_longlong(acc);
                     ob_lo = (unsigned)bits; ob_hi = (unsigned)(bits >> 32);
                 } else if constexpr (FMT == 6) ob_lo = y1;
@@ -658,7 +705,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
     BQ_STAMP(1);
     /* the NB steps of a batch in which every lane is busy */
     auto fast_steps = [&](int tb) __attribute__((always_inline)) {
-        if constexpr (FMT == 6 && P == 16) {
+        if constexpr (FMT == 6 && P == 16 && !WIDE) {
                     /* The same thirteen instructions per step, in an order the compiler does not find: it issues the
                      * five dependent v_fma_f64 back to back (each waits ~4 cycles for its predecessor) and the eight
                      * independent instructions after them.  Here one of those sits behind every FMA, and the first FMA of
@@ -704,8 +751,13 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
                 }
     };
     /* what a lane's output-batch register holds, as the word that goes to the ring (a FIR follows) or to the output block */
-    auto flush_word = [&](bool to_ring) __attribute__((always_inline)) -> unsigned {
-        if constexpr (FMT == 4) {
+    auto flush_word = [&](bool to_ring, [[maybe_unused]] int n) __attribute__((always_inline)) -> unsigned {
+        if constexpr (WIDE) {                           /* (no FIR behind a dressed chain, and only the last piece of a long one is WIDE) */
+            const unsigned long long bits = ((unsigned long long)ob_hi << 32) | ob_lo;
+            alu_t X;
+            if constexpr (FMT == 2) X = (long long)bits; else X = __longlong_as_double((long long)bits);
+            return finish_stage<FMT>(X, ofin.finish, ofin.gain_bits, addend_l[n], io_l.store_mask);
+        } else if constexpr (FMT == 4) {
             const double X = __longlong_as_double((long long)(((unsigned long long)ob_hi << 32) | ob_lo));
             return to_ring || oc.sat == kStoreRaw ? narrow_stage<FMT>(X) : store_stage<FMT>(X, oc.sat, io_l.store_mask);
         } else if constexpr (FMT == 6) {
@@ -729,8 +781,8 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
         /* flush the output batch: this lane holds the result of step tb + ostep of chain `ocid` */
         const int n = tb + ostep - 1 - 2 * (nsec - 1);
         if (owner && n >= 0 && n < B) {
-            if (FMT != 2 && oc.fir_taps) ring_put(ring_l, ocid, n, flush_word(true), a.ready != nullptr);
-            else emit_out(io_l, oc, n, flush_word(false));
+            if (FMT != 2 && oc.fir_taps) ring_put(ring_l, ocid, n, flush_word(true, n), a.ready != nullptr);
+            else emit_out(io_l, oc, n, flush_word(false, n));
         }
     };
     /* The batches in the middle of the block -- all but the first and the last few -- need none of that: every step is busy,
@@ -764,7 +816,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
             in_run += in_step;
             if (owner) {
                 if (to_ring) {
-                    const unsigned w = flush_word(true);
+                    const unsigned w = flush_word(true, n_run);
                     if (wt) {                             /* (write-through, like ring_put) */
                         __hip_atomic_store(reinterpret_cast<unsigned *>(rrow) + ridx, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(reinterpret_cast<unsigned *>(rrow) + ridx + (rmask + 1u), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -778,7 +830,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
                         if (wrow) { const double wd = mulop(__uint_as_float(w)); wrow[(ridx + 3u) & rmask] = wd; wrow[((ridx + 3u) & rmask) + (rmask + 1u)] = wd; }
                     }
                 } else {
-                    const unsigned w = flush_word(false);
+                    const unsigned w = flush_word(false, n_run);
                     if (more_stores) emit_out(io_l, oc, n_run, w);      /* (several STOREs of the same value: the general way) */
                     else *out_run = w;
                 }
@@ -829,9 +881,9 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BiquadArgs a)
         if (replay && have_chain && s == 0) {
             /* copies made here, in the branch nobody takes: the callee wants its arguments in memory, and without them the
              * kernel's own arguments would live there for the whole loop */
-            const BiquadArgs a2 = a;
-            const avdsp_chain c2 = a2.chains[cid];
-            cascade_in_reference_order<FMT>(a2, cid, c2);
+            const BqArgs<WIDE> a2 = a;
+            const DevChain c2 = a2.chains[cid];
+            cascade_in_reference_order<FMT, WIDE>(a2, cid, c2);
         }
     }
     if (a.ready) {                                      /* the chains' blocks are in the ring: say so (a chain's lanes sit in one wave) */
@@ -955,7 +1007,7 @@ __global__ __launch_bounds__(kBlock) void biquad_row(const BiquadArgs a)
                 const unsigned v = !ACC && c_sat ? __float_as_uint(saturate_f32_0db(__uint_as_float(w))) : w;      /* (ACC: w is the stored word already) */
                 if (one_store) io_l.out[(size_t)n * io_l.out_stride + (rr.out_io - io_l.out_base)] = v;     /* (the record has the column: no look at the chain) */
                 else {
-                    const avdsp_chain oc = a.chains[cid];
+                    const DevChain oc = a.chains[cid];
                     emit_out(io_l, oc, n, v);
                 }
             }
@@ -1299,7 +1351,7 @@ __global__ __launch_bounds__(kBlock) void biquad_row(const BiquadArgs a)
     }
     if (replay && have_chain && sec == 0) {
         const BiquadArgs a2 = a;
-        const avdsp_chain c2 = a2.chains[cid];
+        const DevChain c2 = a2.chains[cid];
         cascade_in_reference_order<FMT>(a2, cid, c2);
     }
     if (a.ready) {                                      /* the rows' blocks are in the ring: say so */
@@ -1381,7 +1433,7 @@ __global__ __launch_bounds__(kBlock) void biquad_row_i64(const BiquadArgs a)
         if (have_chain && n >= 0 && n < B) {
             if ((rr.flags >> 16 & 0xFF) == 1) io_l.out[(size_t)n * io_l.out_stride + (rr.out_io - io_l.out_base)] = w;   /* (the record has the column) */
             else {
-                const avdsp_chain oc = a.chains[cid];
+                const DevChain oc = a.chains[cid];
                 emit_out(io_l, oc, n, w);
             }
         }
@@ -1610,13 +1662,13 @@ __global__ __launch_bounds__(kBlock) void biquad_row_i64(const BiquadArgs a)
 }
 
 /* lane per chain, the reference's loop order: the cross-check path ("biquad_impl" 0) */
-template <int FMT>
-__global__ __launch_bounds__(64) void biquad_simple(const BiquadArgs a)
+template <int FMT, bool WIDE = false>
+__global__ __launch_bounds__(64) void biquad_simple(const BqArgs<WIDE> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     const int slot = blockIdx.x * 64 + threadIdx.x;
     const int cid = slot < a.ngroup ? a.group[slot] : -1;
-    if (cid >= 0) cascade_in_reference_order<FMT>(a, cid, a.chains[cid]);
+    if (cid >= 0) cascade_in_reference_order<FMT, WIDE>(a, cid, a.chains[cid]);
     if (a.ready) {
         chain_ready_release();
         if (cid >= 0 && a.chains[cid].fir_taps) chain_ready_publish(a.ready, cid, a.seq);
@@ -1628,7 +1680,7 @@ __global__ __launch_bounds__(64) void biquad_simple(const BiquadArgs a)
  * ---------------------------------------------------------------------------------------- */
 struct FirArgs {
     int            *buf;
-    const avdsp_chain *chains;
+    const DevChain *chains;
     const int      *group;
     int             ngroup;
     Ring            ring;
@@ -1668,7 +1720,7 @@ __device__ __forceinline__ unsigned fir_input_word(unsigned raw, int load_mode, 
 
 /* FIR-only chains: the FIR's input is (float)X of the load stage; append it to the ring first */
 template <int FMT>
-__device__ __forceinline__ void fir_append_input(const FirArgs &a, const avdsp_chain &c, int cid)
+__device__ __forceinline__ void fir_append_input(const FirArgs &a, const DevChain &c, int cid)
 {
     const int B = a.io.nframes;
     const unsigned *inp = a.io.in + (c.in_io - a.io.in_base);
@@ -1701,7 +1753,7 @@ __device__ __forceinline__ int fir_win_slot(int u, int tid)
     return 16 * (16 * (t >> 4) + i) + (t & 15);
 }
 
-__device__ __forceinline__ void fir_chunk_fetch(const FirArgs &a, const avdsp_chain &c, int cid, int mlo, ChunkRegs &r)
+__device__ __forceinline__ void fir_chunk_fetch(const FirArgs &a, const DevChain &c, int cid, int mlo, ChunkRegs &r)
 {
     const int T = c.fir_taps, B = a.io.nframes, tid = threadIdx.x;
     const float *taps = reinterpret_cast<const float *>(a.buf + c.fir_coef_word);
@@ -1742,7 +1794,7 @@ __global__ __launch_bounds__(kBlock, NG == 1 ? 5 : 4) void fir_mfma(const FirArg
     const int slot = xcd_remap(blockIdx.x, a.per_xcd);
     if (slot >= a.ngroup) return;
     const int cid = a.group[slot];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     double *hs = lds, *xs = lds + a.hs_cap;
     const int row = a.win_row, gpc = a.gpc;
     const int T = c.fir_taps, B = a.io.nframes;
@@ -1856,7 +1908,7 @@ static_assert(TileGeom<4>::ROW >= 16 + (4 * (TileGeom<4>::CKMAX - 1) + 63) / 64 
               TileGeom<1, true>::ROW >= 16 + (4 * (TileGeom<1, true>::CKMAX - 1) + 15) / 16, "window rows hold a chunk");
 
 struct FirTileArgs {
-    int *buf; const avdsp_chain *chains; const int *group; int ngroup; Ring ring; int per_xcd;
+    int *buf; const DevChain *chains; const int *group; int ngroup; Ring ring; int per_xcd;
     const double *taps64; int pitch64;       /* f64 copy of the taps, [chain id][pitch64] */
     BlockIO io;
     unsigned *ready; unsigned seq; unsigned *timeouts;      /* chain_ready_wait: null = the launch is ordered behind its cascades by the stream / an event */
@@ -1926,7 +1978,7 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
             const int sl = SPLIT ? blk >> 1 : blk * (4 >> wsh) + q;      /* (SPLIT: the workgroup is two tiles of one chain) */
             if (sl < a.ngroup) {
                 const int ci = a.group[sl];
-                const avdsp_chain cc = a.chains[ci];
+                const DevChain cc = a.chains[ci];
                 if (cc.nsec == 0) fir_append_input<FMT>(fa, cc, ci);
             }
         }
@@ -1956,7 +2008,7 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
     /* the wave's unit -- chain, tap count, ring row, taps -- is the same for all its lanes: say so (scalar registers, scalar
      * address arithmetic, and loads in the base + 32-bit offset form) */
     const int cid = __builtin_amdgcn_readfirstlane(a.group[slot]);
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int T = __builtin_amdgcn_readfirstlane(c.fir_taps);
     double *hs = lds + (size_t)wv * G::LDS_DOUBLES, *ws = hs + 2 * G::HLEN;     /* taps images at hs and hs + HLEN */
     const double *hbuf = a.taps64 + (size_t)cid * a.pitch64;
@@ -2315,7 +2367,7 @@ static_assert(SharedGeom<1>::LDS_DOUBLES * 8 <= 64 * 1024 && SharedGeom<2>::LDS_
 static_assert(SharedGeom<4>::HLEN / 128 <= 4, "one taps piece per wave");
 
 struct FirSharedArgs {
-    int *buf; const avdsp_chain *chains; const int *ids; const SharedTile *tiles; int ntiles; int nfb; Ring ring; int per_xcd;
+    int *buf; const DevChain *chains; const int *ids; const SharedTile *tiles; int ntiles; int nfb; Ring ring; int per_xcd;
     const double *taps64; int pitch64;       /* f64 copy of the groups' taps, [group][pitch64] (taps64_pitch) */
     BlockIO io;
 };
@@ -2423,7 +2475,7 @@ __global__ __launch_bounds__(kBlock, 2) void fir_shared(const FirSharedArgs a)
     }
     if (!active || !col) return;
     /* C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15 (the chain), row = (lane >> 4) + 4 * reg (the frame) */
-    const avdsp_chain c = a.chains[my_cid];
+    const DevChain c = a.chains[my_cid];
     /* Inf / NaN among a column's samples make its sums non-finite (Inf x 0 is a NaN; the reference reads exponent 255 as 2^128 x 1.m):
      * such an output is summed again tap by tap with the reference's operands (fir_tile's LEAN look, per output) */
     bool odd = false;
@@ -2652,7 +2704,7 @@ __global__ __launch_bounds__(kStreamBlock, 1) void fir_stream(const FirTileArgs 
     int n = 0;
     for (; u < nunits; u += npairs) {
         const StreamUnit d = unit_of(u);
-        const avdsp_chain c = a.chains[d.cid];
+        const DevChain c = a.chains[d.cid];
 #pragma unroll
         for (int r = 0; r < R; r++) acc[r] = v4f64{0.0, 0.0, 0.0, 0.0};
         if (n == 0) FIR_STAMP(24);
@@ -2762,7 +2814,7 @@ __global__ __launch_bounds__(kBlock, BIG ? 1 : 2) void fir_flow(const FirTileArg
             const int sl = blk * (4 / G::WPC) + q;
             if (sl < a.ngroup) {
                 const int ci = a.group[sl];
-                const avdsp_chain cc = a.chains[ci];
+                const DevChain cc = a.chains[ci];
                 if (cc.nsec == 0) fir_append_input<FMT>(fa, cc, ci);
             }
         }
@@ -2785,7 +2837,7 @@ __global__ __launch_bounds__(kBlock, BIG ? 1 : 2) void fir_flow(const FirTileArg
         return;
     }
     const int cid = __builtin_amdgcn_readfirstlane(a.group[slot]);
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int T = __builtin_amdgcn_readfirstlane(c.fir_taps);
     if (a.ready && c.nsec) chain_ready_wait(a.ready, cid, a.seq, a.timeouts, a.ready_acquire != 0);
     double *hs = lds + (size_t)wv * G::LDS_DOUBLES, *ws = hs + 2 * G::HLEN;
@@ -2977,7 +3029,7 @@ __global__ __launch_bounds__(kBlock) void fir_feed(const FirTileArgs a)
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
         const int slot = (int)(g % a.ngroup), n = (int)(g / a.ngroup);
         const int cid = a.group[slot];
-        const avdsp_chain c = a.chains[cid];
+        const DevChain c = a.chains[cid];
         if (c.nsec) continue;
         unsigned raw = a.io.in[(size_t)n * a.io.in_stride + (c.in_io - a.io.in_base)];
         if constexpr (FMT == 6) raw = ftz_bits(raw);
@@ -2986,11 +3038,11 @@ __global__ __launch_bounds__(kBlock) void fir_feed(const FirTileArgs a)
 }
 
 /* the f64 copy of a chain's taps, made once per plan: Hbuf[j] = mulop(h[j - kTapsLead]), zeros around */
-struct Taps64Args { const int *buf; const avdsp_chain *chains; const int *group; double *taps64; int pitch64; int by_index; };
+struct Taps64Args { const int *buf; const DevChain *chains; const int *group; double *taps64; int pitch64; int by_index; };
 __global__ __launch_bounds__(kBlock) void taps_to_f64(const Taps64Args a)
 {
     const int cid = a.group[blockIdx.x];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const float *taps = reinterpret_cast<const float *>(a.buf + c.fir_coef_word);
     double *dst = a.taps64 + (size_t)(a.by_index ? (int)blockIdx.x : cid) * a.pitch64;     /* (by_index: fir_shared's row per group) */
     for (int j = threadIdx.x; j < a.pitch64; j += blockDim.x) {
@@ -3008,7 +3060,7 @@ __global__ __launch_bounds__(kBlock) void fir_plain(const FirArgs a)
     const int slot = xcd_remap(blockIdx.x, a.per_xcd);
     if (slot >= a.ngroup) return;
     const int cid = a.group[slot];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int T = c.fir_taps, B = a.io.nframes;
     if (c.nsec == 0) fir_append_input<FMT>(a, c, cid);
     const float *taps = reinterpret_cast<const float *>(a.buf + c.fir_coef_word);
@@ -3024,19 +3076,19 @@ __global__ __launch_bounds__(kBlock) void fir_plain(const FirArgs a)
 
 /* ring <-> reference delay-line layout, one workgroup per FIR chain */
 struct RingConvArgs {
-    int *buf; const avdsp_chain *chains; const int *group; int ngroup; Ring ring;
+    int *buf; const DevChain *chains; const int *group; int ngroup; Ring ring;
 };
 __global__ __launch_bounds__(kBlock) void ring_to_state(const RingConvArgs a)
 {
     const int cid = a.group[blockIdx.x];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     float *st = reinterpret_cast<float *>(a.buf + c.fir_state_word);
     for (int i = threadIdx.x; i < c.fir_taps; i += blockDim.x) st[i] = *ring_at(a.ring, cid, -1 - i);
 }
 __global__ __launch_bounds__(kBlock) void state_to_ring(const RingConvArgs a)
 {
     const int cid = a.group[blockIdx.x];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const float *st = reinterpret_cast<const float *>(a.buf + c.fir_state_word);
     for (int i = threadIdx.x; i < a.ring.R; i += blockDim.x) ring_put(a.ring, cid, -1 - i, i < c.fir_taps ? __float_as_uint(st[i]) : 0u);
 }
@@ -3052,22 +3104,31 @@ __global__ __launch_bounds__(kBlock) void ring_widen(const RingConvArgs a)
 
 /* chains with neither biquads nor FIR: LOAD -> [SAT0DB] -> STORE */
 struct PassArgs {
-    const avdsp_chain *chains;
+    const DevChain *chains;
     const int *group;
     int ngroup;
     BlockIO io;
 };
+struct PassArgsDressed : PassArgs {        /* chains with a dressed finish */
+    const unsigned long long *addend;      /* the dither addend of every frame of this launch (dither_block) */
+    const FinishRec *finish;               /* [chain record] */
+};
 
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void passthrough(const PassArgs a)
+/* DRESSED: the chains have a dressed finish (LOAD -> SAT0DB_TPDF / _GAIN / _TPDF_GAIN -> STORE) */
+template <int FMT, bool DRESSED = false>
+__global__ __launch_bounds__(kBlock) void passthrough(const std::conditional_t<DRESSED, PassArgsDressed, PassArgs> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     const long long total = (long long)a.ngroup * a.io.nframes;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
         const int slot = (int)(g % a.ngroup), n = (int)(g / a.ngroup);
-        const avdsp_chain c = a.chains[a.group[slot]];
+        const DevChain c = a.chains[a.group[slot]];
         auto X = load_stage<FMT>(a.io.in[(size_t)n * a.io.in_stride + (c.in_io - a.io.in_base)], c.load_mode, c.gain_bits);
-        emit_out(a.io, c, n, store_stage<FMT>(X, c.sat, a.io.store_mask));
+        if constexpr (DRESSED) {
+            const FinishRec fin = a.finish[a.group[slot]];
+            emit_out(a.io, c, n, finish_stage<FMT>(X, fin.finish, fin.gain_bits, a.addend[n], a.io.store_mask));
+        }
+        else emit_out(a.io, c, n, store_stage<FMT>(X, c.sat, a.io.store_mask));
     }
 }
 
@@ -3300,6 +3361,77 @@ __global__ __launch_bounds__(kBlock) void tag_column(const TagArgs a)
 static constexpr int kStrandMaxOps = 512;         /* operations per strand (strand_lanes keeps the list in LDS) */
 #include "avdsp_interp.inc"
 
+/* ------------------------------------------------------------------------------------------
+ * Dressed finishes ("chain_finish"): DSP_SAT0DB_TPDF / _GAIN / _TPDF_GAIN in a chain's SAT0DB slot, and the
+ * DSP_TPDF_CALC at the head of the core.  The arithmetic is the interpreter's (fmul, to_sp, sat0db, strand_dither ...), not a copy.
+ * ---------------------------------------------------------------------------------------- */
+#pragma clang fp contract(off)
+/* dsp_runtime.c:494-534, then :610-633.  `addend`: the bits of what dspTpdfApply adds in this frame (dsp_tpdf.h:133-156) -- a double,
+ * or the shifted value of the int64 model.  The addition is made whenever the finish dithers, also with 0.0 (-0.0 + 0.0 is +0.0);
+ * a finish without dither gets none. */
+template <int FMT>
+__device__ __forceinline__ unsigned finish_stage(typename Alu<FMT>::type X, int finish, unsigned gain_bits, unsigned long long addend, int mask)
+{
+    using namespace interp;
+    if (finish & AVDSP_FINISH_GAIN) {
+        if constexpr (FMT == 2) X = (long long)((unsigned long long)(X >> 28) * (unsigned long long)(long long)(int)gain_bits);
+        else X = fmul<FMT>(to_sp<FMT>(X), __uint_as_float(gain_bits));
+    }
+    if (finish & AVDSP_FINISH_TPDF) {
+        if constexpr (FMT == 2) X = (long long)((unsigned long long)X + addend);
+        else X = X + __longlong_as_double((long long)addend);
+    }
+    return store_stage<FMT>(sat0db<FMT>(X), 0, mask);
+}
+
+/* One wave per block call, on the call's stream ahead of the cascades: the core's DSP_TPDF_CALC over the whole block (has_calc: what
+ * tpdf_walk does -- the generator frame by frame, a first frame that finds another dither width only installs the new one, the
+ * result word, the globals written back), and every frame's addend into table[frame].  A core without the opcode dithers with the
+ * value the globals hold when its block starts: the table is that value's addend throughout. */
+template <int FMT>
+__global__ __launch_bounds__(64) void dither_block(TpdfGlobals *g, int *buf, int has_calc, int dith, int result_word, unsigned long long *table, int nframes)
+{
+    using namespace interp;
+    using alu_t = typename M<FMT>::alu;
+    const int lane = threadIdx.x;
+    TpdfLocal tp = g->global;
+    unsigned xs[4] = {g->xs[0], g->xs[1], g->xs[2], g->xs[3]};
+    int gv = g->value, gr = g->random;
+    const int want = dith ? dith : g->default_dither;
+    const int first = has_calc && want != tp.dither ? 1 : 0;
+    if (first) tpdf_prepare<FMT>(g, &tp, &tp, dith);          /* (every lane on its copy; the globals get it at the end) */
+    auto put = [&](int n, int v) __attribute__((always_inline)) {
+        int w[2] = {0, 0};
+        st_alu<FMT>(w, strand_dither<FMT>(v, tp));
+        table[n] = ((unsigned long long)(unsigned)w[1] << 32) | (unsigned)w[0];
+    };
+    if (!has_calc) {
+        for (int n = lane; n < nframes; n += 64) put(n, gv);
+        return;
+    }
+    for (int n0 = 0; n0 < nframes; n0 += 64) {
+        const int nb = min(64, nframes - n0), fst = n0 ? 0 : first;
+        int r1 = 0, r2 = 0;
+        for (int f = fst; f < nb; f++) {
+            const int a1 = (int)xoshiro128p(xs), a2 = (int)xoshiro128p(xs);
+            if (lane == f) { r1 = a1; r2 = a2; }
+        }
+        if (lane >= fst) { gv = (r1 >> 1) + (r2 >> 1); gr = r2; }
+        if (lane < nb) put(n0 + lane, gv);
+        if (n0 + nb == nframes && lane == nb - 1) {
+            g->xs[0] = xs[0]; g->xs[1] = xs[1]; g->xs[2] = xs[2]; g->xs[3] = xs[3];
+            if (first) g->global = tp;
+            if (lane >= fst) {
+                g->value = gv; g->random = gr;
+                alu_t X;
+                if constexpr (M<FMT>::alu_int) X = gv; else X = from_int_scaled<FMT>(gv, 31);
+                st_alu<FMT>(buf + result_word, X);
+            }
+        }
+    }
+}
+#pragma clang fp contract(fast)
+
 
 /* ------------------------------------------------------------------------------------------
  * chain_lane<FMT>: the chain shape  LOAD | LOAD_GAIN -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+  with ONE LANE PER CHAIN,
@@ -3309,7 +3441,7 @@ static constexpr int kStrandMaxOps = 512;         /* operations per strand (stra
  * are the interpreter's (goldens in all five models); a program of N channels runs N lanes wide instead of on one wave.
  * ---------------------------------------------------------------------------------------- */
 struct LaneArgs {
-    int *buf; const avdsp_chain *chains; const int *sec_coef, *sec_state; int nchains; BlockIO io;
+    int *buf; const DevChain *chains; const int *sec_coef, *sec_state; int nchains; BlockIO io;
     /* chains with a FIR: the cascade's outputs go to the chain's row of a sequence buffer, x[m] of the block at seq[row + hist + m]
      * with the delay line's content in front of it (m < 0), and fir_lane works from there; seq == nullptr: the FIR runs here, tap by
      * tap on the mirror's delay line (single frames) */
@@ -3326,7 +3458,7 @@ __global__ __launch_bounds__(64) void chain_lane(const LaneArgs a)
     flush_f32_subnormals_like_the_reference();
     const int cid = blockIdx.x * 64 + threadIdx.x;
     if (cid >= a.nchains) return;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     if (a.rows_take && c.nsec >= 1 && c.nsec <= 16) return;                    /* chain_rows' */
     if (a.seq && c.nsec == 0 && c.fir_taps) return;                            /* fir_lane_feed's: no cascade, every frame's input at once */
     const unsigned *inp = a.io.in + (c.in_io - a.io.in_base);
@@ -3371,7 +3503,7 @@ __global__ __launch_bounds__(64) void chain_rows(const LaneArgs a, const int *id
     const int gi = blockIdx.x * 4 + row;
     const bool valid = gi < nids;
     const int cid = ids[valid ? gi : nids - 1];
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int S = c.nsec, B = a.io.nframes;
     /* rows are RIGHT-aligned (round 4): the chain's last section sits in lane 15 of its row whatever the section count, so that its
      * results reach the row's lanes with one dpp (row_newbcast:15) and leave sixteen frames at a time; rp is the lane's place in the
@@ -3640,7 +3772,7 @@ constexpr int kFirLaneChunk = 2048, kFirLaneFrames = 256;
 __global__ __launch_bounds__(256) void fir_lane_history(const LaneArgs a)
 {
     const int cid = blockIdx.x;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int i = blockIdx.y * 256 + threadIdx.x;
     if (i < c.fir_taps - 1) a.seq[(size_t)cid * a.pitch + a.hist - 1 - i] = (unsigned)a.buf[c.fir_state_word + i];
 }
@@ -3654,7 +3786,7 @@ __global__ __launch_bounds__(256) void fir_lane_feed(const LaneArgs a)
     using alu_t = typename M<FMT>::alu;
     flush_f32_subnormals_like_the_reference();
     const int cid = blockIdx.x, n = blockIdx.y * 256 + threadIdx.x;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     if (c.nsec != 0 || c.fir_taps == 0 || n >= a.io.nframes) return;
     const unsigned raw = a.io.in[(size_t)n * a.io.in_stride + (c.in_io - a.io.in_base)];
     alu_t X;
@@ -3671,7 +3803,7 @@ __global__ __launch_bounds__(256) void fir_lane_feed(const LaneArgs a)
 __global__ __launch_bounds__(256) void fir_lane_state(const LaneArgs a)
 {
     const int cid = blockIdx.x;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int i = blockIdx.y * 256 + threadIdx.x;
     if (i < c.fir_taps) a.buf[c.fir_state_word + i] = (int)a.seq[(size_t)cid * a.pitch + a.hist + a.io.nframes - 1 - i];
 }
@@ -3690,7 +3822,7 @@ __global__ __launch_bounds__(kFirLaneFrames) void fir_lane(const LaneArgs a)
      * exponent sum, sign into bit 8, 24 x 24 mantissa product >> 22, one normalising shift with its exponent step, pack, float add. */
     __shared__ uint2 ws[kFirLaneChunk + kFirLaneFrames], cs[kFirLaneChunk];
     const int cid = blockIdx.x, t = threadIdx.x, n0 = blockIdx.y * kFirLaneFrames;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int T = c.fir_taps;
     if (T == 0) return;                                  /* (uniform: the whole workgroup is one chain's) */
     const unsigned *x = a.seq + (size_t)cid * a.pitch + a.hist;          /* x[m], m = -(T-1) .. nframes-1 */
@@ -3784,7 +3916,7 @@ __global__ __launch_bounds__(256) void fir_lane_hw(const LaneArgs a)
     unsigned *ws = wsbuf + kFront;
     __shared__ int rng[5];                               /* xmin - 1 (unsigned: a zero exponent counts as 2^32 - 1), xmax, hmin - 1, hmax; [4]: a lane's sum so far is -0.0 or under 2^-101 */
     const int cid = blockIdx.x, t = threadIdx.x, n0 = blockIdx.y * kFirHwFrames;
-    const avdsp_chain c = a.chains[cid];
+    const DevChain c = a.chains[cid];
     const int T = c.fir_taps;
     if (T == 0) return;                                  /* (uniform: the whole workgroup is one chain's) */
     const unsigned *x = a.seq + (size_t)cid * a.pitch + a.hist;          /* x[m], m = -(T-1) .. nframes-1 */
@@ -4044,7 +4176,7 @@ struct Plan {
     size_t ga_lds = 0; bool ga_staged = false;
     int format = 0, nchains = 0, store_mask = -1;
     int instances = 1;                /* > 1: the chains are that many copies of a core's chains (avdsp_plan_desc::instances) */
-    DevArr<avdsp_chain> d_chains;
+    DevArr<DevChain> d_chains;
     DevArr<int> d_sec_coef, d_sec_state;
     /* launch groups (device arrays of chain ids) */
     struct Group { int P = 0, nsec = 0, n = 0; DevArr<int> d_ids; bool all_fir = false;      /* all_fir: every chain of the group feeds a FIR (its cascade writes the ring) */
@@ -4053,13 +4185,20 @@ struct Plan {
                     * hands the word between its last section and piece k + 1's first through column j (the chain's place in the group)
                     * of d_scratch[k & 1], [1024 frames][n] words (kLoadRaw / kStoreRaw) */
                    std::vector<Group> pieces; DevArr<unsigned> d_scratch[2];
-                   bool raw_out = false; };      /* a piece but the last: it stores its last section's result word as it is (biquad_row<4> can) */
+                   bool raw_out = false;         /* a piece but the last: it stores its last section's result word as it is (biquad_row<4> can) */
+                   bool wide = false; };         /* chains with a dressed finish: biquad_pipe's WIDE form (GroupLayout::wide) */
     /* the rows of ALL the plan's 16-lane groups in one table (CascadeLayout::all_rows) for ONE biquad_row launch instead of one per section
      * count: nsec 0 in its arguments (every wave takes its rows' count from their records), no ids.  n 0: not made */
     Group rows_all;
     std::vector<Group> bq;            /* biquad chains grouped by section count (P = lanes per chain) */
     DevArr<int> d_fir_ids;  int n_fir = 0, max_taps = 0;
     DevArr<int> d_pass_ids; int n_pass = 0;
+    /* dressed finishes ("chain_finish") */
+    int n_dressed = 0;                                   /* chains with one (their cascades are the WIDE groups of `bq`) */
+    DevArr<int> d_pass_dressed; int n_pass_dressed = 0;  /* ... those with neither sections nor FIR (passthrough's DRESSED form) */
+    DevArr<FinishRec> d_finish;                          /* [record of d_chains]: the finishes (made when n_dressed) */
+    bool has_calc = false; int calc_arg = 0, calc_word = 0;      /* the core begins with a DSP_TPDF_CALC: its width word, its result word in the mirror */
+    int block_f0 = 0;                                    /* first frame, in the block call, of the launch being made (the addend table's index) */
     /* FIR history rings: [nchains][ring_R] floats, frame 0 of the next block goes to index wpos */
     DevArr<float> d_ring; int ring_R = 0, wpos = 0;
     DevArr<double> d_ring64;                             /* fir_stream: the ring as window operands (Ring::wide) */
@@ -4107,6 +4246,7 @@ struct avdsp_hip_prog {
     int *d_buf = nullptr;
     TpdfGlobals *d_tpdf = nullptr;
     int *d_tpdf_seq = nullptr; int tpdf_seq_frames = 0;   /* per-frame dither values inside a core cut into pieces */
+    unsigned long long *d_addend = nullptr; int addend_frames = 0;      /* dressed finishes: the dither addend of every frame of the block call being run (dither_block), grown to the largest block seen */
     unsigned *d_frame = nullptr; int frame_words = 0;     /* samples[] frame of the general interpreter */
     std::vector<Plan> plans;
     unsigned *d_in = nullptr, *d_out = nullptr; size_t in_cap = 0, out_cap = 0;   /* host-call staging */
@@ -4414,6 +4554,24 @@ int launch_biquad(avdsp_hip_prog *prog, Plan &pl, const Plan::Group &g, const in
     a.buf = prog->d_buf; a.chains = pl.d_chains; a.sec_coef = pl.d_sec_coef; a.sec_state = pl.d_sec_state;
     a.group = ids; a.ngroup = n; a.nsec = g.nsec; a.ring = plan_ring(pl); a.io = io;
     a.ready = with_ready ? pl.d_ready.get() : nullptr; a.seq = pl.seq;
+    if (g.wide) {
+        /* chains with a dressed finish: the forms that keep the last section's whole accumulator (16-lane rows: GroupLayout) */
+        if (!prog->d_addend || !pl.d_finish || g.P != 16) return set_err("a launch of dressed chains without its addend table");
+        BiquadArgsWide w{};
+        static_cast<BiquadArgs &>(w) = a;
+        w.addend = prog->d_addend + pl.block_f0; w.finish = pl.d_finish;
+        if (biquad_impl == 0) {
+            scope.begin();
+            hipLaunchKernelGGL((biquad_simple<FMT, true>), dim3((n + 63) / 64), dim3(64), 0, stream, w);
+            if (stop) HIP_TRY(hipEventRecord(stop, stream));
+        } else {
+            const int nblk = (n + 15) / 16;
+            w.per_xcd = (nblk + 7) / 8;
+            if (launch_timed(scope, (const void *)biquad_pipe<FMT, 16, true>, dim3(w.per_xcd * 8), dim3(kBlock), 0, stream, w, stop)) return -1;
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
       /* (a launch whose FIR waits for the words; its ring stores are then write-through) */
 #ifdef AVDSP_BQ_STAMPS
     {
@@ -4997,6 +5155,17 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         hipLaunchKernelGGL(passthrough<FMT>, dim3(grid), dim3(kBlock), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
+    if (pl.n_pass_dressed) {
+        if (!prog->d_addend || !pl.d_finish) return set_err("a launch of dressed chains without its addend table");
+        ProfileScope scope(prog, stream, AVDSP_KERNEL_PASS); scope.begin();
+        PassArgsDressed a{};
+        a.chains = pl.d_chains; a.group = pl.d_pass_dressed; a.ngroup = pl.n_pass_dressed; a.io = io;
+        a.addend = prog->d_addend + pl.block_f0; a.finish = pl.d_finish;
+        const long long total = (long long)pl.n_pass_dressed * io.nframes;
+        const int grid = (int)std::min<long long>((total + kBlock - 1) / kBlock, 2048);
+        hipLaunchKernelGGL((passthrough<FMT, true>), dim3(grid), dim3(kBlock), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
@@ -5273,7 +5442,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
     (void)hipHostFree(p->h_small); (void)hipHostFree(p->h_ready_flag);
     (void)hipHostFree(p->fs_h); (void)hipFree(p->fs_table);
     for (auto e : p->launch_ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(p->d_tpdf_seq); (void)hipFree(p->d_ready_timeouts); for (auto &x : p->alias) (void)hipFree(x.buf);
+    (void)hipFree(p->d_tpdf_seq); (void)hipFree(p->d_addend); (void)hipFree(p->d_ready_timeouts); for (auto &x : p->alias) (void)hipFree(x.buf);
     (void)hipFree(p->d_inst_buf); (void)hipFree(p->d_inst_tpdf); (void)hipFree(p->d_inst_frame); (void)hipFree(p->d_inst_seq);
     delete p;
 }
@@ -5281,7 +5450,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
 /* device copies of a launch group's tables */
 static int upload_group(Plan::Group &g, const GroupLayout &l)
 {
-    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out;
+    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out; g.wide = l.wide;
     return g.d_ids.upload(l.ids) || g.d_rows.upload(l.rows) || g.d_lanes.upload(l.lanes);
 }
 
@@ -5317,7 +5486,7 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         for (int i = 0; i < d->nchains; i++) if (t.chains[i].nsec >= 1 && t.chains[i].nsec <= 16) rows.push_back(i);
         pl.n_lane_rows = (int)rows.size();
         for (int i = 0; i < d->nchains; i++) pl.n_lane_feed += t.chains[i].nsec == 0 && t.chains[i].fir_taps != 0;
-        if (pl.d_chains.upload(t.chains) || pl.d_lane_rows.upload(rows)) return -1;
+        if (pl.d_chains.upload(dev_records(t.chains)) || pl.d_lane_rows.upload(rows)) return -1;
         prog->plans.push_back(std::move(pl));
         return (int)prog->plans.size() - 1;
     }
@@ -5335,13 +5504,21 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
             for (auto &sc : g.d_scratch) if (sc.alloc((size_t)kFirChunk * l.n) != hipSuccess) return set_err("hipMalloc(scratch of %d long cascades)", l.n);
         pl.bq.push_back(std::move(g));
     }
-    if (pl.d_chains.upload(L.dev_chains)) return -1;
+    if (pl.d_chains.upload(dev_records(L.dev_chains))) return -1;
+    if (t.n_dressed) {
+        std::vector<FinishRec> fin(L.dev_chains.size());
+        for (size_t i = 0; i < fin.size(); i++) fin[i] = FinishRec{L.dev_chains[i].finish, L.dev_chains[i].finish_gain_bits};
+        if (pl.d_finish.upload(fin)) return -1;
+    }
     if (!L.all_rows.empty()) {
         pl.rows_all.P = 16; pl.rows_all.n = (int)L.all_rows.size(); pl.rows_all.all_fir = L.rows_all_fir;
         if (pl.rows_all.d_rows.upload(L.all_rows) || pl.rows_all.d_lanes.upload(L.all_lanes)) return -1;
     }
     pl.n_fir = (int)t.fir.size(); pl.n_pass = (int)t.pass.size();
     if (pl.d_fir_ids.upload(t.fir) || pl.d_pass_ids.upload(t.pass)) return -1;
+    pl.n_dressed = t.n_dressed; pl.n_pass_dressed = (int)t.pass_dressed.size();
+    if (pl.d_pass_dressed.upload(t.pass_dressed)) return -1;
+    pl.has_calc = d->tpdf_calc != 0; pl.calc_arg = d->tpdf_calc_arg; pl.calc_word = d->tpdf_calc_result_word;
     if (pl.n_fir) {
         pl.fir_gpc = fir_groups_per_chunk(pl.max_taps);
         pl.ring_R = ring_length(pl.max_taps);
@@ -5967,7 +6144,26 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         HIP_TRY(hipGetLastError());
         return 0;
     }
+    if (pl.n_dressed || pl.has_calc) {
+        /* dressed finishes: one wave walks the core's TPDF_CALC over the whole block call and leaves every frame's addend, ahead of
+         * the launches below (which index the table by the frame's number in the call) */
+        if (!prog->d_tpdf) return set_err("the dither generator has not been seeded");
+        if (prog->addend_frames < nframes) {
+            HIP_TRY(hipDeviceSynchronize());
+            (void)hipFree(prog->d_addend); prog->d_addend = nullptr; prog->addend_frames = 0;
+            const int cap = std::max(nframes, 4096);
+            HIP_TRY(hipMalloc((void **)&prog->d_addend, (size_t)cap * sizeof(unsigned long long)));
+            prog->addend_frames = cap;
+        }
+        ProfileScope scope(prog, (hipStream_t)stream, AVDSP_KERNEL_GENERIC); scope.begin();
+        const void *fn = pl.format == 2 ? (const void *)dither_block<2> : pl.format == 4 ? (const void *)dither_block<4> : (const void *)dither_block<6>;
+        TpdfGlobals *g = prog->d_tpdf; int *buf = prog->d_buf; int has_calc = pl.has_calc ? 1 : 0, arg = pl.calc_arg, word = pl.calc_word;
+        unsigned long long *table = prog->d_addend; int nf = nframes;
+        void *args[] = {&g, &buf, &has_calc, &arg, &word, &table, &nf};
+        HIP_TRY(hipLaunchKernel(fn, dim3(1), dim3(64), args, 0, (hipStream_t)stream));
+    }
     for (int f0 = 0; f0 < nframes; f0 += kFirChunk) {
+        pl.block_f0 = f0;
         BlockIO io;
         io.in = (const unsigned *)d_in + (size_t)f0 * in_stride;  io.in_stride = in_stride;   io.in_base = in_io_base;
         io.out = (unsigned *)d_out + (size_t)f0 * out_stride;     io.out_stride = out_stride; io.out_base = out_io_base;

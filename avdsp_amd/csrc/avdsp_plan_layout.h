@@ -7,8 +7,8 @@
  * avdsp_hip_prog_add_plan runs the stages in this order; each returns its tables, or an error text for set_err:
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads
- *     check_chains     section ranges, IOs, FIR words, the IO spans, max_taps, the `fir` and `pass` lists
- *     cascade_groups   launch groups by section count, pieces of long cascades, biquad_row's records, the merged row table
+ *     check_chains     section ranges, IOs, FIR words, dressed finishes, the IO spans, max_taps, the `fir` and `pass` lists
+ *     cascade_groups   launch groups by section count (dressed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
  */
 #ifndef AVDSP_PLAN_LAYOUT_H_
@@ -89,6 +89,8 @@ struct ChainTables {
     int n_mux_stored = 0;
     int io_in_min = 0x7FFFFFFF, io_in_max = -1, io_out_min = 0x7FFFFFFF, io_out_max = -1, max_taps = 0;
     std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
+    std::vector<int> pass_dressed;       /* ... of the latter, those with a dressed finish (they are not in `pass`) */
+    int n_dressed = 0;                   /* chains with a dressed finish */
 };
 
 inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
@@ -169,7 +171,18 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             t.fir.push_back(i);
             t.max_taps = std::max(t.max_taps, c.fir_taps);
         }
-        if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) t.pass.push_back(i);
+        if (c.finish) {
+            /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front, no LOAD_MUX plan, no instances */
+            if (c.finish < AVDSP_FINISH_TPDF || c.finish > AVDSP_FINISH_TPDF_GAIN || c.sat != 1) return text("chain %d: finish %d", i, c.finish);
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || c.fir_taps || t.has_mux || d->instances > 1)
+                return text("chain %d: a dressed finish has no kernel here", i);
+            t.n_dressed++;
+        }
+        if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
+    }
+    if (d->tpdf_calc) {
+        if ((d->format != 2 && d->format != 4 && d->format != 6) || t.has_mux || d->instances > 1) return "a head TPDF_CALC has no kernel here";
+        if (d->tpdf_calc_result_word < 0 || (long long)d->tpdf_calc_result_word + 2 > buf_words) return "TPDF_CALC result word outside the loaded buffer";
     }
     return "";
 }
@@ -180,6 +193,8 @@ struct GroupLayout {
     int P = 0, nsec = 0, n = 0;          /* lanes per chain, sections, chains */
     bool all_fir = false;                /* every chain of the group feeds a FIR (its cascade writes the ring) */
     bool raw_out = false;                /* a piece but the last: it stores its last section's result word as it is */
+    bool wide = false;                   /* its chains have a dressed finish: the launch keeps the last section's whole accumulator per frame
+                                            (biquad_pipe's WIDE form; no biquad_row records).  Of a long cascade only the last piece is */
     std::vector<int> ids;                /* the chains' records in `dev_chains` */
     std::vector<RowRec> rows; std::vector<LaneRec> lanes;      /* biquad_row's records (P == 16), sections right-aligned in the row */
     std::vector<GroupLayout> pieces;     /* a cascade of more than kPieceMax sections: launched one after the other; piece k hands the
@@ -220,8 +235,9 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
     for (int i = 0; i < (int)t.chains.size(); i++) {
         const int nsec = t.chains[i].nsec;
         if (!nsec) continue;
-        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec; });
-        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; }
+        const bool wide = t.chains[i].finish != 0;       /* dressed chains: launch groups of their own, next to the others */
+        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide; });
+        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; }
         it->ids.push_back(i);
     }
     for (GroupLayout &g : L.groups) {
@@ -230,6 +246,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
          * step is shorter (one input batch per 16 steps, no mid-row section-0 lanes) and idle lanes cost nothing there */
         g.P = g.nsec > 64 ? 128 : pow2ceil(g.nsec);
         if (g.P < 16 && (long long)g.n * 16 <= 65536) g.P = 16;
+        if (g.wide && g.P < 16) g.P = 16;                /* (dressed chains: the WIDE form exists for 16-lane rows only) */
         g.all_fir = true;
         for (int id : g.ids) g.all_fir = g.all_fir && t.chains[id].fir_taps != 0;
         if (g.nsec > kPieceMax) {
@@ -244,6 +261,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
                 GroupLayout pg;
                 pg.nsec = base + (k < extra ? 1 : 0); pg.P = 16; pg.n = g.n;
                 pg.all_fir = k + 1 == np && g.all_fir; pg.raw_out = k + 1 < np;
+                pg.wide = k + 1 == np && g.wide;
                 pg.ids.resize(g.n);
                 for (int j = 0; j < g.n; j++) {
                     const avdsp_chain &c = t.chains[g.ids[j]];
@@ -251,15 +269,15 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
                     pc.sec_base = c.sec_base + at; pc.nsec = pg.nsec;
                     if (k > 0) { pc.in_io = j; pc.load_mode = kLoadRaw; }
                     if (k + 1 < np) {
-                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j;
+                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j; pc.finish = 0;
                         pg.ids[j] = (int)L.dev_chains.size(); L.dev_chains.push_back(pc);
                     } else { pg.ids[j] = g.ids[j]; L.dev_chains[g.ids[j]] = pc; }
                 }
-                row_records(format, L.dev_chains, t, pg);
+                if (!pg.wide) row_records(format, L.dev_chains, t, pg);
                 g.pieces.push_back(std::move(pg));
                 at += base + (k < extra ? 1 : 0);
             }
-        } else if (g.P == 16) {
+        } else if (g.P == 16 && !g.wide) {
             row_records(format, t.chains, t, g);
             /* ... and the same rows in the table of all lengths: this run, filled up to whole waves.  (An empty row is a copy of a real
              * one with no chain behind it: every lane of a wave FETCHES, section or not -- its input column must be one the block has;

@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -126,6 +126,8 @@ def lib() -> C.CDLL:
         L.dspRuntimeFirGroupInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeMuxInfo.restype = i32
         L.dspRuntimeMuxInfo.argtypes = [i32, vp] + [C.POINTER(i32)] * 4
+        L.dspRuntimeFinishInfo.restype = i32
+        L.dspRuntimeFinishInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -239,6 +241,13 @@ class Runtime:
         self._check(self.L.dspRuntimeMuxInfo(self.fmt, self.cores[core_index], *[C.byref(x) for x in v]))
         keys = ("mux_chains", "groups", "grouped_chains", "longest_list")
         return {k: x.value for k, x in zip(keys, v)}
+
+    def finish_info(self, core_index: int = 0):
+        """dspRuntimeFinishInfo (host-only): (chains with a dressed finish -- SAT0DB_TPDF / _GAIN / _TPDF_GAIN -- that "chain_finish" puts
+        on the chain kernels, 1 if the core begins with a TPDF_CALC that dither_block runs), at the current shard."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeFinishInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):
         """dspRuntimeTagOutput on a host block [frames][out_stride] of int32, in place (linux/avdsp_plugin.c:133-137)."""

@@ -10,6 +10,9 @@
  *     (dsp_runtime.c:565-607, 827-849 + dsp_biquadSTD.h:25-119, 928-969 + dsp_firSTD.h:38-52,
  *      464-475, 610-633)
  *
+ * and, where the host has been asked to ("chain_finish"), chains without FIR and LOAD_MUX whose SAT0DB is one of
+ * SAT0DB_TPDF / SAT0DB_GAIN / SAT0DB_TPDF_GAIN (:478-534), behind an optional DSP_TPDF_CALC at the head of the core (:537-545)
+ *
  * for every chain of the core over a block of frame-interleaved samples.
  */
 #ifndef AVDSP_HIP_H_
@@ -46,7 +49,11 @@ typedef struct avdsp_chain {
     int32_t  mux_word;               /* first pair of the list: (IO number, gain) x mux_count from this word on */
     int32_t  mux_count;              /* pairs, >= 1                                              */
     int32_t  mux_result_word;        /* the 8-byte word the reference leaves the accumulator in every frame (2 words) */
+    /* a dressed finish in the SAT0DB slot (dsp_runtime.c:478-534; `sat` is 1 then): the gain, the frame's dither addend, SAT0DB */
+    int32_t  finish;                 /* AVDSP_FINISH_*; 0: none                                  */
+    uint32_t finish_gain_bits;       /* Q4.28 int or float bits of the SAT0DB[_TPDF]_GAIN parameter */
 } avdsp_chain;
+enum { AVDSP_FINISH_NONE = 0, AVDSP_FINISH_TPDF = 1, AVDSP_FINISH_GAIN = 2, AVDSP_FINISH_TPDF_GAIN = 3 };      /* bit 0: dither, bit 1: gain */
 
 /* words between two copies of the mirror (chain instances, avdsp_hip_chain_instances): even, so that state words keep their alignment */
 #define AVDSP_INSTANCE_STRIDE(total_words) (((total_words) + 1) & ~1)
@@ -71,6 +78,10 @@ typedef struct avdsp_plan_desc {
     int32_t  mux_ngroups;
     const int32_t *mux_group_start;  /* [mux_ngroups + 1]                                                                     */
     const int32_t *mux_group_chains; /* indices into chains[]                                                                 */
+    /* the core begins with a DSP_TPDF_CALC (dsp_runtime.c:537-545): dither_block runs it over the block in front of the chains */
+    int32_t  tpdf_calc;              /* 1: it does                                                                            */
+    int32_t  tpdf_calc_arg;          /* its dither width word (0 = the default)                                               */
+    int32_t  tpdf_calc_result_word;  /* the 8-byte word of the mirror its result goes to                                      */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

@@ -85,7 +85,9 @@ int       dspQM32(double x, int m);         /* dsp_header.c:83-85 */
  *
  * Two device paths sit behind these entry points.  A core that is a set of independent
  * LOAD|LOAD_GAIN -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+ chains runs on parallel kernels in every
- * format (in 2, 4 and 6 a chain may also begin with LOAD_MUX, see dspRuntimeMuxInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
+ * format (in 2, 4 and 6 a chain may also begin with LOAD_MUX, see dspRuntimeMuxInfo; and, with dspRuntimeSetOption("chain_finish", 1),
+ * a chain without FIR and LOAD_MUX may end in SAT0DB_TPDF, SAT0DB_GAIN or SAT0DB_TPDF_GAIN instead of SAT0DB, and the core may begin
+ * with one DSP_TPDF_CALC of the default width, see dspRuntimeFinishInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
  * the MFMA FIR (fir_tile); 3 and 5 -- float accumulators and the truncating dspMulFloatFloat -- on
  * chain_rows (a lane per chain and section) and fir_lane (a lane per chain and frame), with
  * chain_lane for single frames and cascades longer than 16 sections.  Any other core -- X/Y
@@ -288,6 +290,20 @@ int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped
  * list.  A core the interpreter runs reports zeros; a LOAD_MUX whose table is damaged (no entries, an IO number outside the range, a
  * result word outside the state area) returns -8. */
 int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, int *grouped_chains, int *longest_list);
+
+/* Dressed finishes (opt-in: dspRuntimeSetOption("chain_finish", 1); default 0, every such core then runs on the interpreter as before).
+ * In formats 2, 4 and 6 a chain's SAT0DB slot -- behind the banks, in front of the first STORE -- may hold DSP_SAT0DB_TPDF, DSP_SAT0DB_GAIN
+ * or DSP_SAT0DB_TPDF_GAIN (dsp_runtime.c:478-534), and the core may begin, in front of its first LOAD, with one DSP_TPDF_CALC(n), n 0 or
+ * the default dither (:537-545).  One wave (dither_block) then walks the generator over the block ahead of the cascades and leaves every
+ * frame's addend in a table; the cascades keep the last section's whole accumulator and finish it with gain, addend, SAT0DB and the
+ * format's STORE, bit for bit the reference's.  A core without the TPDF_CALC dithers with the value the program's globals hold when its
+ * block starts (the reference's hosts run cores outer, frames inner).  Not lowered, i.e. on the interpreter as before: chains with a
+ * DSP_FIR or a LOAD_MUX head, a TPDF_CALC anywhere else or of another width, a DSP_TPDF opcode, formats 3 and 5, any program in which
+ * some core's TPDF_CALC asks for a width other than the default (the global width is then not constant), and every dressed core while
+ * dspRuntimeSetInstances(n > 1) is in force.
+ * dspRuntimeFinishInfo is host-only, nothing runs on the GPU: the chains with a dressed finish among the chains of the core this process
+ * runs (dspRuntimeSetShard) and whether the core begins with a lowered TPDF_CALC.  A core the interpreter runs reports zeros. */
+int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *tpdf_calc);
 
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
