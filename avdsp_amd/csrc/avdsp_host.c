@@ -115,6 +115,7 @@ typedef struct avdsp_ctx {
     int             opt_frame_server, opt_frame_server_idle_us;      /* "frame_server" (AVDSP_OPT_FRAME_SERVER), "frame_server_idle_us" */
     int             opt_fir_shared;                        /* "fir_shared" (AVDSP_OPT_FIR_SHARED), default 1 */
     int             opt_chain_finish;                      /* "chain_finish": dressed SAT0DB finishes and a head TPDF_CALC lowered to the chain kernels (default 0) */
+    int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
@@ -309,6 +310,11 @@ static int set_option_here(const char *key, int value)
         G.opt_chain_finish = value;
         return replan();
     }
+    if (!strcmp(key, "chain_delay")) {                   /* one DSP_DELAY behind a chain's banks on the chain kernels; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "chain_delay: 0 or 1");
+        G.opt_chain_delay = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -401,6 +407,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "ring_wait"))   return G.opt_ring_wait;
     if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
     if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
+    if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -540,7 +547,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -689,6 +696,7 @@ typedef struct {
     int32_t *coef_word, *state_word; int nsec, cap_sec;
     int tpdf_calc, tpdf_calc_arg, tpdf_calc_word;         /* "chain_finish": the core begins with a DSP_TPDF_CALC; its width word and result word */
     int ndressed;                                         /* ... chains with a dressed finish */
+    int ndelayed;                                         /* "chain_delay": chains with a DSP_DELAY */
 } lowered;
 
 static void lowered_free(lowered *L) { free(L->chains); free(L->coef_word); free(L->state_word); memset(L, 0, sizeof *L); }
@@ -720,6 +728,7 @@ static int push_section(lowered *L, int coef, int state)
     return 0;
 }
 
+static int cmp_ll(const void *a, const void *b) { long long x = *(const long long *)a, y = *(const long long *)b; return (x > y) - (x < y); }
 static int cmp_int(const void *a, const void *b) { int x = *(const int *)a, y = *(const int *)b; return (x > y) - (x < y); }
 
 /* Chains of one core run concurrently on the device, so the sequential reading of the opcode
@@ -785,6 +794,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
     /* dressed finishes and the head TPDF_CALC: opt-in, formats 2, 4 and 6, not while the program has instances (each has a generator
      * of its own on the interpreter) */
     const int finish_on = G.opt_chain_finish && G.ninst <= 1 && (format == 2 || format == 4 || format == 6);
+    const unsigned delay_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* dsp_runtime.c:81-90 */
 
     if (ensure_encoding(format)) return g_err_code;
 
@@ -854,6 +864,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             cur.mux_result_word = prog_words + a[1];
             break; }
         case DSP_BIQUADS: {                                   /* :827-849 */
+            if (open && cur.delay_slot) return fail(-8, "word %d: a DSP_DELAY in front of the banks is not lowered to the HIP path", at);
             if (!open || cur.n_out || cur.sat || cur.fir_taps)
                 return fail(-8, "word %d: BIQUADS outside the supported LOAD->BIQUADS->FIR->SAT0DB->STORE order", at);
             LC_NEED(2);
@@ -872,6 +883,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             cur.nsec = L->nsec - cur.sec_base;
             break; }
         case DSP_FIR: {                                       /* :928-969 */
+            if (open && cur.delay_slot) return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
             if (!open || cur.n_out || cur.sat)
                 return fail(-8, "word %d: FIR outside the supported chain order", at);
             if (!float_alu)
@@ -898,12 +910,37 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             }
             break; }
         case DSP_SAT0DB:                                      /* :464-475 */
-            if (!open || cur.n_out) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
+            if (!open || cur.n_out || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
             cur.sat = 1;
             break;
+        case DSP_DELAY_1: case DSP_DELAY_DP:                  /* "chain_delay": only DSP_DELAY is lowered */
+            if (!G.opt_chain_delay) goto not_lowered;
+            return fail(-8, "word %d: %s is not lowered to the HIP path (of the delay lines only DSP_DELAY is)", at, op == DSP_DELAY_1 ? "DSP_DELAY_1" : "DSP_DELAY_DP");
+        case DSP_DELAY: {                                     /* :769-794, "chain_delay": once per chain, behind the banks, on either side of the SAT0DB slot */
+            if (!G.opt_chain_delay) goto not_lowered;
+            if (format != 2 && format != 4 && format != 6) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path in format %d", at, format);
+            if (G.ninst > 1) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path while the program has instances", at);
+            if (!open) return fail(-8, "word %d: a DSP_DELAY in front of the chain's LOAD is not lowered to the HIP path", at);
+            if (cur.n_out) return fail(-8, "word %d: a DSP_DELAY behind a STORE is not lowered to the HIP path", at);
+            if (cur.delay_slot) return fail(-8, "word %d: a second DSP_DELAY in one chain is not lowered to the HIP path", at);
+            if (fir_op || cur.load_mode == AVDSP_LOAD_MUX)
+                return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR or a LOAD_MUX head is not lowered to the HIP path", at);
+            LC_NEED(3);
+            if (a[0] < 0) return fail(-8, "word %d: delay line of negative size %d", at, a[0]);
+            if (a[2]) LC_PROG(a[2], 1);
+            /* with a parameter the first word is the line's size in samples, without it microseconds (the strand lowering's checks) */
+            const long long nline = a[2] ? (long long)a[0] : (long long)(((unsigned long long)(unsigned)a[0] * delay_factor) >> 32);
+            if (a[1] < 0 || (long long)a[1] + 1 + nline > dspHeaderPtr->dataSize)
+                return fail(-8, "word %d: data offset %d (+%lld) outside the state area (%d words)", at, a[1], 1 + nline, dspHeaderPtr->dataSize);
+            cur.delay_slot = cur.sat ? AVDSP_DELAY_B : AVDSP_DELAY_A;
+            cur.delay_word = prog_words + a[1];
+            cur.delay_us_word = a[2] ? at + a[2] : 0;
+            cur.delay_max = a[0];
+            L->ndelayed++;
+            break; }
         case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:      /* :478-534, "chain_finish" */
             if (!finish_on) goto not_lowered;
-            if (!open || cur.n_out || cur.sat) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
+            if (!open || cur.n_out || cur.sat || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
             if (fir_op || cur.load_mode == AVDSP_LOAD_MUX)
                 return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
             if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
@@ -948,6 +985,26 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
     if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
     if ((L->ndressed || L->tpdf_calc) && lowered_has_mux(L))
         return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
+    if (L->ndelayed && lowered_has_mux(L))
+        return fail(-8, "chains with a DSP_DELAY beside LOAD_MUX heads are not lowered to the HIP path");
+    if (L->ndelayed > 1) {
+        /* the chains run side by side: two of them must not share words of a line (the encoder never lets them; the strand lowering
+         * checks the same).  [first word, words] per line, sorted by the first */
+        long long *iv = (long long *)malloc((size_t)L->ndelayed * 2 * sizeof *iv);
+        if (!iv) return fail(-9, "out of memory");
+        int k = 0, clash = 0;
+        for (int i = 0; i < L->nchains; i++) {
+            const avdsp_chain *c = &L->chains[i];
+            if (!c->delay_slot) continue;
+            iv[2 * k] = c->delay_word;
+            iv[2 * k + 1] = 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
+            k++;
+        }
+        qsort(iv, (size_t)k, 2 * sizeof *iv, cmp_ll);
+        for (int i = 1; i < k && !clash; i++) clash = iv[2 * i] < iv[2 * i - 2] + iv[2 * i - 1];
+        free(iv);
+        if (clash) return fail(-8, "two delay lines of the core share words of the state area");
+    }
     return check_independent(L);
 }
 
@@ -1606,6 +1663,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.nsections = sec1 - sec0; d.sec_coef_word = L.coef_word + sec0; d.sec_state_word = L.state_word + sec0;
         d.store_mask = G.store_mask;
         d.tpdf_calc = L.tpdf_calc; d.tpdf_calc_arg = L.tpdf_calc_arg; d.tpdf_calc_result_word = L.tpdf_calc_word;
+        d.delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* (as lower_core_ex checked the lines' extents) */
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -1813,6 +1871,46 @@ int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *t
     }
     if (dressed_chains) *dressed_chains = nd;
     if (tpdf_calc) *tpdf_calc = calc;
+    return 0;
+}
+
+/* Host-only: what "chain_delay" makes of the core -- the chains with a lowered DSP_DELAY among the chains this process runs
+ * (dspRuntimeSetShard), and the longest of their lines in samples at the current rate (a parameter form counts with the delay its
+ * program word asks for now, clamped to the line's size; a line of 0 samples is a bypass).  No device is touched.  A core that is
+ * not a set of chains has neither. */
+int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *longest_line)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nd = 0, longest = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0) {
+            const unsigned fac = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            for (int i = lo; i < hi; i++) {
+                const avdsp_chain *c = &L.chains[i];
+                if (!c->delay_slot) continue;
+                nd++;
+                unsigned n;
+                if (!c->delay_us_word) n = (unsigned)(((unsigned long long)(unsigned)c->delay_max * fac) >> 32);
+                else {
+                    n = (unsigned)(((unsigned long long)(unsigned short)G.code[c->delay_us_word].i32 * fac) >> 32);
+                    if (n > (unsigned)c->delay_max) n = (unsigned)c->delay_max;
+                }
+                if ((int)n > longest) longest = (int)n;
+            }
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (chains_delayed) *chains_delayed = nd;
+    if (longest_line) *longest_line = longest;
     return 0;
 }
 
@@ -2635,7 +2733,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if (G.opt_chain_finish && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

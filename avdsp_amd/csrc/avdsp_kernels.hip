@@ -418,7 +418,14 @@ struct BiquadArgsWide : BiquadArgs {
     const unsigned long long *addend;      /* the dither addend of every frame of this launch (dither_block) */
     const FinishRec *finish;               /* [chain record] */
 };
+/* launches of delayed chains ("chain_delay", the HAND forms below): nothing is finished or stored, every frame's whole accumulator goes
+ * to the chain's row of the plan's hand-over block, where chain_tail takes it up */
+struct BiquadArgsHand : BiquadArgs {
+    unsigned long long *hand;              /* [hand_row][kFirChunk frames] accumulators */
+    const int *hand_row;                   /* [chain record]: the chain's row */
+};
 template <bool WIDE> using BqArgs = std::conditional_t<WIDE, BiquadArgsWide, BiquadArgs>;
+template <bool WIDE, bool HAND> using BqArgsH = std::conditional_t<HAND, BiquadArgsHand, BqArgs<WIDE>>;
 #ifdef AVDSP_BQ_STAMPS
 #define BQ_STAMP(i) do { if ((threadIdx.x & 63) == 0 && (i) < 32) a.stamps[(size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -472,9 +479,10 @@ __device__ __forceinline__ Hand<FMT> hand_rotate(Hand<FMT> h)
  * (dsp_biquadSTD.h:37-74, 87-117), every product through mulop(), i.e. with the bit-field reading of exponent 255.
  * Slow and obviously sequential: biquad_simple runs it for every chain (cross-check path; until round 5 cascades longer than 64
  * sections), biquad_pipe for a chain whose block turned up an Inf or NaN.                                        */
-/* WIDE: the chains of the launch have a dressed finish (finish_stage takes the last section's accumulator) */
-template <int FMT, bool WIDE = false>
-__device__ void cascade_in_reference_order(const BqArgs<WIDE> &a, int cid, const DevChain &c)
+/* WIDE: the chains of the launch have a dressed finish (finish_stage takes the last section's accumulator); HAND (with WIDE): they have a
+ * delay line instead, and the accumulator goes to the hand-over block */
+template <int FMT, bool WIDE = false, bool HAND = false>
+__device__ void cascade_in_reference_order(const BqArgsH<WIDE, HAND> &a, int cid, const DevChain &c)
 {
     using alu_t = typename Alu<FMT>::type;
     const unsigned *inp = a.io.in + (c.in_io - a.io.in_base);
@@ -518,6 +526,11 @@ __device__ void cascade_in_reference_order(const BqArgs<WIDE> &a, int cid, const
         }
         if (c.fir_taps) ring_put(a.ring, cid, n, narrow_stage<FMT>(X), a.ready != nullptr);
         else if (c.sat == kStoreRaw) emit_out(a.io, c, n, xin);      /* (a piece of a long cascade: the last section's result word) */
+        else if constexpr (HAND) {                      /* a delayed chain: chain_tail goes on from the accumulator */
+            unsigned long long bits;
+            if constexpr (FMT == 2) bits = (unsigned long long)X; else bits = (unsigned long long)__double_as_longlong(X);
+            a.hand[(size_t)a.hand_row[cid] * kFirChunk + n] = bits;
+        }
         else if constexpr (WIDE) emit_out(a.io, c, n, finish_stage<FMT>(X, a.finish[cid].finish, a.finish[cid].gain_bits, a.addend[n], a.io.store_mask));
         else emit_out(a.io, c, n, store_stage<FMT>(X, c.sat, a.io.store_mask));
     }
@@ -526,9 +539,11 @@ __device__ void cascade_in_reference_order(const BqArgs<WIDE> &a, int cid, const
 /* WIDE ("chain_finish"): chains with a dressed finish.  The output batch carries the last section's whole accumulator in every format
  * (format 6 otherwise hands on its float, format 2 acc >> 28 -- not enough for a gain or an addend in front of SAT0DB), format 6 takes
  * the C++ step instead of the hand-scheduled one (whose output register is the float), and a lane finishes the accumulator it ends up
- * holding with finish_stage.  WIDE false is the kernel as it was. */
-template <int FMT, int P, bool WIDE = false>
-__global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
+ * holding with finish_stage.  WIDE false is the kernel as it was.
+ * HAND (with WIDE, "chain_delay"): chains with a delay line -- the accumulator is not finished but stored in the chain's row of the
+ * hand-over block.  HAND false is the kernel as it was. */
+template <int FMT, int P, bool WIDE = false, bool HAND = false>
+__global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgsH<WIDE, HAND> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     BQ_STAMP(0);
@@ -544,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
     const Ring ring_l = a.ring;                         /* by value: the lambdas below must not make the kernel arguments addressable */
     const BlockIO io_l = a.io;
     [[maybe_unused]] const unsigned long long *addend_l = nullptr;
-    if constexpr (WIDE) addend_l = a.addend;
+    if constexpr (WIDE && !HAND) addend_l = a.addend;
     const int nsec = a.nsec, B = io_l.nframes;
     const bool have_chain = slot < a.ngroup;
     /* (lanes without a chain fetch like the others -- see below -- so they take the launch's FIRST chain, whose input column the launch's
@@ -572,7 +587,9 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
     const int ocid = a.group[owner ? oslot : 0];
     const DevChain oc = a.chains[ocid];
     [[maybe_unused]] FinishRec ofin{0, 0u};
-    if constexpr (WIDE) ofin = a.finish[ocid];
+    if constexpr (WIDE && !HAND) ofin = a.finish[ocid];
+    [[maybe_unused]] unsigned long long *hand_l = nullptr;      /* HAND: the row of the hand-over block of the chain this lane flushes */
+    if constexpr (HAND) hand_l = a.hand + (size_t)a.hand_row[ocid] * kFirChunk;
     const int ostep = NB - 1 - d;                       /* step of the batch whose result this lane stores */
     [[maybe_unused]] const unsigned long long lastmask = __ballot(last);   /* lanes whose results leave the cascade */
 
@@ -752,7 +769,8 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
     };
     /* what a lane's output-batch register holds, as the word that goes to the ring (a FIR follows) or to the output block */
     auto flush_word = [&](bool to_ring, [[maybe_unused]] int n) __attribute__((always_inline)) -> unsigned {
-        if constexpr (WIDE) {                           /* (no FIR behind a dressed chain, and only the last piece of a long one is WIDE) */
+        if constexpr (HAND) return 0u;                  /* (nothing is stored: the accumulator goes to hand_l) */
+        else if constexpr (WIDE) {                      /* (no FIR behind a dressed chain, and only the last piece of a long one is WIDE) */
             const unsigned long long bits = ((unsigned long long)ob_hi << 32) | ob_lo;
             alu_t X;
             if constexpr (FMT == 2) X = (long long)bits; else X = __longlong_as_double((long long)bits);
@@ -782,6 +800,7 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
         const int n = tb + ostep - 1 - 2 * (nsec - 1);
         if (owner && n >= 0 && n < B) {
             if (FMT != 2 && oc.fir_taps) ring_put(ring_l, ocid, n, flush_word(true, n), a.ready != nullptr);
+            else if constexpr (HAND) hand_l[n] = ((unsigned long long)ob_hi << 32) | ob_lo;
             else emit_out(io_l, oc, n, flush_word(false, n));
         }
     };
@@ -829,7 +848,8 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
                         rrow[ridx] = __uint_as_float(w); rrow[ridx + (rmask + 1u)] = __uint_as_float(w);
                         if (wrow) { const double wd = mulop(__uint_as_float(w)); wrow[(ridx + 3u) & rmask] = wd; wrow[((ridx + 3u) & rmask) + (rmask + 1u)] = wd; }
                     }
-                } else {
+                } else if constexpr (HAND) hand_l[n_run] = ((unsigned long long)ob_hi << 32) | ob_lo;
+                else {
                     const unsigned w = flush_word(false, n_run);
                     if (more_stores) emit_out(io_l, oc, n_run, w);      /* (several STOREs of the same value: the general way) */
                     else *out_run = w;
@@ -881,9 +901,9 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgs<WIDE> a)
         if (replay && have_chain && s == 0) {
             /* copies made here, in the branch nobody takes: the callee wants its arguments in memory, and without them the
              * kernel's own arguments would live there for the whole loop */
-            const BqArgs<WIDE> a2 = a;
+            const BqArgsH<WIDE, HAND> a2 = a;
             const DevChain c2 = a2.chains[cid];
-            cascade_in_reference_order<FMT, WIDE>(a2, cid, c2);
+            cascade_in_reference_order<FMT, WIDE, HAND>(a2, cid, c2);
         }
     }
     if (a.ready) {                                      /* the chains' blocks are in the ring: say so (a chain's lanes sit in one wave) */
@@ -1673,6 +1693,16 @@ __global__ __launch_bounds__(64) void biquad_simple(const BqArgs<WIDE> a)
         chain_ready_release();
         if (cid >= 0 && a.chains[cid].fir_taps) chain_ready_publish(a.ready, cid, a.seq);
     }
+}
+
+/* ... of delayed chains ("chain_delay"): the accumulators to the hand-over block */
+template <int FMT>
+__global__ __launch_bounds__(64) void biquad_simple_hand(const BiquadArgsHand a)
+{
+    if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    const int cid = slot < a.ngroup ? a.group[slot] : -1;
+    if (cid >= 0) cascade_in_reference_order<FMT, true, true>(a, cid, a.chains[cid]);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -3369,8 +3399,9 @@ static constexpr int kStrandMaxOps = 512;         /* operations per strand (stra
 /* dsp_runtime.c:494-534, then :610-633.  `addend`: the bits of what dspTpdfApply adds in this frame (dsp_tpdf.h:133-156) -- a double,
  * or the shifted value of the int64 model.  The addition is made whenever the finish dithers, also with 0.0 (-0.0 + 0.0 is +0.0);
  * a finish without dither gets none. */
+/* (finish_alu: the accumulator behind the opcode, which a DSP_DELAY behind the slot takes its word from -- chain_tail) */
 template <int FMT>
-__device__ __forceinline__ unsigned finish_stage(typename Alu<FMT>::type X, int finish, unsigned gain_bits, unsigned long long addend, int mask)
+__device__ __forceinline__ typename Alu<FMT>::type finish_alu(typename Alu<FMT>::type X, int finish, unsigned gain_bits, unsigned long long addend)
 {
     using namespace interp;
     if (finish & AVDSP_FINISH_GAIN) {
@@ -3381,7 +3412,97 @@ __device__ __forceinline__ unsigned finish_stage(typename Alu<FMT>::type X, int 
         if constexpr (FMT == 2) X = (long long)((unsigned long long)X + addend);
         else X = X + __longlong_as_double((long long)addend);
     }
-    return store_stage<FMT>(sat0db<FMT>(X), 0, mask);
+    return sat0db<FMT>(X);
+}
+template <int FMT>
+__device__ __forceinline__ unsigned finish_stage(typename Alu<FMT>::type X, int finish, unsigned gain_bits, unsigned long long addend, int mask)
+{
+    return store_stage<FMT>(finish_alu<FMT>(X, finish, gain_bits, addend), 0, mask);
+}
+
+/* ------------------------------------------------------------------------------------------
+ * chain_tail<FMT> ("chain_delay"): what stands behind the banks of a chain with one DSP_DELAY (dsp_runtime.c:769-794)
+ * -- the delay in front of the SAT0DB slot or behind it, the slot's opcode (none, SAT0DB, or a dressed finish), the STOREs.  One
+ * workgroup per chain, a thread per frame of the launch (at most kFirChunk); nobody else touches the chain's line.  A frame's
+ * accumulator comes from the chain's row of the hand-over block (the cascades' HAND forms put it there) or, without sections, from the
+ * sample block.  The line and its index word stay where the reference has them, in the mirror.
+ *
+ * Slot of frame f: the reference's counter stepped frame by frame from the index word (state_index: a counter outside the line's
+ * allocation reads as 0).  A counter at or beyond a line that a parameter edit has shortened is visited once, by frame 0, and the
+ * cycle 0 .. n-1 starts with frame 1 (`odd`, as in strand_lanes).  A frame takes the line's old word on a slot's first visit in the
+ * launch, else the word frame f - n put there (through LDS); every old word is read before the barrier, only a slot's last visitor
+ * writes behind it.  n == 0 (the fixed form at a low rate, a parameter of 0 us) bypasses the opcode: nothing read, nothing written.
+ * ---------------------------------------------------------------------------------------- */
+struct DelayRec {
+    int cid;                                /* the chain's record (input, STOREs) */
+    int slot, line_word, us_word, max;      /* avdsp_chain::delay_slot, ::delay_word, ::delay_us_word, ::delay_max */
+    int hand_row;                           /* its row of the hand-over block; -1: no sections, LOAD / LOAD_GAIN of the sample block */
+    int sat, finish; unsigned gain_bits;    /* the SAT0DB slot: avdsp_chain::sat, ::finish, ::finish_gain_bits */
+};
+struct TailArgs {
+    int *buf; const DevChain *chains; const DelayRec *recs;
+    const unsigned long long *hand, *addend;      /* the hand-over block; the dither addend of every frame of this launch */
+    unsigned delay_factor;
+    BlockIO io;
+};
+template <int FMT>
+__global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a)
+{
+    using namespace interp;
+    using alu_t = typename Alu<FMT>::type;
+    if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
+    __shared__ int put[kFirChunk];                       /* the word each frame puts into the line */
+    const DelayRec r = a.recs[blockIdx.x];
+    const DevChain c = a.chains[r.cid];
+    const int B = a.io.nframes, f = threadIdx.x;
+    const bool on = f < B;                               /* (lanes without a frame read nothing) */
+    unsigned n;                                          /* :772-781 */
+    int alloc;
+    if (r.us_word == 0) { n = (unsigned)(((unsigned long long)(unsigned)r.max * a.delay_factor) >> 32); alloc = (int)n; }
+    else {
+        const unsigned short us = (unsigned short)a.buf[r.us_word];
+        n = (unsigned)(((unsigned long long)us * a.delay_factor) >> 32);
+        if (n > (unsigned)r.max) n = (unsigned)r.max;
+        alloc = r.max;
+    }
+    alu_t X = 0;
+    if (on) {
+        if (r.hand_row >= 0) {
+            const unsigned long long bits = a.hand[(size_t)r.hand_row * kFirChunk + f];
+            if constexpr (FMT == 2) X = (long long)bits; else X = __longlong_as_double((long long)bits);
+        } else X = load_stage<FMT>(a.io.in[(size_t)f * a.io.in_stride + (c.in_io - a.io.in_base)], c.load_mode, c.gain_bits);
+    }
+    auto slot_opcode = [&](alu_t v) __attribute__((always_inline)) -> alu_t {
+        if (r.finish) return finish_alu<FMT>(v, r.finish, r.gain_bits, a.addend[f]);
+        return r.sat ? sat0db<FMT>(v) : v;
+    };
+    if (on && r.slot == AVDSP_DELAY_B) X = slot_opcode(X);
+    if (n) {                                             /* (uniform over the workgroup) */
+        int *d = a.buf + r.line_word;
+        const int p0 = state_index(d[0], alloc);
+        const int odd = (unsigned)p0 >= n ? 1 : 0;
+        const int pos = odd ? (f == 0 ? p0 : (int)((unsigned)(f - 1) % n)) : (int)(((unsigned)p0 + (unsigned)f) % n);
+        const long long k = (long long)f - (long long)n;      /* the frame that visited this slot before */
+        int in = 0, old = 0;
+        if (on) {
+            if constexpr (FMT == 2) in = (int)X; else in = __float_as_int(to_sp<FMT>(X));
+            put[f] = in;
+            if (k < odd) old = d[1 + pos];
+        }
+        /* every read of the line and of its index word has come back before anyone writes either */
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (on) {
+            const int v = k >= odd ? put[(int)k] : old;
+            if constexpr (FMT == 2) X = (long long)v; else X = to_alu<FMT>(__int_as_float(v));
+            if ((long long)f + (long long)n >= B || (odd && f == 0)) d[1 + pos] = in;      /* the slot's last visitor */
+            if (f == B - 1) { const int nx = pos + 1; d[0] = (unsigned)nx >= n ? 0 : nx; }
+        }
+    }
+    if (on) {
+        if (r.slot == AVDSP_DELAY_A) X = slot_opcode(X);
+        emit_out(a.io, c, f, store_stage<FMT>(X, 0, a.io.store_mask));
+    }
 }
 
 /* One wave per block call, on the call's stream ahead of the cascades: the core's DSP_TPDF_CALC over the whole block (has_calc: what
@@ -4186,7 +4307,8 @@ struct Plan {
                     * of d_scratch[k & 1], [1024 frames][n] words (kLoadRaw / kStoreRaw) */
                    std::vector<Group> pieces; DevArr<unsigned> d_scratch[2];
                    bool raw_out = false;         /* a piece but the last: it stores its last section's result word as it is (biquad_row<4> can) */
-                   bool wide = false; };         /* chains with a dressed finish: biquad_pipe's WIDE form (GroupLayout::wide) */
+                   bool wide = false;            /* chains with a dressed finish: biquad_pipe's WIDE form (GroupLayout::wide) */
+                   bool hand = false; };         /* chains with a delay line: biquad_pipe's HAND form (GroupLayout::hand) */
     /* the rows of ALL the plan's 16-lane groups in one table (CascadeLayout::all_rows) for ONE biquad_row launch instead of one per section
      * count: nsec 0 in its arguments (every wave takes its rows' count from their records), no ids.  n 0: not made */
     Group rows_all;
@@ -4199,6 +4321,11 @@ struct Plan {
     DevArr<FinishRec> d_finish;                          /* [record of d_chains]: the finishes (made when n_dressed) */
     bool has_calc = false; int calc_arg = 0, calc_word = 0;      /* the core begins with a DSP_TPDF_CALC: its width word, its result word in the mirror */
     int block_f0 = 0;                                    /* first frame, in the block call, of the launch being made (the addend table's index) */
+    /* delay lines ("chain_delay"): chain_tail behind the cascades */
+    int n_tail = 0; DevArr<DelayRec> d_tail;             /* chains with a DSP_DELAY */
+    DevArr<unsigned long long> d_hand;                   /* [those with sections][kFirChunk]: the accumulators their cascades hand over */
+    DevArr<int> d_hand_row;                              /* [record of d_chains]: the chain's row there (-1: none) */
+    unsigned delay_factor = 0;
     /* FIR history rings: [nchains][ring_R] floats, frame 0 of the next block goes to index wpos */
     DevArr<float> d_ring; int ring_R = 0, wpos = 0;
     DevArr<double> d_ring64;                             /* fir_stream: the ring as window operands (Ring::wide) */
@@ -4554,6 +4681,24 @@ int launch_biquad(avdsp_hip_prog *prog, Plan &pl, const Plan::Group &g, const in
     a.buf = prog->d_buf; a.chains = pl.d_chains; a.sec_coef = pl.d_sec_coef; a.sec_state = pl.d_sec_state;
     a.group = ids; a.ngroup = n; a.nsec = g.nsec; a.ring = plan_ring(pl); a.io = io;
     a.ready = with_ready ? pl.d_ready.get() : nullptr; a.seq = pl.seq;
+    if (g.hand) {
+        /* chains with a delay line: the forms that hand the last section's whole accumulator to chain_tail (16-lane rows: GroupLayout) */
+        if (!pl.d_hand || !pl.d_hand_row || g.P != 16) return set_err("a launch of delayed chains without its hand-over block");
+        BiquadArgsHand w{};
+        static_cast<BiquadArgs &>(w) = a;
+        w.hand = pl.d_hand; w.hand_row = pl.d_hand_row;
+        if (biquad_impl == 0) {
+            scope.begin();
+            hipLaunchKernelGGL(biquad_simple_hand<FMT>, dim3((n + 63) / 64), dim3(64), 0, stream, w);
+            if (stop) HIP_TRY(hipEventRecord(stop, stream));
+        } else {
+            const int nblk = (n + 15) / 16;
+            w.per_xcd = (nblk + 7) / 8;
+            if (launch_timed(scope, (const void *)biquad_pipe<FMT, 16, true, true>, dim3(w.per_xcd * 8), dim3(kBlock), 0, stream, w, stop)) return -1;
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (g.wide) {
         /* chains with a dressed finish: the forms that keep the last section's whole accumulator (16-lane rows: GroupLayout) */
         if (!prog->d_addend || !pl.d_finish || g.P != 16) return set_err("a launch of dressed chains without its addend table");
@@ -5166,6 +5311,16 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         hipLaunchKernelGGL((passthrough<FMT, true>), dim3(grid), dim3(kBlock), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
+    if (pl.n_tail) {
+        /* chains with a delay line: behind their cascades (which have joined `stream`), a workgroup per chain, a thread per frame */
+        if (!prog->d_addend || !pl.d_tail) return set_err("a launch of delayed chains without its tables");
+        ProfileScope scope(prog, stream, AVDSP_KERNEL_PASS); scope.begin();
+        TailArgs a{};
+        a.buf = prog->d_buf; a.chains = pl.d_chains; a.recs = pl.d_tail; a.hand = pl.d_hand; a.addend = prog->d_addend + pl.block_f0;
+        a.delay_factor = pl.delay_factor; a.io = io;
+        hipLaunchKernelGGL(chain_tail<FMT>, dim3((unsigned)pl.n_tail), dim3((unsigned)((io.nframes + 63) / 64 * 64)), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
@@ -5450,7 +5605,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
 /* device copies of a launch group's tables */
 static int upload_group(Plan::Group &g, const GroupLayout &l)
 {
-    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out; g.wide = l.wide;
+    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out; g.wide = l.wide; g.hand = l.hand;
     return g.d_ids.upload(l.ids) || g.d_rows.upload(l.rows) || g.d_lanes.upload(l.lanes);
 }
 
@@ -5509,6 +5664,24 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         std::vector<FinishRec> fin(L.dev_chains.size());
         for (size_t i = 0; i < fin.size(); i++) fin[i] = FinishRec{L.dev_chains[i].finish, L.dev_chains[i].finish_gain_bits};
         if (pl.d_finish.upload(fin)) return -1;
+    }
+    if (!t.tail.empty()) {
+        /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece) */
+        std::vector<int> hand_row(L.dev_chains.size(), -1);
+        std::vector<DelayRec> tail;
+        int rows = 0;
+        for (int i : t.tail) {
+            const avdsp_chain &c = t.chains[i];
+            const int row = c.nsec ? rows++ : -1;
+            hand_row[i] = row;
+            tail.push_back(DelayRec{i, c.delay_slot, c.delay_word, c.delay_us_word, c.delay_max, row, c.sat, c.finish, c.finish_gain_bits});
+        }
+        if (pl.d_tail.upload(tail)) return -1;
+        pl.n_tail = (int)tail.size(); pl.delay_factor = d->delay_line_factor;
+        if (rows) {
+            if (pl.d_hand_row.upload(hand_row)) return -1;
+            if (pl.d_hand.alloc((size_t)rows * kFirChunk) != hipSuccess) return set_err("hipMalloc(hand-over block of %d delayed chains)", rows);
+        }
     }
     if (!L.all_rows.empty()) {
         pl.rows_all.P = 16; pl.rows_all.n = (int)L.all_rows.size(); pl.rows_all.all_fir = L.rows_all_fir;
@@ -6144,8 +6317,8 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (pl.n_dressed || pl.has_calc) {
-        /* dressed finishes: one wave walks the core's TPDF_CALC over the whole block call and leaves every frame's addend, ahead of
+    if (pl.n_dressed || pl.has_calc || pl.n_tail) {
+        /* dressed finishes (and chain_tail, whose finish may be one): one wave walks the core's TPDF_CALC over the whole block call and leaves every frame's addend, ahead of
          * the launches below (which index the table by the frame's number in the call) */
         if (!prog->d_tpdf) return set_err("the dither generator has not been seeded");
         if (prog->addend_frames < nframes) {

@@ -7,8 +7,8 @@
  * avdsp_hip_prog_add_plan runs the stages in this order; each returns its tables, or an error text for set_err:
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads
- *     check_chains     section ranges, IOs, FIR words, dressed finishes, the IO spans, max_taps, the `fir` and `pass` lists
- *     cascade_groups   launch groups by section count (dressed chains apart), pieces of long cascades, biquad_row's records, the merged row table
+ *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `pass` and `tail` lists
+ *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
  */
 #ifndef AVDSP_PLAN_LAYOUT_H_
@@ -91,6 +91,7 @@ struct ChainTables {
     std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
     std::vector<int> pass_dressed;       /* ... of the latter, those with a dressed finish (they are not in `pass`) */
     int n_dressed = 0;                   /* chains with a dressed finish */
+    std::vector<int> tail;               /* chains with a DSP_DELAY ("chain_delay"): chain_tail finishes and stores them (they are in neither pass list) */
 };
 
 inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
@@ -178,6 +179,19 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
                 return text("chain %d: a dressed finish has no kernel here", i);
             t.n_dressed++;
         }
+        if (c.delay_slot) {
+            /* one DSP_DELAY (avdsp_chain::delay_slot): chain_tail of formats 2, 4 and 6, no FIR, no LOAD_MUX plan, no instances; the line
+             * -- its index word and the samples of the longest delay it can be asked for -- and the parameter word inside the buffer */
+            if ((c.delay_slot != AVDSP_DELAY_A && c.delay_slot != AVDSP_DELAY_B) || (c.delay_slot == AVDSP_DELAY_B && c.sat != 1))
+                return text("chain %d: delay slot %d", i, c.delay_slot);
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || c.fir_taps || t.has_mux || d->instances > 1)
+                return text("chain %d: a delay line has no kernel here", i);
+            const long long nline = c.delay_us_word ? (long long)c.delay_max : (long long)(((unsigned long long)(unsigned)c.delay_max * d->delay_line_factor) >> 32);
+            if (c.delay_max < 0 || c.delay_word < 0 || (long long)c.delay_word + 1 + nline > buf_words || c.delay_us_word < 0 || c.delay_us_word >= buf_words)
+                return text("chain %d: delay line outside the loaded buffer", i);
+            t.tail.push_back(i);
+            continue;
+        }
         if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
     }
     if (d->tpdf_calc) {
@@ -193,7 +207,9 @@ struct GroupLayout {
     int P = 0, nsec = 0, n = 0;          /* lanes per chain, sections, chains */
     bool all_fir = false;                /* every chain of the group feeds a FIR (its cascade writes the ring) */
     bool raw_out = false;                /* a piece but the last: it stores its last section's result word as it is */
-    bool wide = false;                   /* its chains have a dressed finish: the launch keeps the last section's whole accumulator per frame
+    bool hand = false;                   /* (with wide) its chains have a delay line: the launch hands every frame's accumulator to chain_tail
+                                            instead of finishing it (biquad_pipe's HAND form) */
+    bool wide = false;                   /* its chains have a dressed finish or a delay line: the launch keeps the last section's whole accumulator per frame
                                             (biquad_pipe's WIDE form; no biquad_row records).  Of a long cascade only the last piece is */
     std::vector<int> ids;                /* the chains' records in `dev_chains` */
     std::vector<RowRec> rows; std::vector<LaneRec> lanes;      /* biquad_row's records (P == 16), sections right-aligned in the row */
@@ -235,9 +251,10 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
     for (int i = 0; i < (int)t.chains.size(); i++) {
         const int nsec = t.chains[i].nsec;
         if (!nsec) continue;
-        const bool wide = t.chains[i].finish != 0;       /* dressed chains: launch groups of their own, next to the others */
-        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide; });
-        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; }
+        /* dressed chains: launch groups of their own, next to the others; delayed chains (dressed or not): again groups of their own */
+        const bool hand = t.chains[i].delay_slot != 0, wide = hand || t.chains[i].finish != 0;
+        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand; });
+        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; }
         it->ids.push_back(i);
     }
     for (GroupLayout &g : L.groups) {
@@ -261,7 +278,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
                 GroupLayout pg;
                 pg.nsec = base + (k < extra ? 1 : 0); pg.P = 16; pg.n = g.n;
                 pg.all_fir = k + 1 == np && g.all_fir; pg.raw_out = k + 1 < np;
-                pg.wide = k + 1 == np && g.wide;
+                pg.wide = k + 1 == np && g.wide; pg.hand = k + 1 == np && g.hand;
                 pg.ids.resize(g.n);
                 for (int j = 0; j < g.n; j++) {
                     const avdsp_chain &c = t.chains[g.ids[j]];
@@ -269,7 +286,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
                     pc.sec_base = c.sec_base + at; pc.nsec = pg.nsec;
                     if (k > 0) { pc.in_io = j; pc.load_mode = kLoadRaw; }
                     if (k + 1 < np) {
-                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j; pc.finish = 0;
+                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j; pc.finish = 0; pc.delay_slot = 0;
                         pg.ids[j] = (int)L.dev_chains.size(); L.dev_chains.push_back(pc);
                     } else { pg.ids[j] = g.ids[j]; L.dev_chains[g.ids[j]] = pc; }
                 }

@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -128,6 +128,8 @@ def lib() -> C.CDLL:
         L.dspRuntimeMuxInfo.argtypes = [i32, vp] + [C.POINTER(i32)] * 4
         L.dspRuntimeFinishInfo.restype = i32
         L.dspRuntimeFinishInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
+        L.dspRuntimeDelayInfo.restype = i32
+        L.dspRuntimeDelayInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -247,6 +249,13 @@ class Runtime:
         on the chain kernels, 1 if the core begins with a TPDF_CALC that dither_block runs), at the current shard."""
         a, b = C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeFinishInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
+
+    def delay_info(self, core_index: int = 0):
+        """dspRuntimeDelayInfo (host-only): (chains with a DSP_DELAY that "chain_delay" puts on the chain kernels, the longest of their
+        lines in samples at the current rate), at the current shard."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeDelayInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
         return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):

@@ -11,7 +11,8 @@
  *      464-475, 610-633)
  *
  * and, where the host has been asked to ("chain_finish"), chains without FIR and LOAD_MUX whose SAT0DB is one of
- * SAT0DB_TPDF / SAT0DB_GAIN / SAT0DB_TPDF_GAIN (:478-534), behind an optional DSP_TPDF_CALC at the head of the core (:537-545)
+ * SAT0DB_TPDF / SAT0DB_GAIN / SAT0DB_TPDF_GAIN (:478-534), behind an optional DSP_TPDF_CALC at the head of the core (:537-545),
+ * and ("chain_delay") chains without FIR and LOAD_MUX with one DSP_DELAY (:769-794) on either side of the SAT0DB slot
  *
  * for every chain of the core over a block of frame-interleaved samples.
  */
@@ -52,7 +53,13 @@ typedef struct avdsp_chain {
     /* a dressed finish in the SAT0DB slot (dsp_runtime.c:478-534; `sat` is 1 then): the gain, the frame's dither addend, SAT0DB */
     int32_t  finish;                 /* AVDSP_FINISH_*; 0: none                                  */
     uint32_t finish_gain_bits;       /* Q4.28 int or float bits of the SAT0DB[_TPDF]_GAIN parameter */
+    /* one DSP_DELAY (dsp_runtime.c:769-794) behind the banks ("chain_delay"): in front of the SAT0DB slot or behind it */
+    int32_t  delay_slot;             /* AVDSP_DELAY_*; 0: none                                   */
+    int32_t  delay_word;             /* the line in the mirror: its index word, the samples from the next word on */
+    int32_t  delay_us_word;          /* program word of the 16-bit microsecond parameter, read at every launch; 0: the fixed form */
+    int32_t  delay_max;              /* with a parameter: the line's size in samples (the delay is clamped to it); fixed form: microseconds */
 } avdsp_chain;
+enum { AVDSP_DELAY_NONE = 0, AVDSP_DELAY_A = 1, AVDSP_DELAY_B = 2 };      /* A: in front of the SAT0DB slot, B: behind it */
 enum { AVDSP_FINISH_NONE = 0, AVDSP_FINISH_TPDF = 1, AVDSP_FINISH_GAIN = 2, AVDSP_FINISH_TPDF_GAIN = 3 };      /* bit 0: dither, bit 1: gain */
 
 /* words between two copies of the mirror (chain instances, avdsp_hip_chain_instances): even, so that state words keep their alignment */
@@ -82,6 +89,7 @@ typedef struct avdsp_plan_desc {
     int32_t  tpdf_calc;              /* 1: it does                                                                            */
     int32_t  tpdf_calc_arg;          /* its dither width word (0 = the default)                                               */
     int32_t  tpdf_calc_result_word;  /* the 8-byte word of the mirror its result goes to                                      */
+    uint32_t delay_line_factor;      /* 2^32 / 10^6 x fs of the current rate (chains with a delay_slot: samples = us x factor >> 32) */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

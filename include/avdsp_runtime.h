@@ -87,7 +87,8 @@ int       dspQM32(double x, int m);         /* dsp_header.c:83-85 */
  * LOAD|LOAD_GAIN -> BIQUADS* -> [FIR] -> [SAT0DB] -> STORE+ chains runs on parallel kernels in every
  * format (in 2, 4 and 6 a chain may also begin with LOAD_MUX, see dspRuntimeMuxInfo; and, with dspRuntimeSetOption("chain_finish", 1),
  * a chain without FIR and LOAD_MUX may end in SAT0DB_TPDF, SAT0DB_GAIN or SAT0DB_TPDF_GAIN instead of SAT0DB, and the core may begin
- * with one DSP_TPDF_CALC of the default width, see dspRuntimeFinishInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
+ * with one DSP_TPDF_CALC of the default width, see dspRuntimeFinishInfo; and, with dspRuntimeSetOption("chain_delay", 1), such a chain
+ * may hold one DSP_DELAY behind its banks, see dspRuntimeDelayInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
  * the MFMA FIR (fir_tile); 3 and 5 -- float accumulators and the truncating dspMulFloatFloat -- on
  * chain_rows (a lane per chain and section) and fir_lane (a lane per chain and frame), with
  * chain_lane for single frames and cascades longer than 16 sections.  Any other core -- X/Y
@@ -304,6 +305,23 @@ int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, 
  * dspRuntimeFinishInfo is host-only, nothing runs on the GPU: the chains with a dressed finish among the chains of the core this process
  * runs (dspRuntimeSetShard) and whether the core begins with a lowered TPDF_CALC.  A core the interpreter runs reports zeros. */
 int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *tpdf_calc);
+
+/* Delay lines (opt-in: dspRuntimeSetOption("chain_delay", 1); default 0, every core with a delay opcode then runs on the interpreter
+ * as before and is refused by the chain lowering with the text it always had).  In formats 2, 4 and 6 a chain without DSP_FIR and
+ * LOAD_MUX may hold ONE DSP_DELAY (dsp_runtime.c:769-794) behind its banks: in front of the SAT0DB slot (which may be empty) or between
+ * that slot and the first STORE.  Both forms: dsp_DELAY_FixedMicroSec, and the parameter form whose microsecond word is read from the
+ * device copy of the program at every launch and clamped to the line's size -- an edit of that word takes effect at the next block
+ * without a new plan.  A chain may consist of LOAD, DELAY, STORE alone.  A delayed chain may carry a plain SAT0DB or none whatever
+ * "chain_finish" says, a dressed finish only while "chain_finish" is 1 too.  The cascades hand every frame's whole accumulator to
+ * chain_tail, one workgroup per chain, which runs delay, finish and STOREs in the chain's order; the line and its index word stay in
+ * the state area where the reference keeps them, so dspRuntimeSyncState / UploadState / Reset need nothing new.  Not lowered, i.e. on
+ * the interpreter as before (-8, a text of its own each): DSP_DELAY_DP and DSP_DELAY_1, a DSP_DELAY in front of the banks or behind a
+ * STORE, two delays in one chain, a delayed chain with a DSP_FIR or a LOAD_MUX head or beside LOAD_MUX chains, formats 3 and 5, and any
+ * program while dspRuntimeSetInstances(n > 1) is in force.
+ * dspRuntimeDelayInfo is host-only, nothing runs on the GPU: the chains with a lowered delay among the chains of the core this process
+ * runs (dspRuntimeSetShard), and the longest of their lines in samples at the current rate (parameter forms: what their word asks for
+ * now, clamped).  A core the interpreter runs reports zeros. */
+int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *longest_line);
 
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
