@@ -116,6 +116,7 @@ typedef struct avdsp_ctx {
     int             opt_fir_shared;                        /* "fir_shared" (AVDSP_OPT_FIR_SHARED), default 1 */
     int             opt_chain_finish;                      /* "chain_finish": dressed SAT0DB finishes and a head TPDF_CALC lowered to the chain kernels (default 0) */
     int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
+    int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
@@ -315,6 +316,11 @@ static int set_option_here(const char *key, int value)
         G.opt_chain_delay = value;
         return replan();
     }
+    if (!strcmp(key, "fir_tail")) {                      /* delay and dressed finish behind a DSP_FIR; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "fir_tail: 0 or 1");
+        G.opt_fir_tail = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -408,6 +414,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
     if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
     if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
+    if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -547,7 +554,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -795,6 +802,8 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
      * of its own on the interpreter) */
     const int finish_on = G.opt_chain_finish && G.ninst <= 1 && (format == 2 || format == 4 || format == 6);
     const unsigned delay_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* dsp_runtime.c:81-90 */
+    /* "fir_tail": the delay and the dressed finish may stand behind a DSP_FIR (formats 4 and 6: the chain FIR's) */
+    const int fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
 
     if (ensure_encoding(format)) return g_err_code;
 
@@ -883,7 +892,9 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             cur.nsec = L->nsec - cur.sec_base;
             break; }
         case DSP_FIR: {                                       /* :928-969 */
-            if (open && cur.delay_slot) return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
+            if (open && cur.delay_slot)
+                return fir_tail ? fail(-8, "word %d: a DSP_DELAY in front of the chain's DSP_FIR is not lowered to the HIP path", at)
+                                : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
             if (!open || cur.n_out || cur.sat)
                 return fail(-8, "word %d: FIR outside the supported chain order", at);
             if (!float_alu)
@@ -923,7 +934,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (!open) return fail(-8, "word %d: a DSP_DELAY in front of the chain's LOAD is not lowered to the HIP path", at);
             if (cur.n_out) return fail(-8, "word %d: a DSP_DELAY behind a STORE is not lowered to the HIP path", at);
             if (cur.delay_slot) return fail(-8, "word %d: a second DSP_DELAY in one chain is not lowered to the HIP path", at);
-            if (fir_op || cur.load_mode == AVDSP_LOAD_MUX)
+            if ((fir_op && !fir_tail) || cur.load_mode == AVDSP_LOAD_MUX)
                 return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR or a LOAD_MUX head is not lowered to the HIP path", at);
             LC_NEED(3);
             if (a[0] < 0) return fail(-8, "word %d: delay line of negative size %d", at, a[0]);
@@ -941,7 +952,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
         case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:      /* :478-534, "chain_finish" */
             if (!finish_on) goto not_lowered;
             if (!open || cur.n_out || cur.sat || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
-            if (fir_op || cur.load_mode == AVDSP_LOAD_MUX)
+            if ((fir_op && !fir_tail) || cur.load_mode == AVDSP_LOAD_MUX)
                 return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
             if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
             cur.finish = op == DSP_SAT0DB_TPDF ? AVDSP_FINISH_TPDF : op == DSP_SAT0DB_GAIN ? AVDSP_FINISH_GAIN : AVDSP_FINISH_TPDF_GAIN;
@@ -1004,6 +1015,35 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
         for (int i = 1; i < k && !clash; i++) clash = iv[2 * i] < iv[2 * i - 2] + iv[2 * i - 1];
         free(iv);
         if (clash) return fail(-8, "two delay lines of the core share words of the state area");
+    }
+    if (L->ndelayed && fir_tail) {
+        /* ("fir_tail") nor may a line share words with the history of a FIR: chain_tail writes the one while a FIR's history is
+         * converted from and to the other.  Lines and histories sorted by their first word; a line must begin behind everything
+         * before it, a history behind every line before it */
+        int nfir = 0;
+        for (int i = 0; i < L->nchains; i++) nfir += L->chains[i].fir_taps != 0;
+        long long *iv = nfir ? (long long *)malloc((size_t)(L->ndelayed + nfir) * 3 * sizeof *iv) : 0;
+        if (nfir && !iv) return fail(-9, "out of memory");
+        int k = 0, clash = 0;
+        for (int i = 0; i < L->nchains && nfir; i++) {
+            const avdsp_chain *c = &L->chains[i];
+            if (c->delay_slot) {
+                iv[3 * k] = c->delay_word;
+                iv[3 * k + 1] = 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
+                iv[3 * k + 2] = 1; k++;
+            }
+            if (c->fir_taps) { iv[3 * k] = c->fir_state_word; iv[3 * k + 1] = c->fir_taps; iv[3 * k + 2] = 0; k++; }
+        }
+        if (nfir) qsort(iv, (size_t)k, 3 * sizeof *iv, cmp_ll);
+        long long end_line = -1, end_any = -1;
+        for (int i = 0; i < k && !clash; i++) {
+            clash = iv[3 * i] < (iv[3 * i + 2] ? end_any : end_line);
+            const long long e = iv[3 * i] + iv[3 * i + 1];
+            if (iv[3 * i + 2] && e > end_line) end_line = e;
+            if (e > end_any) end_any = e;
+        }
+        free(iv);
+        if (clash) return fail(-8, "a delay line and a FIR's history share words of the state area");
     }
     return check_independent(L);
 }
@@ -1503,7 +1543,8 @@ static int fir_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **m
     int32_t *len = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
     if (!idx || !st || !mem || !first || !len) { free(idx); free(st); free(mem); free(first); free(len); return -1; }
     int m = 0;
-    for (int i = 0; i < n; i++) if (ch[i].fir_taps > 0) idx[m++] = i;
+    /* (handed FIR chains -- "fir_tail": a delay or a dressed finish behind the FIR -- are in no group: fir_shared stores, it hands nothing over) */
+    for (int i = 0; i < n; i++) if (ch[i].fir_taps > 0 && !ch[i].finish && !ch[i].delay_slot) idx[m++] = i;
     g_fg_chains = ch;
     qsort(idx, (size_t)m, sizeof(int32_t), fir_group_cmp);
     int ng = 0;
@@ -1664,6 +1705,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.store_mask = G.store_mask;
         d.tpdf_calc = L.tpdf_calc; d.tpdf_calc_arg = L.tpdf_calc_arg; d.tpdf_calc_result_word = L.tpdf_calc_word;
         d.delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* (as lower_core_ex checked the lines' extents) */
+        d.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -1911,6 +1953,38 @@ int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *lo
     }
     if (chains_delayed) *chains_delayed = nd;
     if (longest_line) *longest_line = longest;
+    return 0;
+}
+
+/* Host-only: what "fir_tail" makes of the core -- the handed FIR chains (a DSP_FIR with taps at the current rate, and behind it a
+ * DSP_DELAY and / or a dressed finish) among the chains this process runs (dspRuntimeSetShard), and how many of them have the delay
+ * (DESIGN.md 4.2h).  No device is touched.  A core that is not a set of chains has neither. */
+int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *of_them_delayed)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nh = 0, nd = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0) {
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            for (int i = lo; i < hi; i++) {
+                const avdsp_chain *c = &L.chains[i];
+                if (!c->fir_taps || (!c->finish && !c->delay_slot)) continue;
+                nh++;
+                nd += c->delay_slot != 0;
+            }
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (handed_chains) *handed_chains = nh;
+    if (of_them_delayed) *of_them_delayed = nd;
     return 0;
 }
 
@@ -2733,7 +2807,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if ((G.opt_chain_finish || G.opt_chain_delay) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

@@ -1953,6 +1953,13 @@ struct FirTileArgs {
     unsigned long long *stamps;              /* diagnostic build (tools/fir_timeline.py): 32 s_memtime stamps per wave */
 #endif
 };
+/* the launch of a plan's handed FIR chains ("fir_tail", the HAND forms below): nothing is stored, every frame's accumulator goes to the
+ * chain's row of the plan's hand-over block, where chain_tail takes it up (as BiquadArgsHand) */
+struct FirTileArgsHand : FirTileArgs {
+    unsigned long long *hand;                /* [hand_row][kFirChunk frames] accumulators */
+    const int *hand_row;                     /* [chain record]: the chain's row */
+};
+template <bool HAND> using FirTileArgsH = std::conditional_t<HAND, FirTileArgsHand, FirTileArgs>;
 #ifdef AVDSP_FIR_STAMPS
 #define FIR_STAMP(i) do { if (lane == 0 && (i) <= 30) a.stamps[(size_t)(blockIdx.x * 4 + stamp_row) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define FIR_STAMP_CHUNK() do { if (stamp_i <= 21) FIR_STAMP(stamp_i); stamp_i++; } while (0)   /* three per chunk, the first seven chunks */
@@ -1986,10 +1993,14 @@ template <int R, bool BIG = false> __device__ __forceinline__ constexpr int win_
  * turn no longer fits under the partner's chunk once a cascade wave takes its share of the slots -- a 512-chain shard's FIR alone
  * 68.4 -> 66.7 us, its step 87.6 -> 96.6; 2048 chains 247.2 -> 244.6 us alone, the step 0.259 -> 0.269 ms -- so such launches keep
  * the long boundary (launch_fir chooses). */
-template <int FMT, int R, bool BIG = false, bool SPLIT = false, bool LEAN = true>
-__global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
+/* HAND ("fir_tail"): the chains of the launch have a delay line or a dressed finish behind the FIR.  Only the end
+ * differs: no word is formed and nothing is stored, the bits of every accumulator of a frame of the block go to the chain's row of
+ * the hand-over block, and chain_tail goes on from there under its own MODE.  No SPLIT form.  HAND false is the kernel as it was. */
+template <int FMT, int R, bool BIG = false, bool SPLIT = false, bool LEAN = true, bool HAND = false>
+__global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a)
 {
     static_assert(!SPLIT || (R == 1 && !BIG), "the tap split: one row tile, ordinary chunks");
+    static_assert(!HAND || !SPLIT, "handed launches keep the reference's summation order");
     using G = TileGeom<R, BIG>;
     constexpr int NR = G::NR;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2021,7 +2032,7 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
      * the very end); a wave without a unit only attends that barrier */
     [[maybe_unused]] int *xchg = reinterpret_cast<int *>(lds + (size_t)4 * G::LDS_DOUBLES);      /* [wave]: out_io of its chain, or -1 */
     if (slot >= a.ngroup || F0 >= B) {
-        if constexpr (R >= 2) {
+        if constexpr (R >= 2 && !HAND) {                 /* (HAND: no tile leaves with another, no barrier at the end) */
             if (lane == 0) xchg[wv] = -1;
             __syncthreads();
         }
@@ -2270,7 +2281,18 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgs a)
                 }
         }
     }
-    if constexpr (R >= 2) {
+    if constexpr (HAND) {
+        /* the accumulators as they are -- no store_stage, no flush: chain_tail converts.  A (row tile, register) pair is 16 runs of
+         * four consecutive frames, 32 bytes each, of the chain's row */
+        unsigned long long *row = a.hand + (size_t)a.hand_row[cid] * kFirChunk;
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const int n = F0 + NR * i16 + 16 * r + 4 * v + k;
+                if (n < B) row[n] = (unsigned long long)__double_as_longlong(acc[r][v]);
+            }
+    } else if constexpr (R >= 2) {
         /* The tiles leave as 16-byte (R = 4) or 8-byte (R = 2) pieces.  A wave's results are one CHANNEL: stored by itself it
          * writes 4 bytes into each of 256 R different 128-byte lines, and with every wave of the chip doing that the L2's request
          * rate is what the epilogue waits for (~13 000 cycles per wave at R = 4, tools/fir_timeline.py).  The workgroup holds R
@@ -3083,8 +3105,10 @@ __global__ __launch_bounds__(kBlock) void taps_to_f64(const Taps64Args a)
 
 /* cross-check path: one thread per output frame, the reference's loop verbatim (ascending taps),
  * operands straight from the ring and the program words (L1/L2)                                */
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void fir_plain(const FirArgs a)
+struct FirArgsHand : FirArgs { unsigned long long *hand; const int *hand_row; };      /* (as FirTileArgsHand) */
+/* HAND ("fir_tail"): handed FIR chains -- the accumulators to the hand-over block.  HAND false is the kernel as it was. */
+template <int FMT, bool HAND = false>
+__global__ __launch_bounds__(kBlock) void fir_plain(const std::conditional_t<HAND, FirArgsHand, FirArgs> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     const int slot = xcd_remap(blockIdx.x, a.per_xcd);
@@ -3100,7 +3124,8 @@ __global__ __launch_bounds__(kBlock) void fir_plain(const FirArgs a)
         double acc = 0.0;
         for (int t = 0; t < T; t++)
             acc = __builtin_fma(mulop(ringrow[(a.ring.wpos + n - t) & rmask]), mulop(taps[t]), acc);
-        emit_out(a.io, c, n, store_stage<FMT>(acc, c.sat, a.io.store_mask));
+        if constexpr (HAND) a.hand[(size_t)a.hand_row[cid] * kFirChunk + n] = (unsigned long long)__double_as_longlong(acc);
+        else emit_out(a.io, c, n, store_stage<FMT>(acc, c.sat, a.io.store_mask));
     }
 }
 
@@ -4326,6 +4351,9 @@ struct Plan {
     DevArr<unsigned long long> d_hand;                   /* [those with sections][kFirChunk]: the accumulators their cascades hand over */
     DevArr<int> d_hand_row;                              /* [record of d_chains]: the chain's row there (-1: none) */
     unsigned delay_factor = 0;
+    /* handed FIR chains ("fir_tail"): a HAND launch of their own behind the plain FIR launches, their rows in d_hand,
+     * their records in d_tail; d_fir_plain: the others (made when there are handed ones) */
+    DevArr<int> d_fir_hand, d_fir_plain; int n_fir_hand = 0;
     /* FIR history rings: [nchains][ring_R] floats, frame 0 of the next block goes to index wpos */
     DevArr<float> d_ring; int ring_R = 0, wpos = 0;
     DevArr<double> d_ring64;                             /* fir_stream: the ring as window operands (Ring::wide) */
@@ -4780,6 +4808,11 @@ void add_fir_tile(std::vector<FirVariant> &v)
     v.push_back({{kFirTile, R, BIG, SPLIT, true}, (const void *)fir_tile<FMT, R, BIG, SPLIT, true>, lds, TileGeom<R, BIG>::FW, TileGeom<R, BIG>::WPC});
     v.push_back({{kFirTile, R, BIG, SPLIT, false}, (const void *)fir_tile<FMT, R, BIG, SPLIT, false>, lds, TileGeom<R, BIG>::FW, TileGeom<R, BIG>::WPC});
 }
+template <int FMT, int R, bool BIG>
+void add_fir_hand(std::vector<FirVariant> &v)
+{
+    v.push_back({{kFirTile, R, BIG, false, true, true}, (const void *)fir_tile<FMT, R, BIG, false, true, true>, 4 * TileGeom<R, BIG>::LDS_DOUBLES * 8 + 64, TileGeom<R, BIG>::FW, TileGeom<R, BIG>::WPC});
+}
 template <int FMT, int R>
 void add_fir_rows(std::vector<FirVariant> &v)
 {
@@ -4801,6 +4834,9 @@ const std::vector<FirVariant> &fir_variants()
             v.push_back({{kFirMfma, 1, false, false, false}, (const void *)fir_mfma<FMT, 1>, -1, 0, 0});
             v.push_back({{kFirMfma, 2, false, false, false}, (const void *)fir_mfma<FMT, 2>, -1, 0, 0});
             v.push_back({{kFirPlain, 1, false, false, false}, (const void *)fir_plain<FMT>, 0, 0, 0});
+            /* the HAND forms ("fir_tail", fir_hand_choice): lean, unsplit */
+            add_fir_hand<FMT, 1, false>(v); add_fir_hand<FMT, 2, false>(v); add_fir_hand<FMT, 4, false>(v); add_fir_hand<FMT, 1, true>(v);
+            v.push_back({{kFirPlain, 1, false, false, false, true}, (const void *)fir_plain<FMT, true>, 0, 0, 0});
         }
         return v;
     }();
@@ -4810,7 +4846,7 @@ template <int FMT>
 const FirVariant *fir_variant(const FirChoice &c)
 {
     for (const FirVariant &v : fir_variants<FMT>()) if (v.c == c) return &v;
-    set_err("no FIR kernel of family %d with %d row tiles (%d %d %d) in format %d", c.family, c.R, c.BIG, c.SPLIT, c.LEAN, FMT);
+    set_err("no FIR kernel of family %d with %d row tiles (%d %d %d %d) in format %d", c.family, c.R, c.BIG, c.SPLIT, c.LEAN, c.HAND, FMT);
     return nullptr;
 }
 int fir_opt_in(int format, int gpc)
@@ -4907,15 +4943,18 @@ int launch_fir_shared(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t st
 }
 
 /* fir_impl: 0 = fir_plain (the reference's loop), 1 = fir_tile (default), 2 = fir_mfma (round 1's workgroup-per-channel kernel),
- * 3 = fir_stream, 4 = fir_flow; which variant of it: fir_choice (avdsp_plan_layout.h) */
+ * 3 = fir_stream, 4 = fir_flow; which variant of it: fir_choice (avdsp_plan_layout.h).
+ * hand: the launch of the plan's handed FIR chains ("fir_tail": fir_hand_choice, the HAND forms, the hand-over block in the arguments) */
 template <int FMT>
-int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, int fir_impl, hipStream_t stream, bool wait_ready = false, hipEvent_t stop = nullptr)
+int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, int fir_impl, hipStream_t stream, bool wait_ready = false, hipEvent_t stop = nullptr, bool hand = false)
 {
-    if constexpr (FMT == 2) { (void)prog; (void)pl; (void)ids; (void)n; (void)io; (void)fir_impl; (void)stream; (void)wait_ready; (void)stop; return 0; }
+    if constexpr (FMT == 2) { (void)prog; (void)pl; (void)ids; (void)n; (void)io; (void)fir_impl; (void)stream; (void)wait_ready; (void)stop; (void)hand; return 0; }
     else {
+        if (hand && (!pl.d_hand || !pl.d_hand_row)) return set_err("a launch of handed FIR chains without its hand-over block");
         if (ensure_private_taps(prog, pl, stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
-        const FirChoice c = fir_choice(fir_impl, n, io.nframes, FirOptions{prog->fir_rows, prog->fir_split, prog->fir_lean}, !pl.bq.empty(), (long long)pl.n_fir * pl.max_taps);
+        const FirChoice c = hand ? fir_hand_choice(fir_impl, n, io.nframes, prog->fir_rows, !pl.bq.empty(), (long long)pl.n_fir * pl.max_taps)
+                                 : fir_choice(fir_impl, n, io.nframes, FirOptions{prog->fir_rows, prog->fir_split, prog->fir_lean}, !pl.bq.empty(), (long long)pl.n_fir * pl.max_taps);
         const FirVariant *v = fir_variant<FMT>(c);
         if (!v) return -1;
         if (c.family != kFirTile && c.family != kFirFlow) scope.begin();
@@ -4942,6 +4981,12 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
             const int nwg = (n * wpc * (c.SPLIT ? 2 : 1) + 3) / 4;
             a.per_xcd = (nwg + 7) / 8;
             if (fir_stamp_buffer(a, stream)) return -1;
+            if (hand) {
+                FirTileArgsHand h{};
+                static_cast<FirTileArgs &>(h) = a;
+                h.hand = pl.d_hand; h.hand_row = pl.d_hand_row;
+                return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, h, stop);
+            }
             return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, a, stop);
         }
         if (c.family == kFirStream) {
@@ -4965,7 +5010,10 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
         a.gpc = pl.fir_gpc;
         size_t lds = 0;
         if (c.family == kFirMfma) lds = fir_lds_bytes(a.gpc, &a.hs_cap, &a.win_row);
-        void *kargs[] = {(void *)&a};
+        FirArgsHand h{};
+        static_cast<FirArgs &>(h) = a;
+        if (hand) { h.hand = pl.d_hand; h.hand_row = pl.d_hand_row; }
+        void *kargs[] = {hand ? (void *)&h : (void *)&a};
         HIP_TRY(hipLaunchKernel(v->fn, dim3(a.per_xcd * 8), dim3(64 * nwaves), kargs, lds, stream));
         return 0;
     }
@@ -5282,15 +5330,20 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         prog->blk++;
     } else {
         if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false)) return -1;
-        if (pl.n_fir && shared_path(prog, pl, fir_impl)) {
+        /* (a plan with handed FIR chains: the plain ones have a list of their own; else it is every FIR chain, as ever) */
+        const int n_plain = pl.n_fir - pl.n_fir_hand;
+        const int *plain_ids = pl.n_fir_hand ? pl.d_fir_plain.get() : pl.d_fir_ids.get();
+        if (n_plain && shared_path(prog, pl, fir_impl)) {
             /* chains of one bank on fir_shared, the others on fir_tile as ever: two launches on the stream */
             if (pl.n_fir_rest && launch_fir<FMT>(prog, pl, pl.d_fir_rest, pl.n_fir_rest, io, fir_impl, stream)) return -1;
             if (launch_fir_shared<FMT>(prog, pl, io, stream)) return -1;
             prog->sh_chains_now = pl.n_sh_chains; prog->sh_groups_now = pl.n_sh_groups;
         } else if (pl.n_fir) {
-            if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, stream)) return -1;
+            if (n_plain && launch_fir<FMT>(prog, pl, plain_ids, n_plain, io, fir_impl, stream)) return -1;
             prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;
         }
+        /* the handed FIR chains ("fir_tail"): their accumulators into the hand-over block, chain_tail below takes them up */
+        if (pl.n_fir_hand && launch_fir<FMT>(prog, pl, pl.d_fir_hand, pl.n_fir_hand, io, fir_impl, stream, false, nullptr, true)) return -1;
     }
     if (pl.n_pass) {
         ProfileScope scope(prog, stream, AVDSP_KERNEL_PASS); scope.begin();
@@ -5665,16 +5718,23 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         for (size_t i = 0; i < fin.size(); i++) fin[i] = FinishRec{L.dev_chains[i].finish, L.dev_chains[i].finish_gain_bits};
         if (pl.d_finish.upload(fin)) return -1;
     }
+    if (!t.fir_hand.empty()) {
+        pl.n_fir_hand = (int)t.fir_hand.size();
+        if (pl.d_fir_hand.upload(t.fir_hand) || pl.d_fir_plain.upload(t.fir_plain)) return -1;
+    }
     if (!t.tail.empty()) {
-        /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece) */
+        /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece; a handed FIR chain's row is
+         * filled by its FIR, and one without a delay gets the record of a line of 0 samples in front of its slot: chain_tail bypasses
+         * such a line -- nothing read, nothing written -- and runs the slot's opcode and the STOREs) */
         std::vector<int> hand_row(L.dev_chains.size(), -1);
         std::vector<DelayRec> tail;
         int rows = 0;
         for (int i : t.tail) {
             const avdsp_chain &c = t.chains[i];
-            const int row = c.nsec ? rows++ : -1;
+            const int row = (c.nsec || c.fir_taps) ? rows++ : -1;
             hand_row[i] = row;
-            tail.push_back(DelayRec{i, c.delay_slot, c.delay_word, c.delay_us_word, c.delay_max, row, c.sat, c.finish, c.finish_gain_bits});
+            if (c.delay_slot) tail.push_back(DelayRec{i, c.delay_slot, c.delay_word, c.delay_us_word, c.delay_max, row, c.sat, c.finish, c.finish_gain_bits});
+            else tail.push_back(DelayRec{i, AVDSP_DELAY_A, 0, 0, 0, row, c.sat, c.finish, c.finish_gain_bits});
         }
         if (pl.d_tail.upload(tail)) return -1;
         pl.n_tail = (int)tail.size(); pl.delay_factor = d->delay_line_factor;
@@ -5718,7 +5778,7 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
             if (!launched) return set_err("taps_to_f64 (groups) failed to launch");
         }
         /* ... and the per-chain rows, unless every FIR chain is grouped and the shared path is on (then ensure_private_taps, if ever) */
-        if (!(pl.n_sh_groups > 0 && pl.n_fir_rest == 0 && prog->fir_shared)) {
+        if (!(pl.n_sh_groups > 0 && pl.n_fir_rest == 0 && pl.n_fir_hand == 0 && prog->fir_shared)) {
             e = pl.d_taps64.alloc((size_t)d->nchains * pl.pitch64);
             if (e != hipSuccess) return set_err("hipMalloc(f64 taps, %d x %d): %s", d->nchains, pl.pitch64, hipGetErrorString(e));
             Taps64Args ta{prog->d_buf, pl.d_chains, pl.d_fir_ids, pl.d_taps64, pl.pitch64, 0};

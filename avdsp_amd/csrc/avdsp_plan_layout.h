@@ -7,7 +7,7 @@
  * avdsp_hip_prog_add_plan runs the stages in this order; each returns its tables, or an error text for set_err:
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads
- *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `pass` and `tail` lists
+ *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `fir_hand`, `pass` and `tail` lists
  *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
  */
@@ -91,7 +91,11 @@ struct ChainTables {
     std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
     std::vector<int> pass_dressed;       /* ... of the latter, those with a dressed finish (they are not in `pass`) */
     int n_dressed = 0;                   /* chains with a dressed finish */
-    std::vector<int> tail;               /* chains with a DSP_DELAY ("chain_delay"): chain_tail finishes and stores them (they are in neither pass list) */
+    std::vector<int> tail;               /* chains with a DSP_DELAY ("chain_delay") and the handed FIR chains: chain_tail finishes and stores them (they are in neither pass list) */
+    /* "fir_tail": the handed FIR chains -- a FIR, and a dressed finish and / or a delay behind it.  Their FIR launch (a HAND form) leaves
+     * the accumulators in the hand-over block for chain_tail.  `fir` holds every chain with a FIR, they among them (rings, taps, history);
+     * `fir_plain` those that store themselves */
+    std::vector<int> fir_hand, fir_plain;
 };
 
 inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
@@ -155,6 +159,7 @@ inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
 
 inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
 {
+    const bool fir_tail = d->fir_tail && (d->format == 4 || d->format == 6);
     for (int i = 0; i < d->nchains; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return text("chain %d: bad section range", i);
@@ -173,25 +178,26 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             t.max_taps = std::max(t.max_taps, c.fir_taps);
         }
         if (c.finish) {
-            /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front, no LOAD_MUX plan, no instances */
+            /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front (but under "fir_tail"), no LOAD_MUX plan, no instances */
             if (c.finish < AVDSP_FINISH_TPDF || c.finish > AVDSP_FINISH_TPDF_GAIN || c.sat != 1) return text("chain %d: finish %d", i, c.finish);
-            if ((d->format != 2 && d->format != 4 && d->format != 6) || c.fir_taps || t.has_mux || d->instances > 1)
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || t.has_mux || d->instances > 1)
                 return text("chain %d: a dressed finish has no kernel here", i);
             t.n_dressed++;
         }
         if (c.delay_slot) {
-            /* one DSP_DELAY (avdsp_chain::delay_slot): chain_tail of formats 2, 4 and 6, no FIR, no LOAD_MUX plan, no instances; the line
+            /* one DSP_DELAY (avdsp_chain::delay_slot): chain_tail of formats 2, 4 and 6, no FIR (but under "fir_tail"), no LOAD_MUX plan, no instances; the line
              * -- its index word and the samples of the longest delay it can be asked for -- and the parameter word inside the buffer */
             if ((c.delay_slot != AVDSP_DELAY_A && c.delay_slot != AVDSP_DELAY_B) || (c.delay_slot == AVDSP_DELAY_B && c.sat != 1))
                 return text("chain %d: delay slot %d", i, c.delay_slot);
-            if ((d->format != 2 && d->format != 4 && d->format != 6) || c.fir_taps || t.has_mux || d->instances > 1)
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || t.has_mux || d->instances > 1)
                 return text("chain %d: a delay line has no kernel here", i);
             const long long nline = c.delay_us_word ? (long long)c.delay_max : (long long)(((unsigned long long)(unsigned)c.delay_max * d->delay_line_factor) >> 32);
             if (c.delay_max < 0 || c.delay_word < 0 || (long long)c.delay_word + 1 + nline > buf_words || c.delay_us_word < 0 || c.delay_us_word >= buf_words)
                 return text("chain %d: delay line outside the loaded buffer", i);
-            t.tail.push_back(i);
-            continue;
         }
+        const bool handed = c.fir_taps && (c.finish || c.delay_slot);
+        if (handed) t.fir_hand.push_back(i); else if (c.fir_taps) t.fir_plain.push_back(i);
+        if (c.delay_slot || handed) { t.tail.push_back(i); continue; }
         if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
     }
     if (d->tpdf_calc) {
@@ -251,8 +257,10 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
     for (int i = 0; i < (int)t.chains.size(); i++) {
         const int nsec = t.chains[i].nsec;
         if (!nsec) continue;
-        /* dressed chains: launch groups of their own, next to the others; delayed chains (dressed or not): again groups of their own */
-        const bool hand = t.chains[i].delay_slot != 0, wide = hand || t.chains[i].finish != 0;
+        /* dressed chains: launch groups of their own, next to the others; delayed chains (dressed or not): again groups of their own.
+         * Not the cascade of a handed FIR chain ("fir_tail"): delay and finish stand behind its FIR, the cascade feeds the ring like any */
+        const bool fir = t.chains[i].fir_taps != 0;
+        const bool hand = !fir && t.chains[i].delay_slot != 0, wide = hand || (!fir && t.chains[i].finish != 0);
         auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand; });
         if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; }
         it->ids.push_back(i);
@@ -334,7 +342,7 @@ inline SharedLayout shared_fir_layout(const avdsp_plan_desc *d, const ChainTable
         const int c0 = d->fir_group_chains[b];
         for (int j = b; j < e; j++) {
             const int ci = d->fir_group_chains[j];
-            if (ci < 0 || ci >= d->nchains || in_group[ci] || !t.chains[ci].fir_taps || t.chains[ci].fir_taps != t.chains[c0].fir_taps ||
+            if (ci < 0 || ci >= d->nchains || in_group[ci] || !t.chains[ci].fir_taps || t.chains[ci].finish || t.chains[ci].delay_slot || t.chains[ci].fir_taps != t.chains[c0].fir_taps ||
                 t.chains[ci].fir_coef_word != t.chains[c0].fir_coef_word) { S.err = text("FIR group %d: chain %d is not one of its bank", g, ci); return S; }
             in_group[ci] = 1;
             if (!t.chains[ci].nsec) S.feed.push_back(ci);
@@ -345,7 +353,7 @@ inline SharedLayout shared_fir_layout(const avdsp_plan_desc *d, const ChainTable
             S.tiles.push_back(SharedTile{gi, (int)S.ids.size() + (j - b), std::min(16, e - j), t.chains[c0].fir_taps});
         S.ids.insert(S.ids.end(), d->fir_group_chains + b, d->fir_group_chains + e);
     }
-    for (int ci : t.fir) if (!in_group[ci]) S.rest.push_back(ci);
+    for (int ci : t.fir_plain) if (!in_group[ci]) S.rest.push_back(ci);
     return S;
 }
 
@@ -408,6 +416,7 @@ inline bool stores_whole_window(const ChainTables &t)
 inline bool overlap_ok(const ChainTables &t)
 {
     bool any = false;
+    if (!t.fir_hand.empty()) return false;               /* (a handed FIR chain: its tail follows its FIR on the caller's stream, the plan runs back to back) */
     for (const avdsp_chain &c : t.chains) { if (c.nsec && !c.fir_taps) return false; any = any || c.nsec; }
     return any && !t.fir.empty() && !t.has_mux;
 }
@@ -415,8 +424,9 @@ inline bool overlap_ok(const ChainTables &t)
 /* ---- which FIR kernel a launch takes ---- */
 /* fir_impl's values, and fir_shared, which launch_all takes for the grouped chains of a plan (shared_path) */
 enum FirFamily { kFirPlain = 0, kFirTile = 1, kFirMfma = 2, kFirStream = 3, kFirFlow = 4, kFirShared = 5 };
-struct FirChoice { int family, R; bool BIG, SPLIT, LEAN; };       /* R: row tiles per wave (fir_mfma: its NG); the flags are fir_tile's / fir_flow's, else false */
-inline bool operator==(const FirChoice &a, const FirChoice &b) { return a.family == b.family && a.R == b.R && a.BIG == b.BIG && a.SPLIT == b.SPLIT && a.LEAN == b.LEAN; }
+struct FirChoice { int family, R; bool BIG, SPLIT, LEAN; bool HAND = false; };       /* R: row tiles per wave (fir_mfma: its NG); the flags are fir_tile's / fir_flow's, else false;
+                                                                                         HAND: the launch of a plan's handed FIR chains (fir_hand_choice) */
+inline bool operator==(const FirChoice &a, const FirChoice &b) { return a.family == b.family && a.R == b.R && a.BIG == b.BIG && a.SPLIT == b.SPLIT && a.LEAN == b.LEAN && a.HAND == b.HAND; }
 struct FirOptions { int fir_rows, fir_split, fir_lean; };         /* the options of those names: 0 = by the rules below, 0 = off, -1 = by the plan */
 
 /* Row tiles per wave by cost.  The chip holds 2048 of these waves at a time, a wave of R row tiles lasts R units, and a launch is over
@@ -481,6 +491,15 @@ inline FirChoice fir_choice(int impl, long long n, int frames, const FirOptions 
     default:              /* fir_mfma.  Few workgroups per CU: the deeper operand sets */
         return FirChoice{kFirMfma, n <= 2 * 256 ? 2 : 1, false, false, false};
     }
+}
+
+/* the launch of a plan's handed FIR chains ("fir_tail"): fir_plain with fir_impl 0, else fir_tile -- never split (the hand-over keeps the
+ * reference's summation order), always the lean boundary (no cascade runs beside it: such a plan has no overlap) */
+inline FirChoice fir_hand_choice(int impl, long long n, int frames, int fir_rows, bool cascades, long long plan_taps)
+{
+    FirChoice c = fir_choice(impl == kFirPlain ? kFirPlain : kFirTile, n, frames, FirOptions{fir_rows, 0, 1}, cascades, plan_taps);
+    c.HAND = true;
+    return c;
 }
 
 }  // namespace avdsp_layout

@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -130,6 +130,8 @@ def lib() -> C.CDLL:
         L.dspRuntimeFinishInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeDelayInfo.restype = i32
         L.dspRuntimeDelayInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
+        L.dspRuntimeFirTailInfo.restype = i32
+        L.dspRuntimeFirTailInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -256,6 +258,13 @@ class Runtime:
         lines in samples at the current rate), at the current shard."""
         a, b = C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeDelayInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
+
+    def fir_tail_info(self, core_index: int = 0):
+        """dspRuntimeFirTailInfo (host-only): (handed FIR chains -- a delay and / or a dressed finish behind the FIR, which "fir_tail"
+        puts on the chain kernels --, those of them with a delay), at the current shard."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeFirTailInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
         return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):

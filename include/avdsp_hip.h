@@ -13,6 +13,7 @@
  * and, where the host has been asked to ("chain_finish"), chains without FIR and LOAD_MUX whose SAT0DB is one of
  * SAT0DB_TPDF / SAT0DB_GAIN / SAT0DB_TPDF_GAIN (:478-534), behind an optional DSP_TPDF_CALC at the head of the core (:537-545),
  * and ("chain_delay") chains without FIR and LOAD_MUX with one DSP_DELAY (:769-794) on either side of the SAT0DB slot
+ * and ("fir_tail", formats 4 and 6) both of them behind a chain's DSP_FIR
  *
  * for every chain of the core over a block of frame-interleaved samples.
  */
@@ -90,6 +91,8 @@ typedef struct avdsp_plan_desc {
     int32_t  tpdf_calc_arg;          /* its dither width word (0 = the default)                                               */
     int32_t  tpdf_calc_result_word;  /* the 8-byte word of the mirror its result goes to                                      */
     uint32_t delay_line_factor;      /* 2^32 / 10^6 x fs of the current rate (chains with a delay_slot: samples = us x factor >> 32) */
+    int32_t  fir_tail;               /* 1 ("fir_tail", formats 4 and 6): a chain with fir_taps may have a finish and / or a delay_slot -- a handed FIR chain,
+                                        whose FIR hands its accumulators to chain_tail; 0: such a chain is refused                */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

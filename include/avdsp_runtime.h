@@ -323,6 +323,21 @@ int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *t
  * now, clamped).  A core the interpreter runs reports zeros. */
 int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *longest_line);
 
+/* Dressed finishes and delay lines behind a FIR (opt-in: dspRuntimeSetOption("fir_tail", 1); default 0, every core then takes the path
+ * and is refused with the text it always had).  In formats 4 and 6 a chain with one DSP_FIR behind its optional banks may go on as
+ * FIR -> [DELAY] -> [SAT0DB | SAT0DB_TPDF | SAT0DB_GAIN | SAT0DB_TPDF_GAIN] -> [DELAY] -> STORE(s): a "handed FIR chain", whose FIR
+ * kernel (fir_tile's or fir_plain's HAND form) hands every frame's 64-bit accumulator to chain_tail instead of storing it.  The
+ * dressed finish and a head TPDF_CALC still need "chain_finish" 1, the DELAY "chain_delay" 1, and all their rules hold (one delay, both
+ * forms, a constant dither width, disjoint lines -- also disjoint from every FIR history --, no instances, no LOAD_MUX in the core).  A
+ * bypassed DSP_FIR (offset 0 at the current rate, or length 0) no longer refuses such a chain: it is then an ordinary dressed / delayed
+ * cascade chain.  Plain FIR chains of the same core stay what they are.  Limits: handed chains are in no fir_shared group (see
+ * dspRuntimeFirGroupInfo), a plan that holds one runs back to back whatever "overlap" says, "fir_split" does not apply to their launch.
+ * Not lowered (-8, a text each): the FIR pure-delay variant, formats 3 and 5 (and 2, which has no FIR), LOAD_MUX heads, DSP_DELAY_DP /
+ * DSP_DELAY_1, a DSP_DELAY in front of the FIR, two FIRs in a chain.
+ * dspRuntimeFirTailInfo is host-only, nothing runs on the GPU: the handed FIR chains among the chains of the core this process runs
+ * (dspRuntimeSetShard) and how many of them have a delay.  A core the interpreter runs reports zeros. */
+int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *of_them_delayed);
+
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
 /* Several programs in one process.  dspRuntimeInit(codePtr, ...) loads a program into a context of its own, keyed by the
