@@ -97,7 +97,7 @@ typedef struct avdsp_ctx {
     int             shard_rank, shard_world;               /* dspRuntimeSetShard: this process's slice of every chain core */
     int             numfreq_at_init;                       /* dspChangeFormat's view of the rate count (see dspRuntimeInit) */
     int             opt_profile_stride;
-    int             opt_overlap, opt_fir_rows, opt_host_split, opt_host_pin, opt_ready_words, opt_lane_hw, opt_fir_split, opt_fir_launch, opt_fir_launch_set, opt_fir_lean, opt_fir_lean_set, opt_ring_wait; /* launch arrangement of the chain kernels (avdsp_hip_prog_set_option) */
+    int             opt_overlap, opt_fir_rows, opt_host_split, opt_host_pin, opt_ready_words, opt_lane_hw, opt_fir_split, opt_fir_launch, opt_fir_launch_set, opt_fir_lean, opt_fir_lean_set, opt_ring_wait, opt_fir_ahead; /* launch arrangement of the chain kernels (avdsp_hip_prog_set_option) */
     arrangement     arr[MAX_ARRANGEMENTS]; int arr_next;   /* how the cores / pieces go to the device: [0] whole program, [1..] single cores */
     int             biquad_freq_skip, mantissa;            /* this program's dspBiquadFreqSkip / dspMantissa */
     int             device_ordinal;                        /* the GPU its device copy lives on (-1: none yet) */
@@ -120,7 +120,7 @@ typedef struct avdsp_ctx {
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
-static avdsp_ctx g_template = { .opt_lane_hw = 1, .opt_ring_wait = 1, .opt_ready_words = -1, .opt_fir_impl = 1, .opt_biquad_impl = 1, .opt_device = -1, .opt_interp_impl = 1, .opt_strand_split = 1, .opt_strand_lanes = 1, .shard_world = 1,
+static avdsp_ctx g_template = { .opt_lane_hw = 1, .opt_ring_wait = 1, .opt_ready_words = -1, .opt_fir_ahead = -1, .opt_fir_impl = 1, .opt_biquad_impl = 1, .opt_device = -1, .opt_interp_impl = 1, .opt_strand_split = 1, .opt_strand_lanes = 1, .shard_world = 1,
                                 .mantissa = DSP_MANT, .device_ordinal = -1, .opt_frame_server_idle_us = 1000, .opt_fir_shared = 1 };
 
 /* A host written for the reference cannot call dspRuntimeSetOption: AVDSP_FRAME_SERVER=1 in the environment makes "frame_server" 1 the
@@ -129,6 +129,9 @@ __attribute__((constructor)) static void frame_server_from_environment(void)
 {
     const char *e = getenv("AVDSP_FRAME_SERVER");
     if (e && !strcmp(e, "1")) g_template.opt_frame_server = 1;
+    /* ... and AVDSP_FIR_AHEAD=-1|0|1 the default of "fir_ahead" (include/avdsp_runtime.h); dspRuntimeGetOption("fir_ahead") then reads that value */
+    e = getenv("AVDSP_FIR_AHEAD");
+    if (e && (!strcmp(e, "-1") || !strcmp(e, "0") || !strcmp(e, "1"))) g_template.opt_fir_ahead = atoi(e);
 }
 #define MAX_PROGRAMS 64
 static avdsp_ctx *g_ctx[MAX_PROGRAMS];
@@ -326,6 +329,13 @@ static int set_option_here(const char *key, int value)
         G.opt_ring_wait = value != 0;
         return 0;
     }
+    if (!strcmp(key, "fir_ahead")) {                     /* staged FIR launches under "overlap" 1: -1 by the plan, 0 never, 1 whenever legal */
+        if (value < -1 || value > 1) return fail(-1, "fir_ahead: -1 (by plan), 0 (never) or 1 (whenever it is legal)");
+        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_AHEAD, value)) return hip_fail();
+        G.opt_fir_ahead = value;
+        return 0;
+    }
+    if (!strcmp(key, "fir_ahead_now") || !strcmp(key, "fir_ahead_apart")) return fail(-1, "%s is read-only", key);
     if (!strcmp(key, "fir_launch")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LAUNCH, value)) return hip_fail();
         G.opt_fir_launch = value; G.opt_fir_launch_set = 1;
@@ -412,6 +422,9 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_lean"))    return G.opt_fir_lean_set ? G.opt_fir_lean : -1;
     if (!strcmp(key, "ring_wait"))   return G.opt_ring_wait;
     if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
+    if (!strcmp(key, "fir_ahead"))   return G.opt_fir_ahead;
+    if (!strcmp(key, "fir_ahead_now")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_AHEAD_NOW) : 0; }
+    if (!strcmp(key, "fir_ahead_apart")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_AHEAD_APART) : -1; }
     if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
     if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
     if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
@@ -553,7 +566,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         const avdsp_ctx *o = &g_template;
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
-        c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
+        c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_fir_ahead = o->opt_fir_ahead; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
         c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
@@ -1509,7 +1522,7 @@ static int ensure_device(void)
     avdsp_hip_profile_enable(G.dev, G.opt_profile);
     if (avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_PROFILE_STRIDE, G.opt_profile_stride > 0 ? G.opt_profile_stride : 1) ||
         avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_OVERLAP, G.opt_overlap) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_ROWS, G.opt_fir_rows) ||
-        avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_READY_WORDS, G.opt_ready_words) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_LANE_HW, G.opt_lane_hw) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SPLIT, G.opt_fir_split) || (G.opt_fir_launch_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LAUNCH, G.opt_fir_launch)) || (G.opt_fir_lean_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LEAN, G.opt_fir_lean)) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, G.opt_ring_wait) ||
+        avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_READY_WORDS, G.opt_ready_words) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_LANE_HW, G.opt_lane_hw) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SPLIT, G.opt_fir_split) || (G.opt_fir_launch_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LAUNCH, G.opt_fir_launch)) || (G.opt_fir_lean_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LEAN, G.opt_fir_lean)) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, G.opt_ring_wait) || (G.opt_fir_ahead != -1 && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_AHEAD, G.opt_fir_ahead)) ||
         avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_SPLIT, G.opt_host_split) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_PIN, G.opt_host_pin) ||
         (G.opt_cu_split && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_CU_SPLIT, G.opt_cu_split)) ||
         (G.opt_group_serial && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_GROUP_FANOUT, 0)) ||

@@ -4390,6 +4390,8 @@ struct Plan {
     bool stores_whole_window = false;                    /* every IO of [io_out_min, io_out_max] is stored by some chain */
     bool overlap_ok = false;                             /* every cascade of the plan feeds a FIR: its launches may run under the previous block's FIR */
     DevArr<unsigned> d_ready; unsigned seq = 0;          /* [nchains] ready words (chain_ready_*): the number of the latest launch whose cascade is through, and the launch counter */
+    /* "fir_ahead" (launch_all): the output IOs the plan's FIR chains store, ascending -- the columns the copy behind a staged FIR launch moves */
+    DevArr<int> d_ahead_cols; int n_ahead_cols = 0, ahead_lo = 0; bool ahead_run = false;      /* ahead_run: one run of n_ahead_cols IOs from ahead_lo */
 };
 
 }  // namespace
@@ -4449,6 +4451,16 @@ struct avdsp_hip_prog {
     hipEvent_t ev_bq[kAhead] = {nullptr, nullptr, nullptr}, ev_fir[kAhead] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fir_now[kAhead] = {nullptr, nullptr, nullptr};   /* what stands for "FIR of this slot has ended": ev_fir[slot], or the stop event of the kernel timer that rode on that launch (no second event on the stream) */
     hipEvent_t last_ride_stop = nullptr; /* ProfileScope::ride: the stop event the latest timed launch carries */
+    /* "fir_ahead" (launch_all): under "overlap" 1 the FIRs of consecutive blocks on s_fir[] in turn, each into a staging
+     * block of the library's own; a copy on the caller's stream behind the FIR's event moves its columns into the caller's block.
+     * -1 by the plan (fir_ahead_by_plan), 0 never, 1 whenever it is legal */
+    int fir_ahead = -1, fir_ahead_now = 0;                /* (fir_ahead_now: what the latest launch did) */
+    DevArr<unsigned> stage[kAhead]; long long stage_words = 0;      /* the staging block of a slot: kFirChunk frames of the widest output window so far */
+    hipEvent_t ev_out[kAhead] = {nullptr, nullptr, nullptr};        /* behind the copy that last read the slot's staging block, on its caller's stream */
+    bool ev_out_set[kAhead] = {false, false, false};
+    std::vector<std::pair<hipStream_t, int>> ahead_probed;       /* per caller's stream: the four streams of a staged launch were seen to run at once (ahead_streams_apart) */
+    int ahead_apart = 0, ahead_remade = 0;                /* ... of the latest staged launch's; streams made anew for it */
+    bool call_in_place = false;                           /* the block call being run has its input and output windows in the same memory (avdsp_hip_run_block) */
     /* How an un-timed FIR launch of the overlap mode is enqueued (launch_all), by what was measured:
      *   1  the event the next cascades wait for rides on the dispatch's own completion signal (hipExtLaunchKernel's stop slot) instead
      *      of a marker packet behind it: 4096 chains 0.5110 -> 0.5078 ms per step, 2048 chains 0.2592 -> 0.2572;
@@ -5080,25 +5092,28 @@ static int make_side_stream(avdsp_hip_prog *prog, hipStream_t *st, bool cascades
     return 0;
 }
 
-static int probe_once(avdsp_hip_prog *prog, hipStream_t fir_stream, bool *ok)
+/* a kernel on `waiter` that waits (bounded) for a word, then a kernel on `setter` that sets it: seen to run at once, or not */
+static int probe_pair(avdsp_hip_prog *prog, hipStream_t waiter, hipStream_t setter, bool *ok)
 {
     *ok = false;
     if (!prog->d_ready_timeouts || !prog->h_ready_flag) return 0;
     unsigned *dseen = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void **)&dseen, prog->h_ready_flag, 0));
     *(volatile unsigned *)(prog->h_ready_flag + 1) = 0;
-    HIP_TRY(hipMemsetAsync(prog->d_ready_timeouts + 1, 0, 4, fir_stream));
-    HIP_TRY(hipStreamSynchronize(fir_stream));
-    HIP_TRY(hipStreamSynchronize(prog->s_bq));
-    hipLaunchKernelGGL(probe_wait, dim3(1), dim3(64), 0, fir_stream, prog->d_ready_timeouts + 1, dseen + 1);
+    HIP_TRY(hipMemsetAsync(prog->d_ready_timeouts + 1, 0, 4, waiter));
+    HIP_TRY(hipStreamSynchronize(waiter));
+    HIP_TRY(hipStreamSynchronize(setter));
+    hipLaunchKernelGGL(probe_wait, dim3(1), dim3(64), 0, waiter, prog->d_ready_timeouts + 1, dseen + 1);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(probe_set, dim3(1), dim3(64), 0, prog->s_bq, prog->d_ready_timeouts + 1);
+    hipLaunchKernelGGL(probe_set, dim3(1), dim3(64), 0, setter, prog->d_ready_timeouts + 1);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(fir_stream));
-    HIP_TRY(hipStreamSynchronize(prog->s_bq));
+    HIP_TRY(hipStreamSynchronize(waiter));
+    HIP_TRY(hipStreamSynchronize(setter));
     *ok = *(volatile unsigned *)(prog->h_ready_flag + 1) == 1u;
     return 0;
 }
+
+static int probe_once(avdsp_hip_prog *prog, hipStream_t fir_stream, bool *ok) { return probe_pair(prog, fir_stream, prog->s_bq, ok); }
 
 /* Per stream the FIRs are launched on: do its kernels and the cascades' stream's run side by side?  That depends on the hardware
  * queues the runtime gave the two streams -- it has a handful per device and deals them out in turn, so a caller's stream may well
@@ -5125,7 +5140,7 @@ static int probe_side_by_side(avdsp_hip_prog *prog, hipStream_t fir_stream)
         HIP_TRY(hipStreamSynchronize(prog->s_bq));
         prog->retired.push_back(prog->s_bq);
         prog->s_bq = ns;
-        prog->probed.clear();
+        prog->probed.clear(); prog->ahead_probed.clear();
         prog->remade++;
     }
     prog->side_by_side = ok;
@@ -5142,7 +5157,45 @@ static int overlap_ready(avdsp_hip_prog *prog)
         /* they order kernels of this device among themselves: no system-scope fence (tools/stream_handover_bench.hip: 8.1 instead of 10.6 us) */
         HIP_TRY(hipEventCreateWithFlags(&prog->ev_bq[i], hipEventDisableTiming | hipEventDisableSystemFence));
         HIP_TRY(hipEventCreateWithFlags(&prog->ev_fir[i], hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!prog->ev_out[i]) HIP_TRY(hipEventCreateWithFlags(&prog->ev_out[i], hipEventDisableTiming | hipEventDisableSystemFence));
     }
+    return 0;
+}
+
+/* "fir_ahead" lives on FOUR streams whose kernels run at once: the caller's (the copies), the cascades' and the FIRs' two.  A process
+ * has a handful of hardware queues (four, by default) and the runtime deals its streams out over them, the library's copy stream and
+ * whatever the host made among them: traced, both FIR streams sat on ONE queue, every FIR behind the previous one's event and its own
+ * wait packets (17 us from end to start, the step 0.54 ms instead of 0.50), and a FIR stream that shares the caller's queue would sit
+ * behind the previous call's copy.  So, once per caller's stream, every pair that must not share is tried like the cascades' stream
+ * (probe_side_by_side), and the stream that waited in a pair that did not run at once is made anew -- the runtime hands out the least
+ * used queue, so the old one is kept until the program goes.  `ahead_apart`: all pairs were seen to run at once; without that the
+ * staged path is still correct, but only taken when forced ("fir_ahead" 1). */
+static int ahead_streams_apart(avdsp_hip_prog *prog, hipStream_t stream)
+{
+    for (auto &pr : prog->ahead_probed) if (pr.first == stream) { prog->ahead_apart = pr.second; return 0; }
+    if (prog->ahead_probed.size() >= 16) prog->ahead_probed.clear();
+    bool all = false;
+    for (int attempt = 0; attempt < 12 && !all; attempt++) {
+        hipStream_t *const pairs[6][2] = {{&prog->s_fir[0], &stream}, {&prog->s_fir[1], &stream}, {&prog->s_fir[1], &prog->s_fir[0]},
+                                         {&prog->s_fir[0], &prog->s_bq}, {&prog->s_fir[1], &prog->s_bq}, {&prog->s_bq, &stream}};
+        all = true;
+        for (auto &p : pairs) {
+            bool ok = false;
+            if (probe_pair(prog, *p[0], *p[1], &ok)) return -1;
+            if (ok) continue;
+            all = false;
+            if (!prog->d_ready_timeouts || prog->ahead_remade >= 10) { attempt = 12; break; }      /* (nothing runs side by side here: a counter-collecting profiler) */
+            hipStream_t ns = nullptr;
+            if (make_side_stream(prog, &ns, p[0] == &prog->s_bq)) return -1;
+            prog->retired.push_back(*p[0]);
+            *p[0] = ns;
+            prog->probed.clear(); prog->ahead_probed.clear();
+            prog->ahead_remade++;
+            break;
+        }
+    }
+    prog->ahead_apart = all ? 1 : 0;
+    prog->ahead_probed.push_back({stream, prog->ahead_apart});
     return 0;
 }
 
@@ -5237,16 +5290,77 @@ int launch_mux(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
     return 0;
 }
 
+/* "fir_ahead": the copy behind a staged FIR launch, on the caller's stream -- the words that launch's FIR chains stored, as they were
+ * formed (store mask and FTZ are fir_tile's), from the staging block to the same place of the caller's block.  Both blocks have the
+ * caller's window geometry.  ahead_copy_run: the columns are one run of `ncols` IOs from `lo`, and run, stride and both addresses
+ * are multiples of 16 bytes (the north star: the whole block); ahead_copy_words: any column list, a word per (frame, column). */
+struct AheadCopyArgs { const unsigned *src; unsigned *dst; const int *cols; int ncols, lo, stride, base, nframes; };
+__global__ void ahead_copy_run(AheadCopyArgs a)
+{
+    const unsigned n4 = (unsigned)a.ncols >> 2, total = (unsigned)a.nframes * n4;      /* (<= kAheadStageCapWords / 4) */
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned f = i / n4, c = i - f * n4;
+        const size_t at = (size_t)f * a.stride + (a.lo - a.base) + 4 * c;
+        *reinterpret_cast<uint4 *>(a.dst + at) = *reinterpret_cast<const uint4 *>(a.src + at);
+    }
+}
+__global__ void ahead_copy_words(AheadCopyArgs a)
+{
+    const unsigned n = (unsigned)a.ncols, total = (unsigned)a.nframes * n;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned f = i / n, j = i - f * n;
+        const size_t at = (size_t)f * a.stride + (a.cols[j] - a.base);
+        a.dst[at] = a.src[at];
+    }
+}
+
+/* a staging block per slot, kFirChunk frames of `words` words in all; growing them waits for the device (a wider window than any so far: rare) */
+static int ahead_stage_ready(avdsp_hip_prog *prog, long long words)
+{
+    if (words <= prog->stage_words) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    prog->stage_words = 0;
+    for (auto &st : prog->stage) if (st.alloc((size_t)words) != hipSuccess) return set_err("hipMalloc(staging block of %lld words)", words);
+    prog->stage_words = words;
+    return 0;
+}
+
 template <int FMT>
 int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
 {
     const bool under = prog->overlap && pl.overlap_ok && biquad_impl && fir_impl;
     pl.seq++;                                             /* this launch's number in the plan's ready words */
+    prog->fir_ahead_now = 0;
     if (under) {
         prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
         if (overlap_ready(prog)) return -1;
         const bool own_fir = prog->overlap >= 2 || prog->cu_split > 0;      /* the FIRs on a stream of the library's own */
-        if (probe_side_by_side(prog, prog->overlap >= 2 ? prog->s_fir[prog->blk & 1] : prog->cu_split > 0 ? prog->s_fir[0] : stream)) return -1;     /* (remembered per stream) */
+        /* "fir_ahead" (DESIGN.md 4.5c): "overlap" 2's arrangement of the FIRs under "overlap" 1's contract -- compute early, write the
+         * caller's block late.  The FIR of this block goes on s_fir[] in turn like "overlap" 2's and stores into a staging block of the
+         * library's own; the caller's stream waits for its event and copies the columns it stored into the caller's block.  So the
+         * caller's block is only ever written in the caller's stream order, one output block may serve every call, and work the caller
+         * queued between two calls has read it before the later call's words arrive.  Every ordering is an event between streams; no
+         * wave waits for anything.  Not legal, and the call takes the path below as ever: chain instances, an in-place call (the
+         * next call's cascade reads its input at once, from the stream of the cascades), a window over the staging cap, "overlap" 2
+         * (its own contract), "cu_split"; plans with handed FIR chains or a mux stage have no overlap at all (overlap_ok).
+         * Nor a plan with impulse groups (the shared-impulse path's plans: their per-chain taps may still have to be made, by a kernel
+         * on the launch's stream -- ensure_private_taps -- which nothing orders in front of the OTHER stream's FIR), nor a fir_impl
+         * other than fir_tile's (fir_stream and fir_flow make their operand ring the same way: ensure_operand_ring): whatever a
+         * staged launch reads exists since the plan was built. */
+        bool staged = false;
+        if (prog->fir_ahead != 0 && !own_fir && pl.n_ahead_cols > 0 && pl.instances <= 1 && prog->inst_n <= 1 && prog->chain_inst <= 1 &&
+            fir_impl == 1 && pl.n_sh_groups == 0 && pl.d_taps64) {
+            const long long sw = ahead_stage_words(io.out_stride);
+            const bool legal = sw > 0 && !prog->call_in_place;
+            if (legal && (prog->fir_ahead == 1 || fir_ahead_by_plan(pl.n_fir, pl.max_taps, io.nframes))) {
+                if (ahead_streams_apart(prog, stream)) return -1;                      /* (remembered per stream) */
+                staged = prog->fir_ahead == 1 || prog->ahead_apart;                    /* (by the plan: only where it can gain) */
+            }
+            if (staged && ahead_stage_ready(prog, sw)) return -1;
+        }
+        prog->fir_ahead_now = staged ? 1 : 0;
+        if (staged) prog->side_by_side = prog->ahead_apart;
+        else if (probe_side_by_side(prog, prog->overlap >= 2 ? prog->s_fir[prog->blk & 1] : prog->cu_split > 0 ? prog->s_fir[0] : stream)) return -1;     /* (remembered per stream) */
         /* fir_tile finds its cascades' blocks through the ready words; the other FIR kernels wait for the cascades' event */
         const bool can_words = (fir_impl == 1 || fir_impl == 4) && pl.d_ready && prog->d_ready_timeouts && prog->side_by_side;
         /* Mode 2 takes the wait packet off the FIRs' stream (a FIR follows the previous one like any kernel of a queue): 4096 chains
@@ -5254,7 +5368,8 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
          * 0.2594 -> 0.2686, 512 chains 0.0864 -> 0.0933 (one box) -- so by default only where a launch is more than one round of waves */
         /* (not with "overlap" 2: two FIRs in flight, the later one's waves would sit on their SIMDs looking at words of a cascade that
          * both of them starve -- 0.496 -> 0.547 ms) */
-        const int rw = prog->ready_words >= 0 ? prog->ready_words : (prog->overlap == 1 && (long long)pl.n_fir * pl.max_taps >= 12000000ll ? 2 : 0);
+        /* (nor with a staged launch, for the same reason: the event, whatever "ready_words" says) */
+        const int rw = staged ? 0 : prog->ready_words >= 0 ? prog->ready_words : (prog->overlap == 1 && (long long)pl.n_fir * pl.max_taps >= 12000000ll ? 2 : 0);
         const bool behind = rw == 2 && can_words;                            /* a kernel behind the cascade publishes */
         const bool words = (rw == 1 && fir_impl == 1 && can_words) || behind;      /* the FIR looks at the words: no event wait on its stream */
         prog->ready_mode_now = behind ? 2 : words ? 1 : 0;
@@ -5289,7 +5404,33 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
             hipLaunchKernelGGL(ready_set, dim3((unsigned)((pl.n_fir + kBlock - 1) / kBlock)), dim3(kBlock), 0, prog->s_bq, pl.d_ready, pl.d_fir_ids, pl.n_fir, pl.seq);
             HIP_TRY(hipGetLastError());
         }
-        if (own_fir) {
+        if (staged) {
+            hipStream_t fs = prog->s_fir[prog->blk & 1];
+            HIP_TRY(hipStreamWaitEvent(fs, prog->ev_bq[slot], 0));
+            /* the slot's staging block is free once the copy of the call three back has read it.  Its event is asked first: a wait
+             * packet costs the queue ~9 us even when its signal is long down.  Where the packet is needed it falls under the other
+             * stream's FIR as long as the host runs a call ahead. */
+            if (prog->ev_out_set[slot] && hipEventQuery(prog->ev_out[slot]) != hipSuccess) {
+                (void)hipGetLastError();
+                HIP_TRY(hipStreamWaitEvent(fs, prog->ev_out[slot], 0));
+            }
+            BlockIO sio = io;
+            sio.out = prog->stage[slot];
+            if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, sio, fir_impl, fs, false)) return -1;
+            HIP_TRY(hipEventRecord(prog->ev_fir[slot], fs));
+            prog->ev_fir_now[slot] = prog->ev_fir[slot];
+            HIP_TRY(hipStreamWaitEvent(stream, prog->ev_fir[slot], 0));
+            AheadCopyArgs ca{prog->stage[slot], io.out, pl.d_ahead_cols, pl.n_ahead_cols, pl.ahead_lo, io.out_stride, io.out_base, io.nframes};
+            const bool run = pl.ahead_run && ((pl.ahead_lo - io.out_base) & 3) == 0 && (pl.n_ahead_cols & 3) == 0 && (io.out_stride & 3) == 0 &&
+                             (reinterpret_cast<size_t>(io.out) & 15) == 0;
+            const long long total = (long long)io.nframes * (run ? pl.n_ahead_cols >> 2 : pl.n_ahead_cols);
+            const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096));
+            if (run) hipLaunchKernelGGL(ahead_copy_run, grid, dim3(kBlock), 0, stream, ca);
+            else     hipLaunchKernelGGL(ahead_copy_words, grid, dim3(kBlock), 0, stream, ca);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(prog->ev_out[slot], stream));
+            prog->ev_out_set[slot] = true;
+        } else if (own_fir) {
             /* ("cu_split": ONE stream of the library's own, on the CUs the cascades' stream does not have)
              * the FIRs of consecutive blocks on two streams of the library's own, in turn: FIR k+1 needs nothing of FIR k, and on one
              * stream it would start a queue hand-over (~10 us) after FIR k's last wave; here its first workgroups fill the chip as FIR
@@ -5597,8 +5738,7 @@ avdsp_hip_prog *avdsp_hip_prog_create(int total_words)
     /* + 2 words: the interpreter fetches the two words behind every head word, also behind the last one */
     hipError_t e = hipMalloc((void **)&p->d_buf, ((size_t)(total_words > 0 ? total_words : 1) + 2) * sizeof(int));
     if (e != hipSuccess) { set_err("hipMalloc(mirror, %d words): %s", total_words, hipGetErrorString(e)); delete p; return nullptr; }
-    if (const char *m = getenv("AVDSP_FIR_LAUNCH_MODE")) p->fir_launch_mode = atoi(m);
-    if (hipMalloc((void **)&p->d_ready_timeouts, 16) != hipSuccess || hipMemset(p->d_ready_timeouts, 0, 16) != hipSuccess) p->d_ready_timeouts = nullptr;   /* (without it the FIR waits for events) */
+    if (const char *m = getenv("AVDSP_FIR_LAUNCH_MODE")) p->fir_launch_mode = atoi(m);    if (hipMalloc((void **)&p->d_ready_timeouts, 16) != hipSuccess || hipMemset(p->d_ready_timeouts, 0, 16) != hipSuccess) p->d_ready_timeouts = nullptr;   /* (without it the FIR waits for events) */
     if (p->d_ready_timeouts) {
         /* the word a timed-out wave sets, in mapped pinned host memory; without it no ready words at all (a time-out nobody hears of) */
         unsigned *dflag = nullptr;
@@ -5645,7 +5785,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
     if (p->bq_fork) (void)hipEventDestroy(p->bq_fork);
     for (auto fs : p->s_fir) if (fs) (void)hipStreamDestroy(fs);
     if (p->ev_unpack) (void)hipEventDestroy(p->ev_unpack);
-    for (int i = 0; i < avdsp_hip_prog::kAhead; i++) { if (p->ev_bq[i]) (void)hipEventDestroy(p->ev_bq[i]); if (p->ev_fir[i]) (void)hipEventDestroy(p->ev_fir[i]); }
+    for (int i = 0; i < avdsp_hip_prog::kAhead; i++) { if (p->ev_bq[i]) (void)hipEventDestroy(p->ev_bq[i]); if (p->ev_fir[i]) (void)hipEventDestroy(p->ev_fir[i]); if (p->ev_out[i]) (void)hipEventDestroy(p->ev_out[i]); }
     (void)hipFree(p->d_buf); (void)hipFree(p->d_in); (void)hipFree(p->d_out); (void)hipFree(p->d_tpdf); (void)hipFree(p->d_frame);
     (void)hipHostFree(p->h_small); (void)hipHostFree(p->h_ready_flag);
     (void)hipHostFree(p->fs_h); (void)hipFree(p->fs_table);
@@ -5791,6 +5931,11 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     }
     pl.stores_whole_window = stores_whole_window(t);
     pl.overlap_ok = overlap_ok(t);
+    if (pl.overlap_ok) {                                  /* the columns a staged FIR launch's copy moves ("fir_ahead") */
+        const AheadColumns A = ahead_columns(t);
+        if (pl.d_ahead_cols.upload(A.cols)) return -1;
+        pl.n_ahead_cols = (int)A.cols.size(); pl.ahead_run = A.run; pl.ahead_lo = A.cols.empty() ? 0 : A.cols.front();
+    }
     if (pl.has_mux) {
         pl.n_mux_plain = (int)M.plain.size(); pl.n_mux_tiles = (int)M.tiles.size(); pl.n_mux_tiled = (int)M.tile_ids.size();
         if (pl.d_mux_recs.upload(t.mux_recs) || pl.d_mux_plain.upload(M.plain) || pl.d_mux_tile_ids.upload(M.tile_ids) || pl.d_mux_tiles.upload(M.tiles)) return -1;
@@ -6235,7 +6380,12 @@ int avdsp_hip_upload_words(avdsp_hip_prog *p, const int32_t *host_buf, int first
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
     if (n && copy_from_caller(p->d_buf + first, host_buf + first, (size_t)n * 4)) return -1;
-    return mirror_to_rings(p);
+    /* the rings are rebuilt on the null stream: the next block's cascade -- and its FIR, where that is staged -- run on non-blocking
+     * streams of the library's, which nothing orders behind the null stream.  A cascade that appended while state_to_ring still rewrote
+     * its ring lost its samples (seen as a block of wrong words right behind a dspRuntimeUploadState between blocks, now and then) */
+    if (mirror_to_rings(p)) return -1;
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
 }
 
 int avdsp_hip_download_words(avdsp_hip_prog *p, int32_t *host_buf, int first, int n)
@@ -6256,7 +6406,9 @@ int avdsp_hip_zero_words(avdsp_hip_prog *p, int first, int n)
     if (check_range(p, first, n)) return -1;
     HIP_TRY(hipDeviceSynchronize());
     if (n) HIP_TRY(hipMemset(p->d_buf + first, 0, (size_t)n * 4));
-    return mirror_to_rings(p);
+    if (mirror_to_rings(p)) return -1;
+    HIP_TRY(hipDeviceSynchronize());                    /* (as in avdsp_hip_upload_words) */
+    return 0;
 }
 
 int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in_stride, int in_io_base,
@@ -6302,6 +6454,7 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         const char *o0 = (const char *)d_out, *o1 = o0 + (size_t)nframes * out_stride * 4;
         /* (a plan with LOAD_MUX chains: its cascades and their replays read the stage's scratch columns, never the caller's input -- but
          * chains the stage stores itself are stored while other workgroups of the stage still read the frame) */
+        prog->call_in_place = i0 < o1 && o0 < i1;          /* ("fir_ahead": such a call is never staged, launch_all) */
         const bool direct = pl.has_mux ? pl.n_mux_stored > 0 : pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
         /* (one-frame calls of the other plans go without the copy.  Not those of a mux plan: its stage is many waves over that ONE frame,
          * every chain reads columns that other chains store, and a wave of another workgroup -- in mux_plain of the same one -- may
@@ -7152,7 +7305,10 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
     FS_STOP(prog);
     HIP_TRY(hipDeviceSynchronize());                    /* nothing in flight when the launch arrangement changes */
     switch (key) {
-    case AVDSP_OPT_OVERLAP:  prog->overlap = value; for (bool &f : prog->ev_fir_set) f = false; return 0;
+    case AVDSP_OPT_OVERLAP:  prog->overlap = value; for (bool &f : prog->ev_fir_set) f = false; for (bool &f : prog->ev_out_set) f = false; return 0;
+    /* (the staged copies of the calls so far have run: the device is idle, above) */
+    case AVDSP_OPT_FIR_AHEAD: if (value < -1 || value > 1) return set_err("fir_ahead: -1 (by plan), 0 (never) or 1 (whenever it is legal)");
+                              prog->fir_ahead = value; for (bool &f : prog->ev_out_set) f = false; return 0;
     case AVDSP_OPT_READY_WORDS: if (value < -1 || value > 2) return set_err("ready_words: -1 (by plan), 0 (events), 1 (the cascade's waves publish) or 2 (a kernel behind the cascade publishes)"); prog->ready_words = value; return 0;
     case AVDSP_OPT_LANE_HW: prog->lane_hw = value != 0; return 0;
     case AVDSP_OPT_FIR_SPLIT: prog->fir_split = value != 0; return 0;
@@ -7173,7 +7329,7 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
                 if (prog->ev_fir[i]) { (void)hipEventDestroy(prog->ev_fir[i]); prog->ev_fir[i] = nullptr; }
                 prog->ev_fir_set[i] = false; prog->ev_fir_now[i] = nullptr;
             }
-            prog->probed.clear();
+            prog->probed.clear(); prog->ahead_probed.clear();
             prog->cu_split = value;
         }
         return 0;
@@ -7199,6 +7355,9 @@ int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
     switch (key) {
     case AVDSP_OPT_SIDE_BY_SIDE: return prog->s_bq ? prog->side_by_side : -1;      /* -1: not probed yet (no overlapped launch so far) */
     case AVDSP_OPT_READY_MODE:   return prog->ready_mode_now;
+    case AVDSP_OPT_FIR_AHEAD:    return prog->fir_ahead;
+    case AVDSP_OPT_FIR_AHEAD_NOW: return prog->fir_ahead_now;
+    case AVDSP_OPT_FIR_AHEAD_APART: return prog->ahead_probed.empty() ? -1 : prog->ahead_apart;
     case AVDSP_OPT_STREAMS_REMADE: return prog->remade;
     case AVDSP_OPT_FRAME_SERVER: return prog->fs_on;
     case AVDSP_OPT_FRAME_SERVER_IDLE_US: return prog->fs_idle_us;

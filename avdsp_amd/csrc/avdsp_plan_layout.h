@@ -421,6 +421,35 @@ inline bool overlap_ok(const ChainTables &t)
     return any && !t.fir.empty() && !t.has_mux;
 }
 
+/* ---- "fir_ahead": FIR launches of consecutive blocks in flight together, their output through a staging block ---- */
+/* the output columns the plain FIR chains of a plan store, in ascending order: what the copy behind a staged FIR launch moves, and nothing
+ * else (passthrough chains, other cores and padding are never touched in the caller's block).  `run`: they are one run of consecutive IOs */
+struct AheadColumns { std::vector<int> cols; bool run = false; };
+inline AheadColumns ahead_columns(const ChainTables &t)
+{
+    AheadColumns A;
+    for (int i : t.fir) {                                /* (a plan with handed FIR chains has no overlap mode: every FIR chain here is a plain one) */
+        const avdsp_chain &c = t.chains[i];
+        for (int k = 0; k < c.n_out; k++) A.cols.push_back(c.out_io[k]);
+    }
+    std::sort(A.cols.begin(), A.cols.end());
+    A.cols.erase(std::unique(A.cols.begin(), A.cols.end()), A.cols.end());
+    A.run = !A.cols.empty() && (size_t)(A.cols.back() - A.cols.front()) + 1 == A.cols.size();
+    return A;
+}
+/* Whether an overlapped launch takes the staged path when "fir_ahead" leaves it to the plan (-1).  It pays where a launch is more than
+ * a chip of waves at a time, so that the next launch's first workgroups fill the SIMDs the last ones of this launch leave: plans of
+ * `kAheadPlanTaps` taps in all (FIR chains x the longest FIR) or more -- the north star (4096 x 4096) and a 2048-chain half of it, not
+ * the shards (512 x 4096, 2048 x 2048), whose cascades are the clock and lose under overlapped FIRs (0.087 -> 0.097 ms) -- and blocks of
+ * `kAheadMinFrames` frames or more: measured at 1024, 512 and 256 frames (0.498 -> 0.488, 0.261 -> 0.252, 0.139 -> 0.133 ms per step,
+ * profiles/fir_ahead.md); shorter blocks have not been measured and stay on the direct path. */
+constexpr long long kAheadPlanTaps = 8000000ll;
+constexpr int kAheadMinFrames = 256;
+inline bool fir_ahead_by_plan(long long n_fir, int max_taps, int frames) { return n_fir * max_taps >= kAheadPlanTaps && frames >= kAheadMinFrames; }
+/* words of one staging block: a launch's frames in the caller's window geometry; 0: over the cap (64 MB a block), the call takes the direct path */
+constexpr long long kAheadStageCapWords = 16ll << 20;
+inline long long ahead_stage_words(int out_stride) { const long long w = (long long)kFirChunk * out_stride; return out_stride > 0 && w <= kAheadStageCapWords ? w : 0; }
+
 /* ---- which FIR kernel a launch takes ---- */
 /* fir_impl's values, and fir_shared, which launch_all takes for the grouped chains of a plan (shared_path) */
 enum FirFamily { kFirPlain = 0, kFirTile = 1, kFirMfma = 2, kFirStream = 3, kFirFlow = 4, kFirShared = 5 };

@@ -278,7 +278,18 @@ enum { AVDSP_OPT_OVERLAP = 0, AVDSP_OPT_PROFILE_STRIDE = 1, AVDSP_OPT_FIR_ROWS =
                                                    no chain instances); 0: every FIR chain on the kernels fir_impl names */
        AVDSP_OPT_FIR_SHARED_CHAINS = 24,        /* read-only: chains the latest FIR launch ran on fir_shared */
        AVDSP_OPT_FIR_SHARED_GROUPS = 25,        /* read-only: ... in that many groups */
-       AVDSP_OPT_FIR_SHARED_ROWS = 26           /* read-only: ... with that many row tiles per wave (the R of fir_shared<FMT, R>: 1, 2 or 4; 0: not on fir_shared) */ };
+       AVDSP_OPT_FIR_SHARED_ROWS = 26,          /* read-only: ... with that many row tiles per wave (the R of fir_shared<FMT, R>: 1, 2 or 4; 0: not on fir_shared) */
+       AVDSP_OPT_FIR_AHEAD = 27,                /* under OVERLAP 1: the FIRs of consecutive blocks in flight together, each into a staging block that a copy on the
+                                                   caller's stream moves into the caller's block: -1 (default) by the plan, 0 never, 1 whenever it is legal */
+       AVDSP_OPT_FIR_AHEAD_NOW = 28,            /* read-only: 1 the latest launch took that staged path, 0 it did not */
+       AVDSP_OPT_FIR_AHEAD_APART = 29           /* read-only: 1 the four streams of the staged path (the caller's, the cascades', the FIRs' two) were seen to run at once,
+                                                   0 they were not (a forced staged launch is then correct, but overlaps nothing), -1 not tried yet */ };
+/* FIR_AHEAD: OVERLAP 2's arrangement -- FIR k+1's first workgroups fill the chip as FIR k's last ones leave -- without its
+ * contract on the output: the caller's block is written by a copy in the caller's stream order only, so one block may serve every call.
+ * By the plan: plans of 8 M taps or more in all (FIR chains x the longest FIR) and blocks of 256 frames or more (avdsp_plan_layout.h,
+ * fir_ahead_by_plan).  Never, whatever the value: chain instances, in-place calls, windows of more than 16384 words per frame, plans
+ * without overlap (handed FIR chains, a LOAD_MUX stage, a cascade that stores itself), plans with impulse groups (fir_group_*), a fir_impl
+ * other than 1, OVERLAP 0 / 2, CU_SPLIT. */
 /* FIR_LEAN: fir_tile's chunk boundary with a third of the vector instructions: -1 by the plan (default), 0 never, 1 always. */
 /* READY_WORDS (under OVERLAP): how a block's FIR finds its cascades' block in the rings: 0 an event between the two queues, 1 per-chain
  * words published by the cascade's waves (write-through stores) and polled by the FIR's, 2 the words set by a kernel behind the

@@ -224,6 +224,20 @@ int dspRuntimeStrandInfo(int format, opcode_t *core, int *strands, int *ops_per_
  * (stream order no longer covers it); 2 = also the FIRs of consecutive blocks on two streams in turn, so that one starts while the other's
  * last workgroups leave (worth 3.5 % on a 4096-channel program, a loss below ~2000 channels) -- the caller then also guarantees that the
  * OUTPUT block of a call is not one an earlier call's FIR may still be writing (the caller's stream still waits for every block's end).
+ * "fir_ahead" (under "overlap" 1) = "overlap" 2's arrangement of the FIRs WITHOUT its guarantee on the output: the FIRs of
+ * consecutive blocks run on two streams of the library's own, each into a staging block of the library's, and a copy on the caller's
+ * stream behind the FIR's event moves exactly the words the FIR chains store into the caller's block -- which is therefore only ever
+ * written in the caller's stream order: one output block may serve every call, and work queued between two calls has read it before
+ * the later call's words arrive.  -1 (default) = by the plan: plans of 8 M taps or more in all (FIR chains x the longest FIR: 4096 or
+ * 2048 channels x 4096 taps, not their 8-GPU shards) and launches of 256 frames or more, and only once the four streams in play have
+ * been seen to run side by side; 0 = never; 1 = whenever it is legal.  Never, whatever the value: in-place calls, chain instances,
+ * output windows of more than 16384 words per frame, plans without an overlap mode (handed FIR chains, LOAD_MUX chains, a cascade that
+ * stores itself), plans with impulse groups (dspRuntimeFirGroupInfo: their per-chain taps are made on a launch's own stream), a "fir_impl"
+ * other than 1, "overlap" 0 / 2, "cu_split" -- such a call takes the path it always took.  dspRuntimeGetOption("fir_ahead_now") = 1 /
+ * 0: what the latest launch did; ("fir_ahead_apart") = 1 / 0 / -1: the four streams were seen to run side by side / were not (a
+ * forced staged launch is then correct and overlaps nothing) / not tried yet.  AVDSP_FIR_AHEAD=-1|0|1 in the environment when the
+ * library is loaded is the option's default for a host that cannot call dspRuntimeSetOption (dspRuntimeGetOption reads that value).
+ * Costs three staging blocks of 1024 frames of the widest output window (48 MB for 4096 channels).
  * Results are identical in every mode.  Under "overlap": "ring_wait" 1 (default) = the HOST waits (at most 1 ms, then it leaves it to the
  * stream after all) until the FIR three blocks back has ended before it enqueues a block's cascade -- the call then returns no more than
  * three blocks ahead of the device, and the cascades' stream carries no wait packet (worth 10 % on a 512-channel shard); 0 = that stream
