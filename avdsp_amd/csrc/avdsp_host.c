@@ -117,6 +117,7 @@ typedef struct avdsp_ctx {
     int             opt_chain_finish;                      /* "chain_finish": dressed SAT0DB finishes and a head TPDF_CALC lowered to the chain kernels (default 0) */
     int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
     int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
+    int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
 
 /* no program loaded: options set now are the defaults every program starts from (and keeps following, see dspRuntimeSetOption) */
@@ -324,6 +325,11 @@ static int set_option_here(const char *key, int value)
         G.opt_fir_tail = value;
         return replan();
     }
+    if (!strcmp(key, "mux_tail")) {                      /* dressed finishes, delay lines and a head TPDF_CALC in cores with LOAD_MUX heads; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "mux_tail: 0 or 1");
+        G.opt_mux_tail = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -428,6 +434,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
     if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
     if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
+    if (!strcmp(key, "mux_tail"))     return G.opt_mux_tail;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -567,7 +574,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_fir_ahead = o->opt_fir_ahead; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -817,6 +824,8 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
     const unsigned delay_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* dsp_runtime.c:81-90 */
     /* "fir_tail": the delay and the dressed finish may stand behind a DSP_FIR (formats 4 and 6: the chain FIR's) */
     const int fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
+    /* "mux_tail": all of that also behind a LOAD_MUX head and beside such chains */
+    const int mux_tail = G.opt_mux_tail;
 
     if (ensure_encoding(format)) return g_err_code;
 
@@ -947,7 +956,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (!open) return fail(-8, "word %d: a DSP_DELAY in front of the chain's LOAD is not lowered to the HIP path", at);
             if (cur.n_out) return fail(-8, "word %d: a DSP_DELAY behind a STORE is not lowered to the HIP path", at);
             if (cur.delay_slot) return fail(-8, "word %d: a second DSP_DELAY in one chain is not lowered to the HIP path", at);
-            if ((fir_op && !fir_tail) || cur.load_mode == AVDSP_LOAD_MUX)
+            if ((fir_op && !fir_tail) || (cur.load_mode == AVDSP_LOAD_MUX && !mux_tail))
                 return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR or a LOAD_MUX head is not lowered to the HIP path", at);
             LC_NEED(3);
             if (a[0] < 0) return fail(-8, "word %d: delay line of negative size %d", at, a[0]);
@@ -965,7 +974,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
         case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:      /* :478-534, "chain_finish" */
             if (!finish_on) goto not_lowered;
             if (!open || cur.n_out || cur.sat || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
-            if ((fir_op && !fir_tail) || cur.load_mode == AVDSP_LOAD_MUX)
+            if ((fir_op && !fir_tail) || (cur.load_mode == AVDSP_LOAD_MUX && !mux_tail))
                 return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
             if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
             cur.finish = op == DSP_SAT0DB_TPDF ? AVDSP_FINISH_TPDF : op == DSP_SAT0DB_GAIN ? AVDSP_FINISH_GAIN : AVDSP_FINISH_TPDF_GAIN;
@@ -1007,10 +1016,25 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
 #undef LC_NEED
 #undef LC_PROG
     if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
-    if ((L->ndressed || L->tpdf_calc) && lowered_has_mux(L))
+    if ((L->ndressed || L->tpdf_calc) && !mux_tail && lowered_has_mux(L))
         return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
-    if (L->ndelayed && lowered_has_mux(L))
+    if (L->ndelayed && !mux_tail && lowered_has_mux(L))
         return fail(-8, "chains with a DSP_DELAY beside LOAD_MUX heads are not lowered to the HIP path");
+    if (L->ndelayed && mux_tail && lowered_has_mux(L)) {
+        /* ("mux_tail") the mux stage writes a LOAD_MUX result word once per launch, from its last frame, and ahead of chain_tail, where
+         * the reference writes it in every frame between two visits of the line: no line -- index word and samples -- may share a
+         * word with one of them */
+        int clash = 0;
+        for (int i = 0; i < L->nchains && !clash; i++) {
+            const avdsp_chain *c = &L->chains[i];
+            if (!c->delay_slot) continue;
+            const long long lo = c->delay_word;
+            const long long hi = lo + 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
+            for (int j = 0; j < L->nchains && !clash; j++)
+                if (L->chains[j].load_mode == AVDSP_LOAD_MUX) clash = (long long)L->chains[j].mux_result_word < hi && (long long)L->chains[j].mux_result_word + 2 > lo;
+        }
+        if (clash) return fail(-8, "a delay line and a LOAD_MUX result word share words of the state area");
+    }
     if (L->ndelayed > 1) {
         /* the chains run side by side: two of them must not share words of a line (the encoder never lets them; the strand lowering
          * checks the same).  [first word, words] per line, sorted by the first */
@@ -1719,6 +1743,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.tpdf_calc = L.tpdf_calc; d.tpdf_calc_arg = L.tpdf_calc_arg; d.tpdf_calc_result_word = L.tpdf_calc_word;
         d.delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* (as lower_core_ex checked the lines' extents) */
         d.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
+        d.mux_tail = G.opt_mux_tail;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -1998,6 +2023,41 @@ int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *o
     }
     if (handed_chains) *handed_chains = nh;
     if (of_them_delayed) *of_them_delayed = nd;
+    return 0;
+}
+
+/* Host-only: what "mux_tail" makes of the core -- among the chains this process runs (dspRuntimeSetShard) of a core that holds
+ * LOAD_MUX chain heads: those with a dressed finish, those with a DSP_DELAY, and the LOAD_MUX chains without sections and FIR that
+ * the mux stage itself finishes (a dressed finish, no delay) or hands to chain_tail (a delay) -- the chains that make the stage's
+ * launches the TAIL forms.  No device is touched.  A core without LOAD_MUX heads, or one that is not a set of
+ * chains, has none. */
+int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *delayed_chains, int *stage_finished_or_handed)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nf = 0, nd = 0, ns = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0 && lowered_has_mux(&L)) {
+            int lo, hi;
+            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+            for (int i = lo; i < hi; i++) {
+                const avdsp_chain *c = &L.chains[i];
+                nf += c->finish != 0;
+                nd += c->delay_slot != 0;
+                ns += c->load_mode == AVDSP_LOAD_MUX && !c->nsec && !c->fir_taps && (c->finish || c->delay_slot);
+            }
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (dressed_chains) *dressed_chains = nf;
+    if (delayed_chains) *delayed_chains = nd;
+    if (stage_finished_or_handed) *stage_finished_or_handed = ns;
     return 0;
 }
 
@@ -2820,7 +2880,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

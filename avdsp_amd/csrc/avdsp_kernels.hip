@@ -3228,6 +3228,37 @@ __device__ __forceinline__ void mux_emit(const MuxArgs &a, const MuxRec &r, int 
     }
 }
 
+/* TAIL ("mux_tail"): the plan holds LOAD_MUX chains without a filter whose SAT0DB slot is dressed, or that have a delay
+ * line.  The stage's epilogue then chooses per chain between the column word, the plain store, finish_stage on the full accumulator
+ * (with the frame's addend, as passthrough's DRESSED form) and the chain's row of the hand-over block, where chain_tail takes the
+ * accumulator up as it takes a cascade's.  TAIL false is the stage as it was. */
+struct MuxArgsTail : MuxArgs {
+    const FinishRec *finish;               /* [chain]; null: the plan has no dressed chain */
+    const int *hand_row;                   /* [chain]: the chain's row of the hand-over block, -1: none; null: the plan has no rows */
+    const unsigned long long *addend;      /* the dither addend of every frame of this launch (dither_block) */
+    unsigned long long *hand;              /* [hand_row][kFirChunk frames] accumulators */
+};
+template <bool TAIL> using MuxArgsT = std::conditional_t<TAIL, MuxArgsTail, MuxArgs>;
+
+template <int FMT>
+__device__ __forceinline__ void mux_emit_tail(const MuxArgsTail &a, const MuxRec &r, int cid, int n, typename Alu<FMT>::type X)
+{
+    unsigned long long u;
+    if constexpr (FMT == 2) u = (unsigned long long)X; else u = (unsigned long long)__double_as_longlong(X);
+    const int row = r.col < 0 && a.hand_row ? a.hand_row[cid] : -1;
+    if (r.col >= 0) a.scratch[(size_t)n * a.scratch_stride + r.col] = narrow_stage<FMT>(X);
+    else if (row >= 0) a.hand[(size_t)row * kFirChunk + n] = u;
+    else {
+        const FinishRec fin = a.finish ? a.finish[cid] : FinishRec{0, 0u};
+        const unsigned word = fin.finish ? finish_stage<FMT>(X, fin.finish, fin.gain_bits, a.addend[n], a.io.store_mask)
+                                         : store_stage<FMT>(X, r.sat, a.io.store_mask);
+#pragma unroll
+        for (int k = 0; k < AVDSP_MAX_STORES; k++)
+            if (k < r.n_out) a.io.out[(size_t)n * a.io.out_stride + (r.out_io[k] - a.io.out_base)] = word;
+    }
+    if (n == a.io.nframes - 1) { a.buf[r.result_word] = (int)(unsigned)u; a.buf[r.result_word + 1] = (int)(unsigned)(u >> 32); }
+}
+
 /* a sample word as the operand of the list's products */
 template <int FMT>
 __device__ __forceinline__ double mux_sample(unsigned raw)
@@ -3238,8 +3269,8 @@ __device__ __forceinline__ double mux_sample(unsigned raw)
 
 /* mux_plain<FMT>: one lane per (chain, frame) walks the chain's own list in order -- format 2, chains in no mix group, groups under
  * AVDSP_MUX_GROUP_MIN.  Consecutive lanes take consecutive chains of one frame: the column stores coalesce. */
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void mux_plain(const MuxArgs a)
+template <int FMT, bool TAIL = false>
+__global__ __launch_bounds__(kBlock) void mux_plain(const MuxArgsT<TAIL> a)
 {
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     const long long total = (long long)a.nids * a.io.nframes;
@@ -3256,7 +3287,8 @@ __global__ __launch_bounds__(kBlock) void mux_plain(const MuxArgs a)
             if constexpr (FMT == 2) X = (long long)((unsigned long long)X + (unsigned long long)((long long)(int)raw * (long long)gw));      /* v_mad_i64_i32, wrapping */
             else X = __builtin_fma(mux_sample<FMT>(raw), mulop(__int_as_float(gw)), X);
         }
-        mux_emit<FMT>(a, r, n, X);
+        if constexpr (TAIL) mux_emit_tail<FMT>(a, r, a.ids[slot], n, X);
+        else mux_emit<FMT>(a, r, n, X);
     }
 }
 
@@ -3284,8 +3316,8 @@ __global__ __launch_bounds__(kBlock) void mux_gains_to_f64(const MuxGainArgs a)
  * sample serves 64 chains.  The list is walked in chunks of 32 positions: A [64][33] and B [32][66] doubles in LDS (pitches of 33 and
  * 66 doubles), 33 792 bytes. */
 constexpr int kMuxKc = 32, kMuxFrames = 64, kMuxApitch = kMuxKc + 1, kMuxBpitch = kMuxFrames + 2;
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void mux_tile(const MuxArgs a)
+template <int FMT, bool TAIL = false>
+__global__ __launch_bounds__(kBlock) void mux_tile(const MuxArgsT<TAIL> a)
 {
     __shared__ double As[kMuxRows * kMuxApitch], Xs[kMuxKc * kMuxBpitch];
     flush_f32_subnormals_like_the_reference();
@@ -3334,11 +3366,13 @@ __global__ __launch_bounds__(kBlock) void mux_tile(const MuxArgs a)
     for (int r = 0; r < 4; r++) {
         const int m = 16 * wave + k + 4 * r;
         if (m >= T.nrec) continue;
-        const MuxRec rec = a.recs[a.ids[T.id0 + m]];
+        const int cid = a.ids[T.id0 + m];
+        const MuxRec rec = a.recs[cid];
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             const int n = f0 + 16 * t + ij;
-            if (n < B) mux_emit<FMT>(a, rec, n, acc[t][r]);
+            if constexpr (TAIL) { if (n < B) mux_emit_tail<FMT>(a, rec, cid, n, acc[t][r]); }
+            else if (n < B) mux_emit<FMT>(a, rec, n, acc[t][r]);
         }
     }
 }
@@ -4380,6 +4414,8 @@ struct Plan {
     DevArr<double> d_mux_g64;                            /* their gains as doubles */
     DevArr<unsigned> d_mux_scratch;
     int n_mux_stored = 0;                                /* chains the stage stores itself (no filter behind the head) */
+    int n_mux_finished = 0, n_mux_handed = 0;            /* "mux_tail": of those, the ones with a dressed finish; chains whose accumulator the stage hands to chain_tail
+                                                            (either makes the stage's launches the TAIL forms) */
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
     DevArr<int> d_lane_rows; int n_lane_rows = 0;        /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
@@ -5267,24 +5303,31 @@ int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl,
 
 /* the LOAD_MUX stage of a block (at most kFirChunk frames), on the caller's stream in front of the cascades: mux_tile for the mix groups,
  * mux_plain for everything else; they write different columns and run one behind the other on the stream */
-template <int FMT>
+template <int FMT, bool TAIL = false>
 int launch_mux(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
 {
     ProfileScope scope(prog, stream, AVDSP_KERNEL_MUX); scope.begin();
-    MuxArgs a{};
+    MuxArgsT<TAIL> a{};
     a.buf = prog->d_buf; a.recs = pl.d_mux_recs; a.g64 = pl.d_mux_g64; a.tiles = pl.d_mux_tiles;
     a.scratch = pl.d_mux_scratch; a.scratch_stride = pl.nchains; a.io = io;
+    if constexpr (TAIL) {
+        /* ("mux_tail": the stage finishes dressed chains -- the addend table, this launch's frames -- and hands delayed ones over) */
+        if ((pl.n_mux_finished && (!prog->d_addend || !pl.d_finish)) || (pl.n_mux_handed && (!pl.d_hand || !pl.d_hand_row)))
+            return set_err("a mux stage that finishes or hands over chains without its tables");
+        a.finish = pl.d_finish; a.hand_row = pl.d_hand_row; a.hand = pl.d_hand;
+        a.addend = prog->d_addend ? prog->d_addend + pl.block_f0 : nullptr;
+    }
     if constexpr (FMT != 2) {
         if (pl.n_mux_tiles) {
             a.ids = pl.d_mux_tile_ids; a.nids = pl.n_mux_tiled;
-            hipLaunchKernelGGL(mux_tile<FMT>, dim3((unsigned)pl.n_mux_tiles, (unsigned)((io.nframes + kMuxFrames - 1) / kMuxFrames)), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((mux_tile<FMT, TAIL>), dim3((unsigned)pl.n_mux_tiles, (unsigned)((io.nframes + kMuxFrames - 1) / kMuxFrames)), dim3(kBlock), 0, stream, a);
             HIP_TRY(hipGetLastError());
         }
     }
     if (pl.n_mux_plain) {
         a.ids = pl.d_mux_plain; a.nids = pl.n_mux_plain;
         const long long total = (long long)pl.n_mux_plain * io.nframes;
-        hipLaunchKernelGGL(mux_plain<FMT>, dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 1 << 16)), dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL((mux_plain<FMT, TAIL>), dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 1 << 16)), dim3(kBlock), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -5825,7 +5868,7 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     pl.format = d->format; pl.nchains = d->nchains; pl.store_mask = d->store_mask;
     pl.lane_mode = d->format == 3 || d->format == 5;
     pl.instances = d->instances > 1 ? d->instances : 1;
-    pl.has_mux = t.has_mux; pl.n_mux_stored = t.n_mux_stored; pl.max_taps = t.max_taps;
+    pl.has_mux = t.has_mux; pl.n_mux_stored = t.n_mux_stored; pl.n_mux_finished = t.n_mux_finished; pl.n_mux_handed = t.n_mux_handed; pl.max_taps = t.max_taps;
     pl.io_in_min = t.io_in_min; pl.io_in_max = t.io_in_max; pl.io_out_min = t.io_out_min; pl.io_out_max = t.io_out_max;
     if (pl.d_sec_coef.upload(t.coef) || pl.d_sec_state.upload(t.state)) return -1;
     if (pl.lane_mode) {                                  /* no launch groups, no rings: chain_lane walks the chain list itself */
@@ -5866,12 +5909,13 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece; a handed FIR chain's row is
          * filled by its FIR, and one without a delay gets the record of a line of 0 samples in front of its slot: chain_tail bypasses
          * such a line -- nothing read, nothing written -- and runs the slot's opcode and the STOREs) */
+        /* (the rows are check_chains': a cascade, a FIR -- or, "mux_tail", the mux stage -- fills them) */
         std::vector<int> hand_row(L.dev_chains.size(), -1);
         std::vector<DelayRec> tail;
-        int rows = 0;
+        const int rows = t.n_hand_rows;
         for (int i : t.tail) {
             const avdsp_chain &c = t.chains[i];
-            const int row = (c.nsec || c.fir_taps) ? rows++ : -1;
+            const int row = t.hand_row[i];
             hand_row[i] = row;
             if (c.delay_slot) tail.push_back(DelayRec{i, c.delay_slot, c.delay_word, c.delay_us_word, c.delay_max, row, c.sat, c.finish, c.finish_gain_bits});
             else tail.push_back(DelayRec{i, AVDSP_DELAY_A, 0, 0, 0, row, c.sat, c.finish, c.finish_gain_bits});
@@ -6557,10 +6601,12 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         io.store_mask = pl.store_mask;
         int rc;
         if (pl.has_mux) {                                /* the mux stage, then every chain from its scratch column */
+            /* (the TAIL forms only for a plan whose stage finishes a dressed chain or hands one to chain_tail -- "mux_tail") */
+            const bool tail_forms = pl.n_mux_finished + pl.n_mux_handed > 0;
             switch (pl.format) {
-            case 2:  rc = launch_mux<2>(prog, pl, io, (hipStream_t)stream); break;
-            case 4:  rc = launch_mux<4>(prog, pl, io, (hipStream_t)stream); break;
-            default: rc = launch_mux<6>(prog, pl, io, (hipStream_t)stream); break;
+            case 2:  rc = tail_forms ? launch_mux<2, true>(prog, pl, io, (hipStream_t)stream) : launch_mux<2>(prog, pl, io, (hipStream_t)stream); break;
+            case 4:  rc = tail_forms ? launch_mux<4, true>(prog, pl, io, (hipStream_t)stream) : launch_mux<4>(prog, pl, io, (hipStream_t)stream); break;
+            default: rc = tail_forms ? launch_mux<6, true>(prog, pl, io, (hipStream_t)stream) : launch_mux<6>(prog, pl, io, (hipStream_t)stream); break;
             }
             if (rc) return rc;
             io.in = pl.d_mux_scratch; io.in_stride = pl.nchains; io.in_base = 0;

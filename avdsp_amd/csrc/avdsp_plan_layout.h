@@ -6,7 +6,8 @@
  *
  * avdsp_hip_prog_add_plan runs the stages in this order; each returns its tables, or an error text for set_err:
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
- *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads
+ *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads; which chains the
+ *                      stage stores, finishes or hands over itself ("mux_tail")
  *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `fir_hand`, `pass` and `tail` lists
  *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
@@ -50,7 +51,8 @@ struct MuxRec {                      /* one per chain of a plan that holds LOAD_
     int list_word, count;            /* first (IO, gain) pair in the mirror and the number of pairs; count 0: a LOAD / LOAD_GAIN chain
                                         beside them -- its sample word of IO `list_word` is copied into its column as it is */
     int result_word;                 /* the opcode's 8-byte result word in the mirror */
-    int col;                         /* scratch column; -1: no filter behind the head, the stage stores the chain itself */
+    int col;                         /* scratch column; -1: no filter behind the head, the stage stores the chain itself -- or ("mux_tail", the TAIL forms
+                                        of the stage) finishes it, or hands its accumulator to chain_tail (ChainTables::hand_row) */
     int sat, n_out, out_io[AVDSP_MAX_STORES];
 };
 /* up to 64 chains of one mix group (lists of one IO sequence): four row tiles of mux_tile's workgroup */
@@ -85,8 +87,16 @@ struct ChainTables {
     bool has_mux = false;
     int mux_lo = 0x7FFFFFFF, mux_hi = 0; /* the mirror words that hold the lists */
     std::vector<MuxRec> mux_recs;
-    std::vector<char> mux_stored;        /* chains the mux stage stores itself (no filter behind the head) */
+    std::vector<char> mux_stored;        /* chains the mux stage stores itself (no filter behind the head, no delay line) */
     int n_mux_stored = 0;
+    /* "mux_tail" (DESIGN.md 4.2i): LOAD_MUX chains without a filter whose accumulator the stage hands to chain_tail (a delay line behind
+     * the head; they are not stored by the stage), and those it finishes itself with a dressed finish (they are, and count above).  A plan
+     * with either launches the TAIL forms of mux_tile and mux_plain, every other plan the stage as it was */
+    std::vector<char> mux_handed;
+    int n_mux_handed = 0, n_mux_finished = 0;
+    bool mux_tail_forms() const { return n_mux_handed + n_mux_finished > 0; }
+    std::vector<int> hand_row;           /* per chain: its row of the hand-over block (the chains of `tail` with a cascade, a FIR or a stage hand-over), else -1 */
+    int n_hand_rows = 0;
     int io_in_min = 0x7FFFFFFF, io_in_max = -1, io_out_min = 0x7FFFFFFF, io_out_max = -1, max_taps = 0;
     std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
     std::vector<int> pass_dressed;       /* ... of the latter, those with a dressed finish (they are not in `pass`) */
@@ -104,6 +114,7 @@ inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, Ch
     t.coef.assign(d->sec_coef_word, d->sec_coef_word + d->nsections);
     t.state.assign(d->sec_state_word, d->sec_state_word + d->nsections);
     t.mux_stored.assign(d->nchains, 0);
+    t.mux_handed.assign(d->nchains, 0);
     for (int i = 0; i < d->nsections; i++)
         if (t.coef[i] < 0 || t.coef[i] + 5 > buf_words || t.state[i] < 0 || t.state[i] + 6 > buf_words || (t.state[i] & 1))
             return text("section %d addresses words outside the loaded buffer", i);
@@ -144,7 +155,8 @@ inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
             }
             r.list_word = c.mux_word; r.count = c.mux_count; r.result_word = c.mux_result_word;
             r.col = (c.nsec || c.fir_taps) ? i : -1;
-            if (r.col < 0) { t.mux_stored[i] = 1; t.n_mux_stored++; }
+            if (r.col < 0 && c.delay_slot) { t.mux_handed[i] = 1; t.n_mux_handed++; }      /* ("mux_tail": chain_tail stores it, from its hand-over row) */
+            else if (r.col < 0) { t.mux_stored[i] = 1; t.n_mux_stored++; t.n_mux_finished += c.finish != 0; }
             c.load_mode = kLoadRaw;
         } else {
             if (c.in_io < 0) return text("chain %d: bad IO", i);
@@ -160,6 +172,8 @@ inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
 inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
 {
     const bool fir_tail = d->fir_tail && (d->format == 4 || d->format == 6);
+    const bool mux_refused = t.has_mux && !d->mux_tail;   /* ("mux_tail": dressed finishes, delay lines and a head TPDF_CALC in a plan with LOAD_MUX chains) */
+    t.hand_row.assign(d->nchains, -1);
     for (int i = 0; i < d->nchains; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return text("chain %d: bad section range", i);
@@ -178,18 +192,18 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             t.max_taps = std::max(t.max_taps, c.fir_taps);
         }
         if (c.finish) {
-            /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front (but under "fir_tail"), no LOAD_MUX plan, no instances */
+            /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front (but under "fir_tail"), no LOAD_MUX plan (but under "mux_tail"), no instances */
             if (c.finish < AVDSP_FINISH_TPDF || c.finish > AVDSP_FINISH_TPDF_GAIN || c.sat != 1) return text("chain %d: finish %d", i, c.finish);
-            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || t.has_mux || d->instances > 1)
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || mux_refused || d->instances > 1)
                 return text("chain %d: a dressed finish has no kernel here", i);
             t.n_dressed++;
         }
         if (c.delay_slot) {
-            /* one DSP_DELAY (avdsp_chain::delay_slot): chain_tail of formats 2, 4 and 6, no FIR (but under "fir_tail"), no LOAD_MUX plan, no instances; the line
+            /* one DSP_DELAY (avdsp_chain::delay_slot): chain_tail of formats 2, 4 and 6, no FIR (but under "fir_tail"), no LOAD_MUX plan (but under "mux_tail"), no instances; the line
              * -- its index word and the samples of the longest delay it can be asked for -- and the parameter word inside the buffer */
             if ((c.delay_slot != AVDSP_DELAY_A && c.delay_slot != AVDSP_DELAY_B) || (c.delay_slot == AVDSP_DELAY_B && c.sat != 1))
                 return text("chain %d: delay slot %d", i, c.delay_slot);
-            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || t.has_mux || d->instances > 1)
+            if ((d->format != 2 && d->format != 4 && d->format != 6) || (c.fir_taps && !fir_tail) || mux_refused || d->instances > 1)
                 return text("chain %d: a delay line has no kernel here", i);
             const long long nline = c.delay_us_word ? (long long)c.delay_max : (long long)(((unsigned long long)(unsigned)c.delay_max * d->delay_line_factor) >> 32);
             if (c.delay_max < 0 || c.delay_word < 0 || (long long)c.delay_word + 1 + nline > buf_words || c.delay_us_word < 0 || c.delay_us_word >= buf_words)
@@ -197,11 +211,15 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
         }
         const bool handed = c.fir_taps && (c.finish || c.delay_slot);
         if (handed) t.fir_hand.push_back(i); else if (c.fir_taps) t.fir_plain.push_back(i);
-        if (c.delay_slot || handed) { t.tail.push_back(i); continue; }
+        if (c.delay_slot || handed) {
+            t.tail.push_back(i);
+            if (c.nsec || c.fir_taps || t.mux_handed[i]) t.hand_row[i] = t.n_hand_rows++;
+            continue;
+        }
         if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
     }
     if (d->tpdf_calc) {
-        if ((d->format != 2 && d->format != 4 && d->format != 6) || t.has_mux || d->instances > 1) return "a head TPDF_CALC has no kernel here";
+        if ((d->format != 2 && d->format != 4 && d->format != 6) || mux_refused || d->instances > 1) return "a head TPDF_CALC has no kernel here";
         if (d->tpdf_calc_result_word < 0 || (long long)d->tpdf_calc_result_word + 2 > buf_words) return "TPDF_CALC result word outside the loaded buffer";
     }
     return "";

@@ -14,6 +14,7 @@
  * SAT0DB_TPDF / SAT0DB_GAIN / SAT0DB_TPDF_GAIN (:478-534), behind an optional DSP_TPDF_CALC at the head of the core (:537-545),
  * and ("chain_delay") chains without FIR and LOAD_MUX with one DSP_DELAY (:769-794) on either side of the SAT0DB slot
  * and ("fir_tail", formats 4 and 6) both of them behind a chain's DSP_FIR
+ * and ("mux_tail") all of that behind a LOAD_MUX head and beside LOAD_MUX chains
  *
  * for every chain of the core over a block of frame-interleaved samples.
  */
@@ -93,6 +94,8 @@ typedef struct avdsp_plan_desc {
     uint32_t delay_line_factor;      /* 2^32 / 10^6 x fs of the current rate (chains with a delay_slot: samples = us x factor >> 32) */
     int32_t  fir_tail;               /* 1 ("fir_tail", formats 4 and 6): a chain with fir_taps may have a finish and / or a delay_slot -- a handed FIR chain,
                                         whose FIR hands its accumulators to chain_tail; 0: such a chain is refused                */
+    int32_t  mux_tail;               /* 1 ("mux_tail"): a plan with LOAD_MUX chains may hold chains with a finish or a delay_slot and a head TPDF_CALC
+                                        (the stage finishes or hands over those without a filter behind the head); 0: such a plan is refused */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

@@ -88,7 +88,8 @@ int       dspQM32(double x, int m);         /* dsp_header.c:83-85 */
  * format (in 2, 4 and 6 a chain may also begin with LOAD_MUX, see dspRuntimeMuxInfo; and, with dspRuntimeSetOption("chain_finish", 1),
  * a chain without FIR and LOAD_MUX may end in SAT0DB_TPDF, SAT0DB_GAIN or SAT0DB_TPDF_GAIN instead of SAT0DB, and the core may begin
  * with one DSP_TPDF_CALC of the default width, see dspRuntimeFinishInfo; and, with dspRuntimeSetOption("chain_delay", 1), such a chain
- * may hold one DSP_DELAY behind its banks, see dspRuntimeDelayInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
+ * may hold one DSP_DELAY behind its banks, see dspRuntimeDelayInfo; "fir_tail" and "mux_tail" lift the "without FIR" and the "without
+ * LOAD_MUX" of both, see dspRuntimeFirTailInfo and dspRuntimeMuxTailInfo): 2, 4 and 6 on the section-pipelined cascade (biquad_row / biquad_row_i64 / biquad_pipe) and
  * the MFMA FIR (fir_tile); 3 and 5 -- float accumulators and the truncating dspMulFloatFloat -- on
  * chain_rows (a lane per chain and section) and fir_lane (a lane per chain and frame), with
  * chain_lane for single frames and cascades longer than 16 sections.  Any other core -- X/Y
@@ -351,6 +352,21 @@ int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *lo
  * dspRuntimeFirTailInfo is host-only, nothing runs on the GPU: the handed FIR chains among the chains of the core this process runs
  * (dspRuntimeSetShard) and how many of them have a delay.  A core the interpreter runs reports zeros. */
 int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *of_them_delayed);
+
+/* All of the above in a core with LOAD_MUX chain heads (opt-in: dspRuntimeSetOption("mux_tail", 1); default 0, every core then takes
+ * the path and is refused with the text it always had).  The option lifts the "no LOAD_MUX" rule of "chain_finish", "chain_delay" and
+ * "fir_tail" and replaces none of them: a dressed finish or a head TPDF_CALC still needs "chain_finish" 1, a DSP_DELAY "chain_delay" 1,
+ * anything behind a FIR "fir_tail" 1 (formats 4 and 6).  In formats 2, 4 and 6 every chain of a core with LOAD_MUX chains -- whatever
+ * its own head: LOAD_MUX, LOAD or LOAD_GAIN -- may then be what those options lower anywhere else, and the core may begin with a
+ * TPDF_CALC.  A LOAD_MUX chain with sections or a FIR goes through the kernels those chains take elsewhere, from its column of the
+ * stage's scratch block; one with neither is finished by the mux stage itself from the full accumulator (a dressed finish, no delay)
+ * or handed to chain_tail as 64-bit accumulators (a delay) -- the TAIL forms of mux_tile and mux_plain, which only a plan with such a
+ * chain launches.  Everything else those options refuse stays refused with its text; one check is new (-8): no delay line may share a
+ * word of the state area with a LOAD_MUX result word.
+ * dspRuntimeMuxTailInfo is host-only, nothing runs on the GPU: among the chains of the core this process runs (dspRuntimeSetShard),
+ * if the core holds LOAD_MUX heads, those with a dressed finish, those with a delay, and the LOAD_MUX chains the stage finishes or hands
+ * over itself.  A core without LOAD_MUX heads and a core the interpreter runs report zeros. */
+int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *delayed_chains, int *stage_finished_or_handed);
 
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
