@@ -117,6 +117,7 @@ typedef struct avdsp_ctx {
     int             opt_chain_finish;                      /* "chain_finish": dressed SAT0DB finishes and a head TPDF_CALC lowered to the chain kernels (default 0) */
     int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
     int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
+    int             opt_chain_mem;                         /* "chain_mem": STORE_MEM trunks and LOAD_MEM branches lowered to the chain kernels (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
 
@@ -330,6 +331,11 @@ static int set_option_here(const char *key, int value)
         G.opt_mux_tail = value;
         return replan();
     }
+    if (!strcmp(key, "chain_mem")) {                     /* STORE_MEM trunks and LOAD_MEM branches on the chain kernels; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "chain_mem: 0 or 1");
+        G.opt_chain_mem = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -435,6 +441,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
     if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
     if (!strcmp(key, "mux_tail"))     return G.opt_mux_tail;
+    if (!strcmp(key, "chain_mem"))    return G.opt_chain_mem;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -574,7 +581,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_fir_ahead = o->opt_fir_ahead; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail; c->opt_chain_mem = o->opt_chain_mem;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -724,9 +731,23 @@ typedef struct {
     int tpdf_calc, tpdf_calc_arg, tpdf_calc_word;         /* "chain_finish": the core begins with a DSP_TPDF_CALC; its width word and result word */
     int ndressed;                                         /* ... chains with a dressed finish */
     int ndelayed;                                         /* "chain_delay": chains with a DSP_DELAY */
+    int nmem;                                             /* "chain_mem": trunks and branches */
+    int *pread; int npread, cap_pread;                    /* ... program words [lo, hi) the core's opcodes read as parameters (pairs; kept under "chain_mem" only) */
 } lowered;
 
-static void lowered_free(lowered *L) { free(L->chains); free(L->coef_word); free(L->state_word); memset(L, 0, sizeof *L); }
+static void lowered_free(lowered *L) { free(L->chains); free(L->coef_word); free(L->state_word); free(L->pread); memset(L, 0, sizeof *L); }
+
+static int push_pread(lowered *L, long long lo, long long n)
+{
+    if (L->npread == L->cap_pread) {
+        int c = L->cap_pread ? 2 * L->cap_pread : 256;
+        int *q = (int *)realloc(L->pread, (size_t)c * 2 * sizeof *q);
+        if (!q) return -1;
+        L->pread = q; L->cap_pread = c;
+    }
+    L->pread[2 * L->npread] = (int)lo; L->pread[2 * L->npread + 1] = (int)(lo + n); L->npread++;
+    return 0;
+}
 
 static int push_chain(lowered *L, const avdsp_chain *c)
 {
@@ -776,6 +797,7 @@ static int check_independent(const lowered *L)
         if (outs[i] == outs[i - 1]) rc = fail(-8, "IO %d is stored by more than one chain of the core", outs[i]);
     for (int i = 0; i < L->nchains && !rc; i++) {
         const avdsp_chain *c = &L->chains[i];
+        if (c->load_mode == AVDSP_LOAD_MEM) continue;        /* (a branch loads no IO) */
         if (c->load_mode == AVDSP_LOAD_MUX) {                /* every IO the list names */
             for (int k = 0; k < c->mux_count && !rc; k++)
                 if (bsearch(&G.code[c->mux_word + 2 * k].i32, outs, (size_t)nout, sizeof(int), cmp_int))
@@ -804,9 +826,50 @@ static int dither_width_constant(void)
     return 1;
 }
 
+/* "chain_mem": the memory words of a lowered core against each other and against everything else the core reads.  Words sorted with
+ * their chains: two trunks of one word, words one apart, a branch in front of its trunk; then no word under a parameter some opcode
+ * of the core reads (a gain computed on the fly), no LOAD_MUX head and no FIR beside them */
+static int check_mem_words(const lowered *L)
+{
+    long long *w = (long long *)malloc((size_t)L->nmem * sizeof *w);      /* word << 32 | trunk << 31 ... sorted by word, trunks first */
+    if (!w) return fail(-9, "out of memory");
+    int k = 0, rc = 0;
+    for (int i = 0; i < L->nchains; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        if (c->load_mode == AVDSP_LOAD_MUX) { free(w); return fail(-8, "memory words beside LOAD_MUX heads are not lowered to the HIP path"); }
+        if (c->fir_taps) { free(w); return fail(-8, "memory words beside a chain with a DSP_FIR are not lowered to the HIP path"); }
+        if (c->mem_word) w[k++] = ((long long)c->mem_word << 32) | (c->mem_store ? 0 : 1ll << 31) | (long long)i;
+    }
+    qsort(w, (size_t)k, sizeof *w, cmp_ll);
+    int trunk = -1, trunk_word = -1;
+    for (int j = 0; j < k && !rc; j++) {
+        const int word = (int)(w[j] >> 32), is_branch = (int)(w[j] >> 31) & 1, chain = (int)(w[j] & 0x7FFFFFFF);
+        if (j && word == (int)(w[j - 1] >> 32) + 1)
+            rc = fail(-8, "memory words %d and %d of the core overlap without being the same word", word - 1, word);
+        else if (!is_branch && word == trunk_word) rc = fail(-8, "memory word %d is written by two STORE_MEM of the core", word);
+        else if (!is_branch) { trunk = chain; trunk_word = word; }
+        else if (word == trunk_word && chain < trunk)
+            rc = fail(-8, "memory word %d: a LOAD_MEM in front of the STORE_MEM of its word (the one-frame-lag form) is not lowered to the HIP path", word);
+        for (int q = 0; q < L->npread && !rc; q++)
+            if (word < L->pread[2 * q + 1] && word + 2 > L->pread[2 * q])
+                rc = fail(-8, "memory word %d is read as a parameter by another opcode of the core", word);
+    }
+    free(w);
+    return rc;
+}
+
 /* mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used (dspRuntimeMuxInfo tells it from the others) */
 static int lowered_has_mux(const lowered *L);
+static unsigned char *store_mem_map(void);
+static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_damaged, unsigned char **smap);
 static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damaged)
+{
+    unsigned char *smap = 0;                                 /* store_mem_map(), built at the first memory opcode under "chain_mem" */
+    const int rc = lower_core_body(format, core, L, mux_damaged, &smap);
+    free(smap);
+    return rc;
+}
+static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_damaged, unsigned char **smap)
 {
     int damaged_ = 0;
     if (!mux_damaged) mux_damaged = &damaged_;
@@ -826,6 +889,9 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
     const int fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
     /* "mux_tail": all of that also behind a LOAD_MUX head and beside such chains */
     const int mux_tail = G.opt_mux_tail;
+    /* "chain_mem": STORE_MEM ends a trunk, LOAD_MEM opens a branch */
+    const int mem_on = G.opt_chain_mem;
+    int after_mem = 0;                                       /* the opcode before was a trunk's STORE_MEM: a chain head or the core's end must follow */
 
     if (ensure_encoding(format)) return g_err_code;
 
@@ -842,9 +908,57 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
 #define LC_NEED(n) do { if ((unsigned)(1 + (n)) > skip) return fail(-8, "word %d: opcode payload shorter than %d words", at, (n)); } while (0)
 #define LC_PROG(off, n) do { long long lo_ = (long long)at + (off); if (lo_ < 0 || lo_ + (n) > prog_words) \
             return fail(-8, "word %d: program offset %d (+%d) outside the program", at, (int)(off), (int)(n)); } while (0)
+        if (after_mem && op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) {
+            if (op == DSP_BIQUADS) return fail(-8, "word %d: a STORE_MEM in front of the banks or between two banks is not lowered to the HIP path", at);
+            if (op != DSP_LOAD && op != DSP_LOAD_GAIN && op != DSP_LOAD_MEM && op != DSP_LOAD_MUX)
+                return fail(-8, "word %d: a STORE_MEM that is not the last opcode of its chain is not lowered to the HIP path", at);
+            after_mem = 0;
+        }
         switch (op) {
         case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:
             break;
+        case DSP_LOAD_MEM_DATA:
+            if (!mem_on) goto not_lowered;
+            return fail(-8, "word %d: LOAD_MEM_DATA is not lowered to the HIP path (of the memory opcodes only LOAD_MEM and STORE_MEM are)", at);
+        case DSP_LOAD_MEM: case DSP_STORE_MEM: {              /* :750-766, "chain_mem" */
+            if (!mem_on) goto not_lowered;
+            if (format != 2 && format != 4 && format != 6) return fail(-8, "word %d: a memory word is not lowered to the HIP path in format %d", at, format);
+            if (G.ninst > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the program has instances", at);
+            if (G.shard_world > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the core is sharded", at);
+            LC_NEED(1);
+            LC_PROG(a[0], 2);
+            if (!*smap && !(*smap = store_mem_map())) return fail(-9, "out of memory");
+            for (int k = 0; k < 2; k++)
+                if ((*smap)[at + a[0] + k] != 1)
+                    return fail(-8, "word %d: %s target (word %d) is not a free word of a PARAM section: it would "
+                                    "rewrite %s", at, op == DSP_STORE_MEM ? "STORE_MEM" : "LOAD_MEM", at + a[0] + k,
+                                (*smap)[at + a[0] + k] ? "a count, IO number or length other opcodes rely on" : "the opcode stream");
+            if (op == DSP_LOAD_MEM) {
+                if (open) {
+                    if (cur.n_out == 0)
+                        return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
+                    if (push_chain(L, &cur)) return fail(-9, "out of memory");
+                }
+                memset(&cur, 0, sizeof cur);
+                open = 1; fir_op = 0;
+                cur.sec_base = L->nsec;
+                cur.load_mode = AVDSP_LOAD_MEM;
+                cur.mem_word = at + a[0];
+                L->nmem++;
+                break;
+            }
+            if (!open) return fail(-8, "word %d: STORE_MEM without a LOAD", at);
+            if (cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a memory word in a chain with a LOAD_MUX head is not lowered to the HIP path", at);
+            if (cur.load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a STORE_MEM in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
+            if (fir_op) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
+            if (cur.n_out || cur.sat || cur.delay_slot)
+                return fail(-8, "word %d: a STORE_MEM behind a STORE, a SAT0DB or a DSP_DELAY is not lowered to the HIP path", at);
+            cur.mem_word = at + a[0]; cur.mem_store = 1;
+            if (push_chain(L, &cur)) return fail(-9, "out of memory");
+            memset(&cur, 0, sizeof cur);
+            open = 0; fir_op = 0; after_mem = 1;
+            L->nmem++;
+            break; }
         case DSP_LOAD:                                        /* :565-583 */
         case DSP_LOAD_GAIN:                                   /* :586-607 */
             LC_NEED(op == DSP_LOAD_GAIN ? 2 : 1);
@@ -862,6 +976,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (op == DSP_LOAD_GAIN) {
                 cur.load_mode = AVDSP_LOAD_GAIN;
                 cur.gain_bits = p[a[1]].u32;
+                if (mem_on && push_pread(L, (long long)at + a[1], 1)) return fail(-9, "out of memory");
             }
             break;
         case DSP_LOAD_MUX: {                                  /* :871-897: a chain head like LOAD, the accumulator a weighted sum of inputs */
@@ -880,6 +995,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
                 return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
             *mux_damaged = 0;
+            if (mem_on && push_pread(L, (long long)at + a[0], 1 + 2 * n)) return fail(-9, "out of memory");
             if (open) {
                 if (cur.n_out == 0)
                     return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
@@ -906,6 +1022,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             LC_PROG(a[1], G.biquad_offset + (num - 1) * dspBiquadFreqSkip + 5);
             if (a[0] < 0 || (long long)a[0] + 6ll * num > dspHeaderPtr->dataSize)
                 return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[0], 6 * num, dspHeaderPtr->dataSize);
+            if (mem_on && push_pread(L, (long long)at + a[1], G.biquad_offset + (num - 1) * dspBiquadFreqSkip + 5)) return fail(-9, "out of memory");
             if (bank[1].i32 != 0)                             /* 0 = bypass, :837 */
                 for (int s = 0; s < num; s++)
                     if (push_section(L, (int)(bank - G.code) + G.biquad_offset + s * dspBiquadFreqSkip,
@@ -919,6 +1036,8 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                                 : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
             if (!open || cur.n_out || cur.sat)
                 return fail(-8, "word %d: FIR outside the supported chain order", at);
+            if (open && cur.load_mode == AVDSP_LOAD_MEM)
+                return fail(-8, "word %d: a DSP_FIR in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
             if (!float_alu)
                 return fail(-8, "word %d: DSP_FIR in int64 mode is undefined behaviour in the reference "
                                 "(dsp_firSTD.h:8-35) and is not provided", at);
@@ -933,6 +1052,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                     return fail(-8, "word %d: FIR pure-delay variant is not lowered yet", at);
                 if (length > 0) {
                     LC_PROG(off, 1 + length);
+                    if (mem_on && push_pread(L, (long long)at + off, 1 + length)) return fail(-9, "out of memory");
                     if (a[G.num_freq] < 0 || (long long)a[G.num_freq] + length > dspHeaderPtr->dataSize)
                         return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[G.num_freq], length, dspHeaderPtr->dataSize);
                     if (cur.fir_taps) return fail(-8, "word %d: more than one FIR per chain", at);
@@ -968,6 +1088,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
             cur.delay_slot = cur.sat ? AVDSP_DELAY_B : AVDSP_DELAY_A;
             cur.delay_word = prog_words + a[1];
             cur.delay_us_word = a[2] ? at + a[2] : 0;
+            if (mem_on && a[2] && push_pread(L, (long long)at + a[2], 1)) return fail(-9, "out of memory");
             cur.delay_max = a[0];
             L->ndelayed++;
             break; }
@@ -982,6 +1103,7 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
                 LC_NEED(1);
                 LC_PROG(a[0], 1);
                 cur.finish_gain_bits = p[a[0]].u32;
+                if (mem_on && push_pread(L, (long long)at + a[0], 1)) return fail(-9, "out of memory");
             }
             cur.sat = 1;
             L->ndressed++;
@@ -1016,6 +1138,10 @@ static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damage
 #undef LC_NEED
 #undef LC_PROG
     if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
+    if (L->nmem) {
+        const int rc = check_mem_words(L);
+        if (rc) return rc;
+    }
     if ((L->ndressed || L->tpdf_calc) && !mux_tail && lowered_has_mux(L))
         return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
     if (L->ndelayed && !mux_tail && lowered_has_mux(L))
@@ -1744,6 +1870,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* (as lower_core_ex checked the lines' extents) */
         d.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
         d.mux_tail = G.opt_mux_tail;
+        d.chain_mem = G.opt_chain_mem;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -2061,6 +2188,40 @@ int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *
     return 0;
 }
 
+/* Host-only: what "chain_mem" makes of the core -- its trunks (chains that end in STORE_MEM), its branches (chains that start with
+ * LOAD_MEM) and, of those, the ones whose word no chain of the core writes: they read what the mirror holds when a launch starts
+ * (DESIGN.md 4.2j).  No device is touched.  A core that is not a set of chains has none. */
+int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int nt = 0, nb = 0, nc = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0 && L.nmem) {
+            for (int i = 0; i < L.nchains; i++) {
+                const avdsp_chain *c = &L.chains[i];
+                if (c->mem_store) nt++;
+                if (c->load_mode != AVDSP_LOAD_MEM) continue;
+                nb++;
+                int written = 0;
+                for (int j = 0; j < L.nchains && !written; j++) written = L.chains[j].mem_store && L.chains[j].mem_word == c->mem_word;
+                nc += !written;
+            }
+        }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (trunks) *trunks = nt;
+    if (branches) *branches = nb;
+    if (constant_branches) *constant_branches = nc;
+    return 0;
+}
+
 /* Host-only: which chains of the core this process runs under the current dspRuntimeSetShard, and the IO numbers
  * they load and store -- what the block call's windows must cover, so a host can cut its column slice of a
  * [frames][channels] block for ANY loaded program.  total == 0: not a chain core (it runs whole on every rank). */
@@ -2081,7 +2242,7 @@ int dspRuntimeShardInfo(int format, opcode_t *core, int *total_chains, int *firs
             shard_range(tot, G.shard_world, G.shard_rank, &lo, &hi);
             for (int i = lo; i < hi; i++) {
                 const avdsp_chain *c = &L.chains[i];
-                for (int k = 0; k < (c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : 1); k++) {      /* (a LOAD_MUX head: every IO of its list) */
+                for (int k = 0; k < (c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : c->load_mode == AVDSP_LOAD_MEM ? 0 : 1); k++) {      /* (a LOAD_MUX head: every IO of its list; a LOAD_MEM branch: none) */
                     const int io = c->load_mode == AVDSP_LOAD_MUX ? G.code[c->mux_word + 2 * k].i32 : c->in_io;
                     if (imax < imin || io < imin) imin = io;
                     if (imax < imin || io > imax) imax = io;
@@ -2880,7 +3041,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail || G.opt_chain_mem) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

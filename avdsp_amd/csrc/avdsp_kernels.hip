@@ -3564,6 +3564,73 @@ __global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a)
     }
 }
 
+/* ------------------------------------------------------------------------------------------
+ * mem_stage<FMT> ("chain_mem"): DSP_STORE_MEM / DSP_LOAD_MEM (dsp_runtime.c:750-766) between a trunk and its branches.
+ * On the call's stream, behind the trunks' cascades (HAND forms: every frame's whole accumulator in the trunk's row of the hand-over
+ * block) and in front of the branches' cascades, which read their column of the branch block with kLoadRaw.
+ *
+ * A workgroup takes one tile of trees (avdsp_plan_layout.h, mem_trees: up to kMemTileTrees trees, whose columns are consecutive) and
+ * kMemFrames frames.  First a wave per tree, a lane per frame: the accumulator from the tree's source -- the row ([row][1024 frames] x
+ * 8 bytes: a wave reads 512 consecutive bytes), load_stage of the sample (a trunk without sections), or the mirror's word (no trunk in
+ * this core: constant through the launch) -- then narrow_stage of it into LDS, the branches without sections that the stage finishes
+ * itself (store_stage / finish_stage on all 64 bits, as passthrough), the row chain_tail reads for such branches with a delay line where
+ * no cascade has filled one, and the last frame's accumulator into the memory word, as two 32-bit stores (the word may sit at an odd
+ * index).  Then, behind a barrier, the tile's columns of the branch block ([frame][column] x 4 bytes) from LDS with the column as the
+ * fastest index: consecutive lanes store consecutive words.  LDS rows are kMemFrames + 1 words apart, so that the lanes of one frame,
+ * which read different trees, fall into different banks.  The stage never reads a memory word it writes: a word with a trunk is only
+ * written, a word without one only read.
+ * ---------------------------------------------------------------------------------------- */
+struct MemArgs {
+    int *buf;
+    const MemTree *trees; const MemOwn *own; const MemTile *tiles; const int *col_tree;
+    unsigned long long *hand;              /* [hand_row][kFirChunk frames] accumulators */
+    const unsigned long long *addend;      /* the dither addend of every frame of this launch (dither_block); null: no dressed chain */
+    unsigned *scratch; int scratch_stride; /* the branch block */
+    BlockIO io;
+};
+template <int FMT>
+__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgs a)
+{
+    using alu_t = typename Alu<FMT>::type;
+    if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
+    __shared__ unsigned s_word[kMemTileTrees][kMemFrames + 1];
+    const MemTile tile = a.tiles[blockIdx.x];
+    const int f0 = (int)blockIdx.y * kMemFrames, nf = min(kMemFrames, a.io.nframes - f0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int tl = wave; tl < tile.ntree; tl += kBlock / 64) {
+        const MemTree tr = a.trees[tile.tree0 + tl];
+        if (lane >= nf) continue;
+        const int f = f0 + lane;
+        unsigned long long u;
+        alu_t X;
+        if (tr.src == kMemSrcSample) {
+            X = load_stage<FMT>(a.io.in[(size_t)f * a.io.in_stride + (tr.in_io - a.io.in_base)], tr.load_mode, tr.gain_bits);
+            if constexpr (FMT == 2) u = (unsigned long long)X; else u = (unsigned long long)__double_as_longlong(X);
+        } else {
+            if (tr.src == kMemSrcRow) u = a.hand[(size_t)tr.row * kFirChunk + f];
+            else u = (unsigned long long)(unsigned)a.buf[tr.word] | ((unsigned long long)(unsigned)a.buf[tr.word + 1] << 32);
+            if constexpr (FMT == 2) X = (long long)u; else X = __longlong_as_double((long long)u);
+        }
+        s_word[tl][lane] = narrow_stage<FMT>(X);
+        if (tr.src != kMemSrcRow && tr.row >= 0) a.hand[(size_t)tr.row * kFirChunk + f] = u;
+        for (int k = 0; k < tr.n_own; k++) {
+            const MemOwn o = a.own[tr.first_own + k];
+            const unsigned word = o.finish ? finish_stage<FMT>(X, o.finish, o.gain_bits, a.addend[f], a.io.store_mask)
+                                           : store_stage<FMT>(X, o.sat, a.io.store_mask);
+#pragma unroll
+            for (int q = 0; q < AVDSP_MAX_STORES; q++)
+                if (q < o.n_out) a.io.out[(size_t)f * a.io.out_stride + (o.out_io[q] - a.io.out_base)] = word;
+        }
+        if (tr.trunk >= 0 && f == a.io.nframes - 1) { a.buf[tr.word] = (int)(unsigned)u; a.buf[tr.word + 1] = (int)(unsigned)(u >> 32); }
+    }
+    __syncthreads();
+    const int total = tile.ncol * nf;
+    for (int i = threadIdx.x; i < total; i += kBlock) {
+        const int f = i / tile.ncol, c = i - f * tile.ncol;
+        a.scratch[(size_t)(f0 + f) * a.scratch_stride + tile.col0 + c] = s_word[a.col_tree[tile.col0 + c] - tile.tree0][f];
+    }
+}
+
 /* One wave per block call, on the call's stream ahead of the cascades: the core's DSP_TPDF_CALC over the whole block (has_calc: what
  * tpdf_walk does -- the generator frame by frame, a first frame that finds another dither width only installs the new one, the
  * result word, the globals written back), and every frame's addend into table[frame].  A core without the opcode dithers with the
@@ -4367,7 +4434,8 @@ struct Plan {
                    std::vector<Group> pieces; DevArr<unsigned> d_scratch[2];
                    bool raw_out = false;         /* a piece but the last: it stores its last section's result word as it is (biquad_row<4> can) */
                    bool wide = false;            /* chains with a dressed finish: biquad_pipe's WIDE form (GroupLayout::wide) */
-                   bool hand = false; };         /* chains with a delay line: biquad_pipe's HAND form (GroupLayout::hand) */
+                   bool hand = false;            /* chains with a delay line: biquad_pipe's HAND form (GroupLayout::hand) */
+                   int phase = 0; };             /* "chain_mem": 1: branches, launched behind mem_stage on the branch block (GroupLayout::phase) */
     /* the rows of ALL the plan's 16-lane groups in one table (CascadeLayout::all_rows) for ONE biquad_row launch instead of one per section
      * count: nsec 0 in its arguments (every wave takes its rows' count from their records), no ids.  n 0: not made */
     Group rows_all;
@@ -4416,6 +4484,12 @@ struct Plan {
     int n_mux_stored = 0;                                /* chains the stage stores itself (no filter behind the head) */
     int n_mux_finished = 0, n_mux_handed = 0;            /* "mux_tail": of those, the ones with a dressed finish; chains whose accumulator the stage hands to chain_tail
                                                             (either makes the stage's launches the TAIL forms) */
+    /* memory words ("chain_mem"): mem_stage between the trunks' cascades (groups of phase 0, with everything else) and
+     * the branches' (phase 1), which read d_mem_scratch, [1024 frames][n_mem_cols] words */
+    bool has_mem = false;
+    DevArr<MemTree> d_mem_trees; DevArr<MemOwn> d_mem_own; DevArr<MemTile> d_mem_tiles; DevArr<int> d_mem_col_tree;
+    DevArr<unsigned> d_mem_scratch;
+    int n_mem_tiles = 0, n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
     DevArr<int> d_lane_rows; int n_lane_rows = 0;        /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
@@ -5243,7 +5317,7 @@ static int ahead_streams_apart(avdsp_hip_prog *prog, hipStream_t stream)
  * `st` -- the block's FIR, the caller's next kernel -- is ordered behind all of them.  `last_stop`: an event the caller wants on the
  * cascades' completion (the overlap mode's ev_bq): recorded behind the join. */
 template <int FMT>
-int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, hipStream_t st, hipEvent_t last_stop, bool with_ready)
+int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, hipStream_t st, hipEvent_t last_stop, bool with_ready, int phase = -1)
 {
     /* (i) every cascade of up to 16 sections in ONE biquad_row launch, whatever their lengths (the table of all rows, Plan::rows_all):
      * 1024 chains with 1 .. 8 sections 248 -> 33 us.  (ii) what that does not cover -- 17 sections and more, or the options that take
@@ -5264,7 +5338,8 @@ int launch_cascades(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl,
         return 0;
     };
     std::vector<const Plan::Group *> todo;
-    for (auto &g : pl.bq) if (!(merged && g.P == 16 && g.d_rows)) todo.push_back(&g);
+    /* (`phase`, "chain_mem": the groups of that phase only -- such a plan has no table of all rows; -1: every group) */
+    for (auto &g : pl.bq) if (!(merged && g.P == 16 && g.d_rows) && (phase < 0 || g.phase == phase)) todo.push_back(&g);
     if (merged) {
         const Plan::Group &m = pl.rows_all;
         if (launch_biquad<FMT>(prog, pl, m, nullptr, m.n, io, biquad_impl, st, todo.empty() ? last_stop : nullptr, with_ready)) return -1;
@@ -5330,6 +5405,22 @@ int launch_mux(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
         hipLaunchKernelGGL((mux_plain<FMT, TAIL>), dim3((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 1 << 16)), dim3(kBlock), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+/* the memory-word stage of a launch ("chain_mem"), on the caller's stream between the two phases of cascades */
+template <int FMT>
+int launch_mem(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
+{
+    if (!pl.n_mem_tiles) return 0;
+    ProfileScope scope(prog, stream, AVDSP_KERNEL_MUX); scope.begin();
+    if (!pl.d_mem_trees || !pl.d_mem_tiles || (pl.n_mem_cols && (!pl.d_mem_scratch || !pl.d_mem_col_tree))) return set_err("a memory-word stage without its tables");
+    MemArgs a{};
+    a.buf = prog->d_buf; a.trees = pl.d_mem_trees; a.own = pl.d_mem_own; a.tiles = pl.d_mem_tiles; a.col_tree = pl.d_mem_col_tree;
+    a.hand = pl.d_hand; a.addend = prog->d_addend ? prog->d_addend + pl.block_f0 : nullptr;
+    a.scratch = pl.d_mem_scratch; a.scratch_stride = pl.n_mem_cols; a.io = io;
+    hipLaunchKernelGGL(mem_stage<FMT>, dim3((unsigned)pl.n_mem_tiles, (unsigned)((io.nframes + kMemFrames - 1) / kMemFrames)), dim3(kBlock), 0, stream, a);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -5512,6 +5603,14 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         }
         prog->ev_fir_set[slot] = true;
         prog->blk++;
+    } else if (pl.has_mem) {
+        /* ("chain_mem": the trunks' cascades and the ordinary chains' on the caller's block, joined; the stage; the branches' cascades on the
+         * branch block, joined.  Such a plan has no FIR) */
+        if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false, 0)) return -1;
+        if (launch_mem<FMT>(prog, pl, io, stream)) return -1;
+        BlockIO bio = io;
+        bio.in = pl.d_mem_scratch; bio.in_stride = pl.n_mem_cols; bio.in_base = 0;
+        if (pl.n_mem_cols && launch_cascades<FMT>(prog, pl, bio, biquad_impl, stream, nullptr, false, 1)) return -1;
     } else {
         if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false)) return -1;
         /* (a plan with handed FIR chains: the plain ones have a list of their own; else it is every FIR chain, as ever) */
@@ -5841,7 +5940,7 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
 /* device copies of a launch group's tables */
 static int upload_group(Plan::Group &g, const GroupLayout &l)
 {
-    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out; g.wide = l.wide; g.hand = l.hand;
+    g.P = l.P; g.nsec = l.nsec; g.n = l.n; g.all_fir = l.all_fir; g.raw_out = l.raw_out; g.wide = l.wide; g.hand = l.hand; g.phase = l.phase;
     return g.d_ids.upload(l.ids) || g.d_rows.upload(l.rows) || g.d_lanes.upload(l.lanes);
 }
 
@@ -5863,6 +5962,7 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         if (copy_to_caller(words.data(), prog->d_buf + t.mux_lo, words.size() * 4)) return -1;
         STAGE(mux_records(words, t));
     }
+    if (t.has_mem) STAGE(mem_trees(d, buf_words, t));
     STAGE(check_chains(d, buf_words, t));
     Plan pl;
     pl.format = d->format; pl.nchains = d->nchains; pl.store_mask = d->store_mask;
@@ -5905,12 +6005,13 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         pl.n_fir_hand = (int)t.fir_hand.size();
         if (pl.d_fir_hand.upload(t.fir_hand) || pl.d_fir_plain.upload(t.fir_plain)) return -1;
     }
-    if (!t.tail.empty()) {
+    if (!t.tail.empty() || t.has_mem) {
         /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece; a handed FIR chain's row is
          * filled by its FIR, and one without a delay gets the record of a line of 0 samples in front of its slot: chain_tail bypasses
          * such a line -- nothing read, nothing written -- and runs the slot's opcode and the STOREs) */
         /* (the rows are check_chains': a cascade, a FIR -- or, "mux_tail", the mux stage -- fills them) */
         std::vector<int> hand_row(L.dev_chains.size(), -1);
+        for (int i = 0; i < d->nchains; i++) if (t.mem_kind[i] == 1) hand_row[i] = t.hand_row[i];      /* ("chain_mem": a trunk's cascade hands over to mem_stage) */
         std::vector<DelayRec> tail;
         const int rows = t.n_hand_rows;
         for (int i : t.tail) {
@@ -5994,6 +6095,12 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
             const bool done = hipDeviceSynchronize() == hipSuccess;
             if (!launched || !done) return set_err("mux_gains_to_f64 failed");
         }
+    }
+    if (t.has_mem) {
+        pl.has_mem = true; pl.n_mem_tiles = (int)t.mem_tiles.size(); pl.n_mem_cols = t.n_mem_cols;
+        pl.n_mem_trunks = t.n_mem_trunks; pl.n_mem_branches = t.n_mem_branches; pl.n_mem_constant = t.n_mem_constant;
+        if (pl.d_mem_trees.upload(t.mem_tree_list) || pl.d_mem_own.upload(t.mem_own) || pl.d_mem_tiles.upload(t.mem_tiles) || pl.d_mem_col_tree.upload(t.mem_col_tree)) return -1;
+        if (t.n_mem_cols && pl.d_mem_scratch.alloc((size_t)kFirChunk * t.n_mem_cols) != hipSuccess) return set_err("hipMalloc(branch block of %d columns)", t.n_mem_cols);
     }
     if (pl.overlap_ok) {                                  /* ready words, all at launch number 0 */
         if (pl.d_ready.alloc((size_t)d->nchains) != hipSuccess ||
@@ -6499,11 +6606,12 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         /* (a plan with LOAD_MUX chains: its cascades and their replays read the stage's scratch columns, never the caller's input -- but
          * chains the stage stores itself are stored while other workgroups of the stage still read the frame) */
         prog->call_in_place = i0 < o1 && o0 < i1;          /* ("fir_ahead": such a call is never staged, launch_all) */
-        const bool direct = pl.has_mux ? pl.n_mux_stored > 0 : pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
+        const bool direct = pl.has_mem ? true : pl.has_mux ? pl.n_mux_stored > 0 : pl.format != 2 && (pl.lane_mode || (!pl.bq.empty() && !pl.overlap_ok));
         /* (one-frame calls of the other plans go without the copy.  Not those of a mux plan: its stage is many waves over that ONE frame,
          * every chain reads columns that other chains store, and a wave of another workgroup -- in mux_plain of the same one -- may
          * still walk its list when the first stores.  dspRuntime_N is not in place: its windows are two blocks of the library's own.) */
-        if (direct && (nframes > 1 || pl.has_mux) && i0 < o1 && o0 < i1) {
+        /* (nor those of a plan with memory words: mem_stage reads a trunk's sample behind the first phase's stores) */
+        if (direct && (nframes > 1 || pl.has_mux || pl.has_mem) && i0 < o1 && o0 < i1) {
             const size_t words = (size_t)nframes * in_stride;
             /* one copy buffer per caller's stream: a buffer is only ever written and read in that stream's order (two in-place calls on
              * different streams used to share one -- a race); growing one waits for its own stream, not for the device */

@@ -8,6 +8,7 @@
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads; which chains the
  *                      stage stores, finishes or hands over itself ("mux_tail")
+ *     mem_trees        (plans with trunks or AVDSP_LOAD_MEM branches, "chain_mem") the trees, their hand-over rows, the columns of the branch block, mem_stage's tiles
  *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `fir_hand`, `pass` and `tail` lists
  *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
@@ -63,6 +64,26 @@ struct MuxTile {
     long long g64;                   /* the gains as doubles, mulop(gain): [nrec][kpad] from here, zeros behind `count` */
 };
 
+/* "chain_mem" (DESIGN.md 4.2j): a tree is one memory word, the trunk that writes it (or none: the word is constant through a launch)
+ * and the branches that read it.  mem_stage takes the accumulator of every frame from `src` and fans it out */
+constexpr int kMemFrames = 64;       /* frames per mem_stage workgroup */
+constexpr int kMemTileTrees = 16;    /* trees per mem_stage workgroup at most ... */
+constexpr int kMemTileCols = 64;     /* ... and a tile is closed once it holds this many columns (one tree may bring more) */
+enum { kMemSrcRow = 0, kMemSrcSample = 1, kMemSrcWord = 2 };
+struct MemTree {
+    int word;                        /* the first of the two mirror words */
+    int src;                         /* kMemSrcRow: the trunk's hand-over row; kMemSrcSample: a trunk without sections, load_stage of its sample;
+                                        kMemSrcWord: no trunk in this plan, the word as the mirror holds it when the launch starts */
+    int trunk;                       /* the trunk's chain, -1: none */
+    int row;                         /* kMemSrcRow: the row read.  Else: a row the stage FILLS for chain_tail (branches without sections but with a
+                                        delay line), -1: no such branch */
+    int in_io, load_mode; unsigned gain_bits;      /* kMemSrcSample: the trunk's head */
+    int col0, ncol;                  /* scratch columns of its branches with sections: [col0, col0 + ncol), in branch order */
+    int first_own, n_own;            /* MemOwn records of the branches the stage finishes and stores itself */
+};
+struct MemOwn { int tree, cid, sat, finish; unsigned gain_bits; int n_out, out_io[AVDSP_MAX_STORES]; };
+struct MemTile { int tree0, ntree, col0, ncol; };
+
 inline std::string text(const char *fmt, ...)
 {
     char b[512];
@@ -106,6 +127,19 @@ struct ChainTables {
      * the accumulators in the hand-over block for chain_tail.  `fir` holds every chain with a FIR, they among them (rings, taps, history);
      * `fir_plain` those that store themselves */
     std::vector<int> fir_hand, fir_plain;
+    /* "chain_mem" (DESIGN.md 4.2j), made by mem_trees: the trees, the columns of the branch block, the branches the stage stores itself.
+     * A branch with sections is a kLoadRaw chain of its column (phase 2: its cascade reads the branch block, not the caller's samples);
+     * trunks and ordinary chains stay on the caller's block (phase 1) */
+    bool has_mem = false;
+    std::vector<char> mem_kind;          /* per chain: 0 ordinary, 1 trunk, 2 branch */
+    std::vector<char> mem_stored;        /* branches without sections and without a delay line: the stage finishes and stores them */
+    std::vector<int> mem_row;            /* per chain: the hand-over row mem_trees gave it (a trunk with sections: its own; a branch without
+                                            sections but with a delay line: its tree's), else -1 */
+    std::vector<MemTree> mem_tree_list;
+    std::vector<MemOwn> mem_own;
+    std::vector<MemTile> mem_tiles;
+    std::vector<int> mem_col_tree;       /* per column of the branch block: its tree */
+    int n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
 };
 
 inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
@@ -115,13 +149,22 @@ inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, Ch
     t.state.assign(d->sec_state_word, d->sec_state_word + d->nsections);
     t.mux_stored.assign(d->nchains, 0);
     t.mux_handed.assign(d->nchains, 0);
+    t.mem_kind.assign(d->nchains, 0); t.mem_stored.assign(d->nchains, 0); t.mem_row.assign(d->nchains, -1);
     for (int i = 0; i < d->nsections; i++)
         if (t.coef[i] < 0 || t.coef[i] + 5 > buf_words || t.state[i] < 0 || t.state[i] + 6 > buf_words || (t.state[i] & 1))
             return text("section %d addresses words outside the loaded buffer", i);
     for (int i = 0; i < d->nchains; i++) {
         const int m = t.chains[i].load_mode;
-        if (m != AVDSP_LOAD_PLAIN && m != AVDSP_LOAD_GAIN && m != AVDSP_LOAD_MUX) return text("chain %d: load mode %d", i, m);
+        const bool mem = d->chain_mem && (m == AVDSP_LOAD_MEM || (t.chains[i].mem_store && (m == AVDSP_LOAD_PLAIN || m == AVDSP_LOAD_GAIN)));
+        if (m != AVDSP_LOAD_PLAIN && m != AVDSP_LOAD_GAIN && m != AVDSP_LOAD_MUX && !mem) return text("chain %d: load mode %d", i, m);
+        if (t.chains[i].mem_store && !mem) return text("chain %d: a memory word has no kernel here", i);
         t.has_mux = t.has_mux || m == AVDSP_LOAD_MUX;
+        t.has_mem = t.has_mem || mem;
+    }
+    if (t.has_mem) {
+        if (d->format != 2 && d->format != 4 && d->format != 6) return text("memory words have no kernels in format %d", d->format);
+        if (d->instances > 1) return "memory words have no chain instances";
+        if (t.has_mux) return "memory words beside LOAD_MUX chains have no kernels";
     }
     if (!t.has_mux) return "";
     if (d->format == 3 || d->format == 5) return text("LOAD_MUX chains have no kernels in format %d", d->format);
@@ -169,6 +212,83 @@ inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
     return "";
 }
 
+/* "chain_mem" (DESIGN.md 4.2j), behind check_heads in a plan with trunks or branches: the trees in program order (those with a trunk
+ * first, then the words nobody here writes), every word index against the buffer, the hand-over rows the stage reads or fills, the
+ * columns of the branch block -- consecutive within a tree -- and mem_stage's tiles.  A branch with sections becomes a kLoadRaw chain of
+ * its column, as the chains of a LOAD_MUX plan do */
+inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
+{
+    const int n = (int)t.chains.size();
+    auto word_ok = [&](int w) { return w >= 1 && (long long)w + 2 <= buf_words; };
+    auto find_tree = [&](int w, int *exact) {
+        *exact = -1;
+        for (size_t k = 0; k < t.mem_tree_list.size(); k++) {
+            const int o = t.mem_tree_list[k].word;
+            if (o == w) *exact = (int)k; else if (o == w - 1 || o == w + 1) return false;
+        }
+        return true;
+    };
+    std::vector<int> tree_of(n, -1);
+    for (int i = 0; i < n; i++) if (t.chains[i].fir_taps) return text("chain %d: a FIR beside memory words has no kernel", i);
+    for (int i = 0; i < n; i++) {
+        const avdsp_chain &c = t.chains[i];
+        if (!c.mem_store) continue;
+        if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || c.fir_taps || c.in_io < 0) return text("chain %d: not a trunk", i);
+        if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
+        int exact;
+        if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
+        if (exact >= 0) return text("chain %d: a second trunk of memory word %d", i, c.mem_word);
+        MemTree tr{};
+        tr.word = c.mem_word; tr.trunk = i; tr.src = c.nsec ? kMemSrcRow : kMemSrcSample;
+        tr.row = c.nsec ? t.n_hand_rows++ : -1;
+        tr.in_io = c.in_io; tr.load_mode = c.load_mode; tr.gain_bits = c.gain_bits;
+        t.mem_kind[i] = 1; t.mem_row[i] = tr.row; t.n_mem_trunks++;
+        t.mem_tree_list.push_back(tr);
+    }
+    for (int i = 0; i < n; i++) {
+        const avdsp_chain &c = t.chains[i];
+        if (c.load_mode != AVDSP_LOAD_MEM) continue;
+        if (c.mem_store || c.fir_taps || c.n_out < 1) return text("chain %d: not a branch", i);
+        if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
+        int exact;
+        if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
+        if (exact >= 0 && t.mem_tree_list[exact].trunk > i) return text("chain %d: a branch in front of its trunk", i);
+        if (exact < 0) {
+            MemTree tr{};
+            tr.word = c.mem_word; tr.trunk = -1; tr.src = kMemSrcWord; tr.row = -1;
+            exact = (int)t.mem_tree_list.size();
+            t.mem_tree_list.push_back(tr);
+        }
+        tree_of[i] = exact; t.mem_kind[i] = 2; t.n_mem_branches++;
+        t.n_mem_constant += t.mem_tree_list[exact].trunk < 0;
+    }
+    /* the branches tree by tree: columns, the stage's own stores, the rows it fills */
+    std::vector<std::vector<int>> members(t.mem_tree_list.size());
+    for (int i = 0; i < n; i++) if (tree_of[i] >= 0) members[tree_of[i]].push_back(i);
+    for (size_t k = 0; k < t.mem_tree_list.size(); k++) {
+        MemTree &tr = t.mem_tree_list[k];
+        tr.col0 = t.n_mem_cols; tr.first_own = (int)t.mem_own.size();
+        for (int i : members[k]) {
+            avdsp_chain &c = t.chains[i];
+            c.load_mode = kLoadRaw; c.in_io = 0;
+            if (c.nsec) { c.in_io = t.n_mem_cols++; t.mem_col_tree.push_back((int)k); }
+            else if (c.delay_slot) { if (tr.row < 0) tr.row = t.n_hand_rows++; t.mem_row[i] = tr.row; }
+            else {
+                MemOwn o{};
+                o.tree = (int)k; o.cid = i; o.sat = c.sat; o.finish = c.finish; o.gain_bits = c.finish_gain_bits; o.n_out = c.n_out;
+                for (int q = 0; q < AVDSP_MAX_STORES; q++) o.out_io[q] = c.out_io[q];
+                t.mem_own.push_back(o); t.mem_stored[i] = 1;
+            }
+        }
+        tr.ncol = t.n_mem_cols - tr.col0; tr.n_own = (int)t.mem_own.size() - tr.first_own;
+        if (t.mem_tiles.empty() || t.mem_tiles.back().ntree == kMemTileTrees || t.mem_tiles.back().ncol >= kMemTileCols)
+            t.mem_tiles.push_back(MemTile{(int)k, 0, tr.col0, 0});
+        t.mem_tiles.back().ntree++; t.mem_tiles.back().ncol += tr.ncol;
+    }
+    (void)d;
+    return "";
+}
+
 inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
 {
     const bool fir_tail = d->fir_tail && (d->format == 4 || d->format == 6);
@@ -177,12 +297,13 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
     for (int i = 0; i < d->nchains; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return text("chain %d: bad section range", i);
-        if (c.n_out < 1 || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return text("chain %d: bad IO", i);
-        if (!t.has_mux) { t.io_in_min = std::min(t.io_in_min, c.in_io); t.io_in_max = std::max(t.io_in_max, c.in_io); }
+        if ((c.n_out < 1 && t.mem_kind[i] != 1) || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return text("chain %d: bad IO", i);
+        if (!t.has_mux && t.mem_kind[i] != 2) { t.io_in_min = std::min(t.io_in_min, c.in_io); t.io_in_max = std::max(t.io_in_max, c.in_io); }
         for (int k = 0; k < c.n_out; k++) {
             if (c.out_io[k] < 0) return text("chain %d: bad IO", i);
             t.io_out_min = std::min(t.io_out_min, c.out_io[k]); t.io_out_max = std::max(t.io_out_max, c.out_io[k]);
         }
+        if (t.mem_kind[i] == 1) { t.hand_row[i] = t.mem_row[i]; continue; }      /* (a trunk, "chain_mem": its cascade hands over to mem_stage, nothing else follows) */
         if (c.fir_taps) {
             if (d->format == 2) return text("chain %d: FIR has no int64 definition", i);
             if (c.fir_coef_word < 0 || c.fir_coef_word + c.fir_taps > buf_words ||
@@ -214,9 +335,10 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
         if (c.delay_slot || handed) {
             t.tail.push_back(i);
             if (c.nsec || c.fir_taps || t.mux_handed[i]) t.hand_row[i] = t.n_hand_rows++;
+            else if (t.mem_row[i] >= 0) t.hand_row[i] = t.mem_row[i];      /* (a branch without sections: its tree's row, shared with its siblings) */
             continue;
         }
-        if (!c.nsec && !c.fir_taps && !t.mux_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
+        if (!c.nsec && !c.fir_taps && !t.mux_stored[i] && !t.mem_stored[i]) (c.finish ? t.pass_dressed : t.pass).push_back(i);
     }
     if (d->tpdf_calc) {
         if ((d->format != 2 && d->format != 4 && d->format != 6) || mux_refused || d->instances > 1) return "a head TPDF_CALC has no kernel here";
@@ -233,6 +355,7 @@ struct GroupLayout {
     bool raw_out = false;                /* a piece but the last: it stores its last section's result word as it is */
     bool hand = false;                   /* (with wide) its chains have a delay line: the launch hands every frame's accumulator to chain_tail
                                             instead of finishing it (biquad_pipe's HAND form) */
+    int phase = 0;                       /* "chain_mem": 1: branches, launched behind mem_stage with the branch block as their input; 0: everything else */
     bool wide = false;                   /* its chains have a dressed finish or a delay line: the launch keeps the last section's whole accumulator per frame
                                             (biquad_pipe's WIDE form; no biquad_row records).  Of a long cascade only the last piece is */
     std::vector<int> ids;                /* the chains' records in `dev_chains` */
@@ -278,9 +401,11 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
         /* dressed chains: launch groups of their own, next to the others; delayed chains (dressed or not): again groups of their own.
          * Not the cascade of a handed FIR chain ("fir_tail"): delay and finish stand behind its FIR, the cascade feeds the ring like any */
         const bool fir = t.chains[i].fir_taps != 0;
-        const bool hand = !fir && t.chains[i].delay_slot != 0, wide = hand || (!fir && t.chains[i].finish != 0);
-        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand; });
-        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; }
+        /* ("chain_mem": a trunk hands over like a delayed chain; branches are groups of their own, of the second phase) */
+        const int kind = t.has_mem ? t.mem_kind[i] : 0, phase = kind == 2 ? 1 : 0;
+        const bool hand = (!fir && t.chains[i].delay_slot != 0) || kind == 1, wide = hand || (!fir && t.chains[i].finish != 0);
+        auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand && g.phase == phase; });
+        if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; it->phase = phase; }
         it->ids.push_back(i);
     }
     for (GroupLayout &g : L.groups) {
@@ -302,7 +427,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
             int at = 0;
             for (int k = 0; k < np; k++) {
                 GroupLayout pg;
-                pg.nsec = base + (k < extra ? 1 : 0); pg.P = 16; pg.n = g.n;
+                pg.nsec = base + (k < extra ? 1 : 0); pg.P = 16; pg.n = g.n; pg.phase = g.phase;
                 pg.all_fir = k + 1 == np && g.all_fir; pg.raw_out = k + 1 < np;
                 pg.wide = k + 1 == np && g.wide; pg.hand = k + 1 == np && g.hand;
                 pg.ids.resize(g.n);
@@ -322,6 +447,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
             }
         } else if (g.P == 16 && !g.wide) {
             row_records(format, t.chains, t, g);
+            if (t.has_mem) continue;                         /* ("chain_mem": two phases with two input blocks -- no table of all rows) */
             /* ... and the same rows in the table of all lengths: this run, filled up to whole waves.  (An empty row is a copy of a real
              * one with no chain behind it: every lane of a wave FETCHES, section or not -- its input column must be one the block has;
              * nothing of it is stored) */
@@ -434,6 +560,7 @@ inline bool stores_whole_window(const ChainTables &t)
 inline bool overlap_ok(const ChainTables &t)
 {
     bool any = false;
+    if (t.has_mem) return false;                         /* ("chain_mem": trunks, the stage and the branches follow each other on the caller's stream) */
     if (!t.fir_hand.empty()) return false;               /* (a handed FIR chain: its tail follows its FIR on the caller's stream, the plan runs back to back) */
     for (const avdsp_chain &c : t.chains) { if (c.nsec && !c.fir_taps) return false; any = any || c.nsec; }
     return any && !t.fir.empty() && !t.has_mux;

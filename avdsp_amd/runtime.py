@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -135,6 +135,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "dspRuntimeMuxTailInfo"):          # (tools/muxtail_bench.py --parent loads a library from before the call)
             L.dspRuntimeMuxTailInfo.restype = i32
             L.dspRuntimeMuxTailInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "dspRuntimeMemInfo"):              # (tools/memtree_bench.py --parent loads a library from before the call)
+            L.dspRuntimeMemInfo.restype = i32
+            L.dspRuntimeMemInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -276,6 +279,13 @@ class Runtime:
         chain_tail itself), at the current shard."""
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeMuxTailInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
+        return (a.value, b.value, c.value)
+
+    def mem_info(self, core_index: int = 0):
+        """dspRuntimeMemInfo (host-only): in a core that "chain_mem" puts on the chain kernels, (trunks -- chains that end in STORE_MEM --,
+        branches -- chains that start with LOAD_MEM --, those of them whose word no chain of the core writes)."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeMemInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
         return (a.value, b.value, c.value)
 
     def tag_output(self, out: np.ndarray, column: int):

@@ -31,7 +31,7 @@ extern "C" {
 #define AVDSP_MAX_STORES 4
 
 /* how the accumulator is loaded at the head of a chain */
-enum { AVDSP_LOAD_PLAIN = 0, AVDSP_LOAD_GAIN = 1, AVDSP_LOAD_MUX = 3 };     /* (2 is taken inside the kernels: a raw word between two pieces) */
+enum { AVDSP_LOAD_PLAIN = 0, AVDSP_LOAD_GAIN = 1, AVDSP_LOAD_MUX = 3, AVDSP_LOAD_MEM = 4 };     /* (2 is taken inside the kernels: a raw word between two pieces) */
 
 /* One channel chain.  All *_word fields are absolute word indices into the caller's buffer
  * (program words first, state area from word `totalLength`).                                    */
@@ -60,6 +60,11 @@ typedef struct avdsp_chain {
     int32_t  delay_word;             /* the line in the mirror: its index word, the samples from the next word on */
     int32_t  delay_us_word;          /* program word of the 16-bit microsecond parameter, read at every launch; 0: the fixed form */
     int32_t  delay_max;              /* with a parameter: the line's size in samples (the delay is clamped to it); fixed form: microseconds */
+    /* memory words ("chain_mem", dsp_runtime.c:750-766): the first of the two PROGRAM words a DSP_STORE_MEM leaves the accumulator in and
+     * a DSP_LOAD_MEM takes it from.  0: none (word 0 is the header's).  A trunk -- LOAD | LOAD_GAIN, [BIQUADS], STORE_MEM -- has
+     * mem_store 1, n_out 0 and no sat / finish / delay; a branch has load_mode AVDSP_LOAD_MEM (in_io unused) and mem_store 0 */
+    int32_t  mem_word;
+    int32_t  mem_store;
 } avdsp_chain;
 enum { AVDSP_DELAY_NONE = 0, AVDSP_DELAY_A = 1, AVDSP_DELAY_B = 2 };      /* A: in front of the SAT0DB slot, B: behind it */
 enum { AVDSP_FINISH_NONE = 0, AVDSP_FINISH_TPDF = 1, AVDSP_FINISH_GAIN = 2, AVDSP_FINISH_TPDF_GAIN = 3 };      /* bit 0: dither, bit 1: gain */
@@ -96,6 +101,8 @@ typedef struct avdsp_plan_desc {
                                         whose FIR hands its accumulators to chain_tail; 0: such a chain is refused                */
     int32_t  mux_tail;               /* 1 ("mux_tail"): a plan with LOAD_MUX chains may hold chains with a finish or a delay_slot and a head TPDF_CALC
                                         (the stage finishes or hands over those without a filter behind the head); 0: such a plan is refused */
+    int32_t  chain_mem;              /* 1 ("chain_mem", formats 2, 4 and 6): the plan may hold trunks and AVDSP_LOAD_MEM branches (mem_stage between their
+                                        cascades); 0: such a chain is refused */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

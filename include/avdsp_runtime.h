@@ -368,6 +368,20 @@ int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *o
  * over itself.  A core without LOAD_MUX heads and a core the interpreter runs report zeros. */
 int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *delayed_chains, int *stage_finished_or_handed);
 
+/* "chain_mem" (dspRuntimeSetOption, 0 or 1, default 0): DSP_STORE_MEM and DSP_LOAD_MEM (dsp_runtime.c:750-766) on the chain
+ * kernels of formats 2, 4 and 6 -- the crossover's shape, one conditioned input feeding several ways.  A trunk is LOAD | LOAD_GAIN,
+ * [BIQUADS], STORE_MEM and has no STORE; a branch is LOAD_MEM and then whatever an ordinary chain may be behind its load, under the
+ * options that lower it ("chain_delay", "chain_finish").  A frame runs the trunk first, then its branches; ordinary chains and other
+ * trees may stand between them.  A branch of a word no chain of the core writes reads what the mirror holds when a launch starts (the
+ * writer core's last frame, or an uploaded parameter).  After a launch both program words of a trunk hold its accumulator of the last
+ * frame.  Refused with -8 and a text of its own, the core then on the interpreter as with 0: a STORE_MEM that is not its chain's last
+ * opcode, two STORE_MEM of one word, words that overlap, a LOAD_MEM in front of the STORE_MEM of its word, a word that another opcode
+ * reads as a parameter or that is no free PARAM word, a DSP_FIR or a LOAD_MUX head in or beside such chains, LOAD_MEM_DATA, formats 3
+ * and 5, instances, a set shard.
+ * dspRuntimeMemInfo is host-only, nothing runs on the GPU: the core's trunks, its branches, and the branches whose word no chain of
+ * the core writes.  A core without memory words and a core the interpreter runs report zeros. */
+int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches);
+
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
 /* Several programs in one process.  dspRuntimeInit(codePtr, ...) loads a program into a context of its own, keyed by the
