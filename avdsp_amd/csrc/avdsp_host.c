@@ -64,6 +64,7 @@ typedef struct {
     int         total_chains, first_chain;            /* chain cores: the core has total_chains, this process runs
                                                          [first_chain, first_chain + nchains) of them (dspRuntimeSetShard) */
     int         empty;                                /* chain core whose shard holds no chain: block calls do nothing */
+    int         ncopy;                                /* "chain_copy": live LOAD_STORE pairs of the plan (a chain plan even with total_chains 0) */
     core_deps   deps;
 } core_plan;
 
@@ -118,6 +119,7 @@ typedef struct avdsp_ctx {
     int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
     int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
     int             opt_chain_mem;                         /* "chain_mem": STORE_MEM trunks and LOAD_MEM branches lowered to the chain kernels (default 0) */
+    int             opt_chain_copy;                        /* "chain_copy": DSP_LOAD_STORE lists lowered to the chain kernels' side as one copy launch (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
 
@@ -336,6 +338,11 @@ static int set_option_here(const char *key, int value)
         G.opt_chain_mem = value;
         return replan();
     }
+    if (!strcmp(key, "chain_copy")) {                    /* DSP_LOAD_STORE lists beside the chains, one copy_pairs launch per block call; 0: such cores on the interpreter */
+        if (value != 0 && value != 1) return fail(-1, "chain_copy: 0 or 1");
+        G.opt_chain_copy = value;
+        return replan();
+    }
     if (!strcmp(key, "ring_wait")) {
         if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
         G.opt_ring_wait = value != 0;
@@ -442,6 +449,7 @@ int dspRuntimeGetOption(const char *key)
     if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
     if (!strcmp(key, "mux_tail"))     return G.opt_mux_tail;
     if (!strcmp(key, "chain_mem"))    return G.opt_chain_mem;
+    if (!strcmp(key, "chain_copy"))   return G.opt_chain_copy;
     if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
     if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
     if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
@@ -581,7 +589,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
         c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
         c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_fir_ahead = o->opt_fir_ahead; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail; c->opt_chain_mem = o->opt_chain_mem;
+        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail; c->opt_chain_mem = o->opt_chain_mem; c->opt_chain_copy = o->opt_chain_copy;
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -733,9 +741,20 @@ typedef struct {
     int ndelayed;                                         /* "chain_delay": chains with a DSP_DELAY */
     int nmem;                                             /* "chain_mem": trunks and branches */
     int *pread; int npread, cap_pread;                    /* ... program words [lo, hi) the core's opcodes read as parameters (pairs; kept under "chain_mem" only) */
+    /* "chain_copy" (DESIGN.md 4.2k): the DSP_LOAD_STORE pairs of the core.  While the core is walked, cp_sym[io] is the frame INPUT whose
+     * word slot `io` holds by now (-1: its own), cp_seen[] the slots a pair has ever given another word; at the end cp_src / cp_dst are
+     * the live pairs, sorted by destination */
+    int ncopy_written;                                    /* pairs as the program writes them */
+    int *cp_sym; unsigned char *cp_mark; int *cp_seen; int ncp_seen, cap_cp_seen;
+    int32_t *cp_src, *cp_dst; int ncopy;
 } lowered;
 
-static void lowered_free(lowered *L) { free(L->chains); free(L->coef_word); free(L->state_word); free(L->pread); memset(L, 0, sizeof *L); }
+static void lowered_free(lowered *L)
+{
+    free(L->chains); free(L->coef_word); free(L->state_word); free(L->pread);
+    free(L->cp_sym); free(L->cp_mark); free(L->cp_seen); free(L->cp_src); free(L->cp_dst);
+    memset(L, 0, sizeof *L);
+}
 
 static int push_pread(lowered *L, long long lo, long long n)
 {
@@ -784,17 +803,21 @@ static int cmp_int(const void *a, const void *b) { int x = *(const int *)a, y = 
  * of the same core stores, and no IO may be stored twice.                                       */
 static int check_independent(const lowered *L)
 {
-    int nout = 0;
+    int nout = L->ncopy;                                     /* ("chain_copy": a live pair's destination is a store, its source a load) */
     for (int i = 0; i < L->nchains; i++) nout += L->chains[i].n_out;
     int *outs = (int *)malloc((size_t)(nout ? nout : 1) * sizeof(int));
     if (!outs) return fail(-9, "out of memory");
     int k = 0;
     for (int i = 0; i < L->nchains; i++)
         for (int j = 0; j < L->chains[i].n_out; j++) outs[k++] = L->chains[i].out_io[j];
+    for (int i = 0; i < L->ncopy; i++) outs[k++] = L->cp_dst[i];
     qsort(outs, (size_t)nout, sizeof(int), cmp_int);
     int rc = 0;
     for (int i = 1; i < nout && !rc; i++)
         if (outs[i] == outs[i - 1]) rc = fail(-8, "IO %d is stored by more than one chain of the core", outs[i]);
+    for (int i = 0; i < L->ncopy && !rc; i++)
+        if (bsearch(&L->cp_src[i], outs, (size_t)nout, sizeof(int), cmp_int))
+            rc = fail(-8, "IO %d is both loaded and stored inside one core (cross-chain dependency)", L->cp_src[i]);
     for (int i = 0; i < L->nchains && !rc; i++) {
         const avdsp_chain *c = &L->chains[i];
         if (c->load_mode == AVDSP_LOAD_MEM) continue;        /* (a branch loads no IO) */
@@ -810,6 +833,101 @@ static int check_independent(const lowered *L)
 }
 
 #define GENERIC_IO_LIMIT 65536            /* IO numbers a program may use (the reference's hosts use well under 100) */
+
+/* "chain_copy": one pair (a -> b) of a DSP_LOAD_STORE list, in program order (dsp_runtime.c:738-747: samples[b] = samples[a]).  Slot b
+ * then holds the input word slot a held -- a's own, or the one an earlier pair left there (forwarding); whatever b held before is gone
+ * (the last writer wins); a slot that gets its own word back is as good as untouched.  -1: out of memory */
+static int copy_pair(lowered *L, int a, int b)
+{
+    if (!L->cp_sym) {
+        L->cp_sym = (int *)malloc(GENERIC_IO_LIMIT * sizeof(int));
+        L->cp_mark = (unsigned char *)calloc(GENERIC_IO_LIMIT, 1);
+        if (!L->cp_sym || !L->cp_mark) return -1;
+        for (int i = 0; i < GENERIC_IO_LIMIT; i++) L->cp_sym[i] = -1;
+    }
+    const int s = L->cp_sym[a] >= 0 ? L->cp_sym[a] : a;
+    L->cp_sym[b] = s == b ? -1 : s;
+    if (s != b && !L->cp_mark[b]) {
+        if (L->ncp_seen == L->cap_cp_seen) {
+            const int c = L->cap_cp_seen ? 2 * L->cap_cp_seen : 64;
+            int *q = (int *)realloc(L->cp_seen, (size_t)c * sizeof *q);
+            if (!q) return -1;
+            L->cp_seen = q; L->cap_cp_seen = c;
+        }
+        L->cp_mark[b] = 1;
+        L->cp_seen[L->ncp_seen++] = b;
+    }
+    return 0;
+}
+
+/* "chain_copy": the last writer of an IO wins among the chains of a core as it does among the pairs of a list (oktodac_diy.c:194-204
+ * stores both chains of its high way to the same two outputs).  No chain and no pair of a lowered core reads an IO a chain stores, so
+ * an earlier STORE of an IO that a later chain -- or the same chain -- stores again is dead: it is taken out of its chain.  A chain left
+ * without a STORE still has to run for its state; that is kept only where chain_tail finishes the chain (a DSP_DELAY: the line goes
+ * on, nothing is stored) -- the other kernels store a chain's first IO unasked */
+static int drop_dead_stores(lowered *L)
+{
+    unsigned char *seen = (unsigned char *)calloc(GENERIC_IO_LIMIT, 1);
+    if (!seen) return fail(-9, "out of memory");
+    int rc = 0;
+    for (int i = L->nchains - 1; i >= 0 && !rc; i--) {
+        avdsp_chain *c = &L->chains[i];
+        const int had = c->n_out;
+        int first_dead = -1;
+        for (int k = c->n_out - 1; k >= 0; k--) {
+            if (!seen[c->out_io[k]]) { seen[c->out_io[k]] = 1; continue; }
+            first_dead = c->out_io[k];
+            for (int j = k; j + 1 < c->n_out; j++) c->out_io[j] = c->out_io[j + 1];
+            c->out_io[--c->n_out] = 0;
+        }
+        if (had && !c->n_out && !c->delay_slot)
+            rc = fail(-8, "IO %d is stored by more than one chain of the core, and the earlier chain stores nothing else and has no DSP_DELAY: not lowered to the HIP path", first_dead);
+    }
+    free(seen);
+    return rc;
+}
+
+/* "chain_copy", behind the walk: the live pairs -- one per slot that ends the frame with another input's word, by destination -- and
+ * what they must not meet.  The copy runs beside the chains, from the caller's input block to its output block: a source is an input
+ * of the frame no chain stores, a destination (and every slot a pair wrote on the way, cp_seen) one no chain loads or stores, and no
+ * slot is both -- in an in-place call a lane would read what another writes */
+static int check_copies(lowered *L)
+{
+    if (!L->ncp_seen) return 0;
+    qsort(L->cp_seen, (size_t)L->ncp_seen, sizeof(int), cmp_int);
+    L->cp_src = (int32_t *)malloc((size_t)L->ncp_seen * sizeof(int32_t));
+    L->cp_dst = (int32_t *)malloc((size_t)L->ncp_seen * sizeof(int32_t));
+    if (!L->cp_src || !L->cp_dst) return fail(-9, "out of memory");
+    for (int i = 0; i < L->ncp_seen; i++) {
+        const int b = L->cp_seen[i];
+        if (L->cp_sym[b] < 0) continue;
+        L->cp_src[L->ncopy] = L->cp_sym[b]; L->cp_dst[L->ncopy] = b; L->ncopy++;
+    }
+    for (int i = 0; i < L->ncopy; i++)
+        if (L->cp_mark[L->cp_src[i]] && L->cp_sym[L->cp_src[i]] >= 0)
+            return fail(-8, "IO %d is both read and written by the LOAD_STORE pairs of the core: not lowered to the HIP path (in an in-place call two lanes would race)", L->cp_src[i]);
+    unsigned char *is_src = (unsigned char *)calloc(GENERIC_IO_LIMIT, 1);
+    if (!is_src) return fail(-9, "out of memory");
+    for (int i = 0; i < L->ncopy; i++) is_src[L->cp_src[i]] = 1;
+    int rc = 0;
+    for (int i = 0; i < L->nchains && !rc; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        for (int k = 0; k < c->n_out && !rc; k++) {
+            if (is_src[c->out_io[k]])
+                rc = fail(-8, "IO %d is stored by a chain of the core and read by a LOAD_STORE pair: a copy of a chain's output is not lowered to the HIP path", c->out_io[k]);
+            else if (L->cp_mark[c->out_io[k]])
+                rc = fail(-8, "IO %d is written by a LOAD_STORE pair and stored by a chain of the core: not lowered to the HIP path", c->out_io[k]);
+        }
+        const int nload = c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : c->load_mode == AVDSP_LOAD_MEM ? 0 : 1;
+        for (int k = 0; k < nload && !rc; k++) {
+            const int io = c->load_mode == AVDSP_LOAD_MUX ? G.code[c->mux_word + 2 * k].i32 : c->in_io;
+            if (L->cp_mark[io])
+                rc = fail(-8, "IO %d is written by a LOAD_STORE pair and loaded by a chain of the core: forwarding a pair into a chain is not lowered to the HIP path", io);
+        }
+    }
+    free(is_src);
+    return rc;
+}
 
 /* "chain_finish": the dither width of the program's globals is one constant -- every DSP_TPDF_CALC of every core asks for the default
  * (0, or its value).  Else a core elsewhere changes the store mask and the addend's scale between two blocks of a dressed core. */
@@ -891,6 +1009,8 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     const int mux_tail = G.opt_mux_tail;
     /* "chain_mem": STORE_MEM ends a trunk, LOAD_MEM opens a branch */
     const int mem_on = G.opt_chain_mem;
+    /* "chain_copy": DSP_LOAD_STORE lists beside the chains */
+    const int copy_on = G.opt_chain_copy;
     int after_mem = 0;                                       /* the opcode before was a trunk's STORE_MEM: a chain head or the core's end must follow */
 
     if (ensure_encoding(format)) return g_err_code;
@@ -908,7 +1028,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
 #define LC_NEED(n) do { if ((unsigned)(1 + (n)) > skip) return fail(-8, "word %d: opcode payload shorter than %d words", at, (n)); } while (0)
 #define LC_PROG(off, n) do { long long lo_ = (long long)at + (off); if (lo_ < 0 || lo_ + (n) > prog_words) \
             return fail(-8, "word %d: program offset %d (+%d) outside the program", at, (int)(off), (int)(n)); } while (0)
-        if (after_mem && op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) {
+        if (after_mem && op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL && !(copy_on && op == DSP_LOAD_STORE)) {      /* (a list ends nothing) */
             if (op == DSP_BIQUADS) return fail(-8, "word %d: a STORE_MEM in front of the banks or between two banks is not lowered to the HIP path", at);
             if (op != DSP_LOAD && op != DSP_LOAD_GAIN && op != DSP_LOAD_MEM && op != DSP_LOAD_MUX)
                 return fail(-8, "word %d: a STORE_MEM that is not the last opcode of its chain is not lowered to the HIP path", at);
@@ -917,6 +1037,19 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         switch (op) {
         case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:
             break;
+        case DSP_LOAD_STORE: {                                /* :738-747, "chain_copy": samples[out] = samples[in], pair by pair */
+            if (!copy_on) goto not_lowered;
+            if (G.ninst > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the program has instances", at);
+            if (G.shard_world > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the core is sharded", at);
+            if (open && cur.n_out == 0)
+                return fail(-8, "word %d: a LOAD_STORE list between a chain's LOAD and its first STORE is not lowered to the HIP path", at);
+            if (!(skip & 1)) return fail(-8, "word %d: a LOAD_STORE list of %u words is no list of pairs (damaged)", at, skip - 1);
+            for (unsigned k = 0; k + 1 < skip; k++)
+                if (a[k] < 0 || a[k] >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", at, a[k], GENERIC_IO_LIMIT);
+            for (unsigned k = 0; k + 2 < skip; k += 2)
+                if (copy_pair(L, a[k], a[k + 1])) return fail(-9, "out of memory");
+            L->ncopy_written += (int)(skip - 1) / 2;
+            break; }
         case DSP_LOAD_MEM_DATA:
             if (!mem_on) goto not_lowered;
             return fail(-8, "word %d: LOAD_MEM_DATA is not lowered to the HIP path (of the memory opcodes only LOAD_MEM and STORE_MEM are)", at);
@@ -1137,7 +1270,15 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     }
 #undef LC_NEED
 #undef LC_PROG
-    if (L->nchains == 0) return fail(-8, "core contains no LOAD..STORE chain");
+    if (copy_on && G.ninst <= 1 && G.shard_world <= 1) {
+        const int rc = drop_dead_stores(L);
+        if (rc) return rc;
+    }
+    if (L->ncp_seen) {
+        const int rc = check_copies(L);
+        if (rc) return rc;
+    }
+    if (L->nchains == 0 && L->ncopy == 0) return fail(-8, "core contains no LOAD..STORE chain");
     if (L->nmem) {
         const int rc = check_mem_words(L);
         if (rc) return rc;
@@ -1843,7 +1984,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
     core_plan *cp = &G.plans[G.nplans];
     cp->core = core; cp->format = format; cp->end_word = end_word; cp->skip_from = G.next_skip_from;
     cp->nchains = 0; cp->max_sections = 0; cp->max_taps = 0;
-    cp->total_chains = 0; cp->first_chain = 0; cp->empty = 0;
+    cp->total_chains = 0; cp->first_chain = 0; cp->empty = 0; cp->ncopy = 0;
     cp->deps = deps;
     if (chains) {
         /* this process's contiguous slice of the core's chains (dspRuntimeSetShard; the whole core when unsharded):
@@ -1851,13 +1992,14 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         int lo, hi;
         shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
         cp->total_chains = L.nchains; cp->first_chain = lo; cp->nchains = hi - lo;
-        if (hi == lo) {                                     /* more ranks than chains: nothing to do here */
+        cp->ncopy = L.ncopy;                                /* ("chain_copy": never under a shard; a core of pairs alone has no chain and is no empty shard) */
+        if (hi == lo && !L.ncopy) {                         /* more ranks than chains: nothing to do here */
             cp->empty = 1; cp->plan_id = -1;
             lowered_free(&L);
             G.nplans++;
             return cp;
         }
-        const int sec0 = L.chains[lo].sec_base;
+        const int sec0 = hi > lo ? L.chains[lo].sec_base : 0;
         const int sec1 = hi < L.nchains ? L.chains[hi].sec_base : L.nsec;
         for (int i = lo; i < hi; i++) L.chains[i].sec_base -= sec0;
         avdsp_plan_desc d;
@@ -1871,6 +2013,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
         d.mux_tail = G.opt_mux_tail;
         d.chain_mem = G.opt_chain_mem;
+        d.chain_copy = G.opt_chain_copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -2222,6 +2365,29 @@ int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, in
     return 0;
 }
 
+/* Host-only: what "chain_copy" makes of the core's DSP_LOAD_STORE lists -- the pairs the core writes and the pairs the
+ * plan copies once forwarding, the last writer and self-copies are resolved.  No device is touched.  A core without lists and a core
+ * the interpreter runs report zeros. */
+int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    int np = 0, nl = 0;
+    if (!G.opt_generic) {
+        lowered L;
+        const int rc = lower_core(format, core, &L);
+        if (rc == 0) { np = L.ncopy_written; nl = L.ncopy; }
+        lowered_free(&L);
+        if (rc && rc != -8) return rc;
+    }
+    if (pairs) *pairs = np;
+    if (live) *live = nl;
+    return 0;
+}
+
 /* Host-only: which chains of the core this process runs under the current dspRuntimeSetShard, and the IO numbers
  * they load and store -- what the block call's windows must cover, so a host can cut its column slice of a
  * [frames][channels] block for ANY loaded program.  total == 0: not a chain core (it runs whole on every rank). */
@@ -2251,6 +2417,12 @@ int dspRuntimeShardInfo(int format, opcode_t *core, int *total_chains, int *firs
                     if (omax < omin || c->out_io[k] < omin) omin = c->out_io[k];
                     if (omax < omin || c->out_io[k] > omax) omax = c->out_io[k];
                 }
+            }
+            for (int i = 0; i < L.ncopy; i++) {               /* ("chain_copy": the live pairs read and write the windows too) */
+                if (imax < imin || L.cp_src[i] < imin) imin = L.cp_src[i];
+                if (imax < imin || L.cp_src[i] > imax) imax = L.cp_src[i];
+                if (omax < omin || L.cp_dst[i] < omin) omin = L.cp_dst[i];
+                if (omax < omin || L.cp_dst[i] > omax) omax = L.cp_dst[i];
             }
         }
         lowered_free(&L);
@@ -2282,7 +2454,7 @@ static int takes_pieces(const core_plan *cp, int nframes, int in_stride, int in_
     /* (windows that share IO numbers used to make every launch deliver whole rows, one after the other, and such a call kept its core in one
      * piece; since the shared columns are copied in front of a call's launches -- show_through, avdsp_kernels.hip -- they are like any others) */
     (void)in_stride; (void)in_io_base; (void)out_stride; (void)out_io_base;
-    return cp->total_chains == 0 && G.opt_strand_split && nframes > 1;
+    return cp->total_chains == 0 && !cp->ncopy && G.opt_strand_split && nframes > 1;
 }
 
 int dspRuntimeBlockDevice(int format, opcode_t *core, int *rundata,
@@ -2815,7 +2987,7 @@ static int expand_core(int format, opcode_t *c, core_plan **cp, int *pn)
     if (!whole) return g_err_code;
     /* [prefix] + a run of identical strands up to the core's end: the run goes to lanes (strand_lower), the prefix -- usually the
      * TPDF_CALC -- stays a piece of the interpreter's, one level ahead */
-    if (G.opt_strand_split && G.opt_strand_lanes && whole->total_chains == 0) {
+    if (G.opt_strand_split && G.opt_strand_lanes && whole->total_chains == 0 && !whole->ncopy) {
         strand_plan S;
         int w = 0, core_end = 0;
         int rc = find_strand_run(format, begin, &w, &core_end, &S);
@@ -2853,7 +3025,7 @@ static int expand_core(int format, opcode_t *c, core_plan **cp, int *pn)
         }
         g_err[0] = 0;
     }
-    if (G.opt_strand_split && whole->total_chains == 0) ng = split_core(c, starts);
+    if (G.opt_strand_split && whole->total_chains == 0 && !whole->ncopy) ng = split_core(c, starts);
     if (ng > 1 && (G.nplans + ng + 8 > MAX_CORE_PLANS || n + ng + 8 > MAX_CORE_PLANS)) ng = 1;   /* plan table nearly full: whole */
     if (ng > 1) {
         /* Inside a core everything happens frame by frame: a later strand sees what an earlier one stored in
@@ -2889,7 +3061,7 @@ static int expand_core(int format, opcode_t *c, core_plan **cp, int *pn)
     typedef struct { int start, end, skip_from, skip_to; } piece_t;
     static piece_t pc[MAX_GROUPS + 2];
     int np = 0;
-    const int interpreted = whole->total_chains == 0 && !whole->empty && G.opt_strand_split;
+    const int interpreted = whole->total_chains == 0 && !whole->ncopy && !whole->empty && G.opt_strand_split;
     starts[ng] = dspHeaderPtr->totalLength;
     for (int g = 0; g < ng; g++) {
         const int ps = ng > 1 ? starts[g] : (int)(begin - G.code), pe = ng > 1 ? starts[g + 1] : dspHeaderPtr->totalLength;
@@ -3041,7 +3213,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail || G.opt_chain_mem) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail || G.opt_chain_mem || G.opt_chain_copy) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the
@@ -3136,6 +3308,10 @@ int dspRuntimeBlockAllInstancesDevice(int format, int *rundata, const void *d_in
                     if (L.chains[i].in_io < in_io_base || L.chains[i].in_io >= in_io_base + in_stride) rc = fail(-10, "input window IO [%d,%d) does not cover IO %d", in_io_base, in_io_base + in_stride, L.chains[i].in_io);
                     for (int o = 0; o < L.chains[i].n_out && !rc; o++)
                         if (L.chains[i].out_io[o] < out_io_base || L.chains[i].out_io[o] >= out_io_base + out_stride) rc = fail(-10, "output window IO [%d,%d) does not cover IO %d", out_io_base, out_io_base + out_stride, L.chains[i].out_io[o]);
+                }
+                for (int i = 0; i < L.ncopy && !rc; i++) {      /* ("chain_copy", one instance: the live pairs) */
+                    if (L.cp_src[i] < in_io_base || L.cp_src[i] >= in_io_base + in_stride) rc = fail(-10, "input window IO [%d,%d) does not cover IO %d", in_io_base, in_io_base + in_stride, L.cp_src[i]);
+                    else if (L.cp_dst[i] < out_io_base || L.cp_dst[i] >= out_io_base + out_stride) rc = fail(-10, "output window IO [%d,%d) does not cover IO %d", out_io_base, out_io_base + out_stride, L.cp_dst[i]);
                 }
                 lowered_free(&L);
                 if (!rc && avdsp_hip_run_block(G.dev, cp->plan_id, d_in, in_stride, in_io_base, d_out, out_stride, out_io_base,

@@ -3187,6 +3187,23 @@ __global__ __launch_bounds__(kBlock) void passthrough(const std::conditional_t<D
     }
 }
 
+/* DSP_LOAD_STORE lists ("chain_copy", dsp_runtime.c:738-747): samples[dst] = samples[src], the raw 32-bit word whatever
+ * the format -- no accumulator, no conversion, no store mask.  The host has resolved the lists' sequential meaning; what arrives are
+ * pairs with distinct destinations whose sources nothing of the plan writes (copy_list), so every (pair, frame) is independent.  A
+ * thread per (pair, frame), the pair the fastest index: the pairs are sorted by destination, so the lanes of a frame store -- and, where
+ * a list copies a run of IOs, load -- neighbouring words of one row, and a list shorter than a wave fills its wave with the next frames'
+ * rows.  One launch covers every frame of a block call */
+struct CopyArgs { const CopyPair *pairs; int npairs; BlockIO io; };
+__global__ __launch_bounds__(kBlock) void copy_pairs(const CopyArgs a)
+{
+    const long long total = (long long)a.npairs * a.io.nframes;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
+        const int slot = (int)(g % a.npairs), n = (int)(g / a.npairs);
+        const CopyPair p = a.pairs[slot];
+        a.io.out[(size_t)n * a.io.out_stride + (p.dst - a.io.out_base)] = a.io.in[(size_t)n * a.io.in_stride + (p.src - a.io.in_base)];
+    }
+}
+
 /* ------------------------------------------------------------------------------------------
  * LOAD_MUX chain heads (dsp_runtime.c:871-897): one stage in front of the cascades.
  *
@@ -4490,6 +4507,8 @@ struct Plan {
     DevArr<MemTree> d_mem_trees; DevArr<MemOwn> d_mem_own; DevArr<MemTile> d_mem_tiles; DevArr<int> d_mem_col_tree;
     DevArr<unsigned> d_mem_scratch;
     int n_mem_tiles = 0, n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
+    /* "chain_copy" (DESIGN.md 4.2k): the live pairs of the core's DSP_LOAD_STORE lists, by destination; copy_pairs once per block call */
+    DevArr<CopyPair> d_copy; int n_copy = 0;
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
     DevArr<int> d_lane_rows; int n_lane_rows = 0;        /* ... chain_rows' chains (1 .. 16 sections) */
     int n_lane_feed = 0;                                 /* ... chains that are a FIR alone (fir_lane_feed) */
@@ -5956,12 +5975,14 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     const long long buf_words = mirror_words(d, prog->total_words);
     ChainTables t;
     STAGE(check_heads(d, buf_words, t));
+    std::vector<int> words;                              /* (plans with LOAD_MUX chains: the mirror's words that hold their lists) */
     if (t.has_mux) {
-        std::vector<int> words((size_t)(t.mux_hi - t.mux_lo));
+        words.resize((size_t)(t.mux_hi - t.mux_lo));
         HIP_TRY(hipDeviceSynchronize());
         if (copy_to_caller(words.data(), prog->d_buf + t.mux_lo, words.size() * 4)) return -1;
-        STAGE(mux_records(words, t));
     }
+    STAGE(copy_list(d, words, t));
+    if (t.has_mux) STAGE(mux_records(words, t));
     if (t.has_mem) STAGE(mem_trees(d, buf_words, t));
     STAGE(check_chains(d, buf_words, t));
     Plan pl;
@@ -5971,6 +5992,8 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
     pl.has_mux = t.has_mux; pl.n_mux_stored = t.n_mux_stored; pl.n_mux_finished = t.n_mux_finished; pl.n_mux_handed = t.n_mux_handed; pl.max_taps = t.max_taps;
     pl.io_in_min = t.io_in_min; pl.io_in_max = t.io_in_max; pl.io_out_min = t.io_out_min; pl.io_out_max = t.io_out_max;
     if (pl.d_sec_coef.upload(t.coef) || pl.d_sec_state.upload(t.state)) return -1;
+    pl.n_copy = (int)t.copy.size();
+    if (pl.d_copy.upload(t.copy)) return -1;
     if (pl.lane_mode) {                                  /* no launch groups, no rings: chain_lane walks the chain list itself */
         pl.n_lane_fir = (int)t.fir.size();               /* (n_fir stays 0: that one counts chains with a ring) */
         std::vector<int> rows;
@@ -6611,7 +6634,10 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
          * every chain reads columns that other chains store, and a wave of another workgroup -- in mux_plain of the same one -- may
          * still walk its list when the first stores.  dspRuntime_N is not in place: its windows are two blocks of the library's own.) */
         /* (nor those of a plan with memory words: mem_stage reads a trunk's sample behind the first phase's stores) */
-        if (direct && (nframes > 1 || pl.has_mux || pl.has_mem) && i0 < o1 && o0 < i1) {
+        /* ("chain_copy": the pairs' sources and destinations are different IOs, which are different words of one block only while both
+         * windows have one geometry -- else copy_pairs too reads the copy) */
+        const bool pairs_meet = pl.n_copy > 0 && (in_io_base != out_io_base || in_stride != out_stride);
+        if (((direct && (nframes > 1 || pl.has_mux || pl.has_mem)) || pairs_meet) && i0 < o1 && o0 < i1) {
             const size_t words = (size_t)nframes * in_stride;
             /* one copy buffer per caller's stream: a buffer is only ever written and read in that stream's order (two in-place calls on
              * different streams used to share one -- a race); growing one waits for its own stream, not for the device */
@@ -6627,7 +6653,22 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
             d_in = al->buf;
         }
     }
+    if (pl.n_copy) {
+        /* "chain_copy": the live pairs of the core's LOAD_STORE lists over every frame of the call, on the caller's stream ahead of
+         * everything else of the plan -- from the block the chains read (the copy above, in an in-place call) into the caller's output */
+        ProfileScope scope(prog, (hipStream_t)stream, AVDSP_KERNEL_PASS); scope.begin();
+        CopyArgs a{};
+        a.pairs = pl.d_copy; a.npairs = pl.n_copy;
+        a.io.in = (const unsigned *)d_in;  a.io.in_stride = in_stride;   a.io.in_base = in_io_base;
+        a.io.out = (unsigned *)d_out;      a.io.out_stride = out_stride; a.io.out_base = out_io_base;
+        a.io.nframes = nframes; a.io.store_mask = -1;
+        const long long total = (long long)pl.n_copy * nframes;
+        const int grid = (int)std::min<long long>((total + kBlock - 1) / kBlock, 2048);
+        hipLaunchKernelGGL(copy_pairs, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
     if (pl.lane_mode) {
+        if (!pl.nchains) return 0;                       /* (a core of pairs alone) */
         ProfileScope scope(prog, (hipStream_t)stream, AVDSP_KERNEL_BIQUAD); scope.begin();
         LaneArgs a{};
         a.buf = prog->d_buf; a.chains = pl.d_chains; a.sec_coef = pl.d_sec_coef; a.sec_state = pl.d_sec_state; a.nchains = pl.nchains;
@@ -6700,6 +6741,7 @@ int avdsp_hip_run_block(avdsp_hip_prog *prog, int plan, const void *d_in, int in
         void *args[] = {&g, &buf, &has_calc, &arg, &word, &table, &nf};
         HIP_TRY(hipLaunchKernel(fn, dim3(1), dim3(64), args, 0, (hipStream_t)stream));
     }
+    if (!pl.nchains) return 0;                           /* (a core of pairs alone, "chain_copy": copy_pairs above was its launch) */
     for (int f0 = 0; f0 < nframes; f0 += kFirChunk) {
         pl.block_f0 = f0;
         BlockIO io;

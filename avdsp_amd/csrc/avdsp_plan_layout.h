@@ -8,6 +8,7 @@
  *     check_heads      section words, load modes, what LOAD_MUX chains refuse, the mirror words [lo, hi) that hold their lists
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads; which chains the
  *                      stage stores, finishes or hands over itself ("mux_tail")
+ *     copy_list        ("chain_copy") the live DSP_LOAD_STORE pairs against each other and against every IO the chains load and store; sorted by destination
  *     mem_trees        (plans with trunks or AVDSP_LOAD_MEM branches, "chain_mem") the trees, their hand-over rows, the columns of the branch block, mem_stage's tiles
  *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `fir_hand`, `pass` and `tail` lists
  *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
@@ -84,6 +85,10 @@ struct MemTree {
 struct MemOwn { int tree, cid, sat, finish; unsigned gain_bits; int n_out, out_io[AVDSP_MAX_STORES]; };
 struct MemTile { int tree0, ntree, col0, ncol; };
 
+/* "chain_copy" (DESIGN.md 4.2k): one live pair of the core's DSP_LOAD_STORE lists -- out[frame][dst] = in[frame][src], the raw word */
+struct CopyPair { int src, dst; };
+constexpr int kCopyIoLimit = 65536;  /* IO numbers of a pair: [0, kCopyIoLimit) */
+
 inline std::string text(const char *fmt, ...)
 {
     char b[512];
@@ -140,6 +145,9 @@ struct ChainTables {
     std::vector<MemTile> mem_tiles;
     std::vector<int> mem_col_tree;       /* per column of the branch block: its tree */
     int n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
+    /* "chain_copy" (DESIGN.md 4.2k), made by copy_list: the live pairs, sorted by destination (consecutive lanes of copy_pairs store
+     * consecutive words where the IOs are).  They count in the IO spans and in stores_whole_window */
+    std::vector<CopyPair> copy;
 };
 
 inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, ChainTables &t)
@@ -212,6 +220,45 @@ inline std::string mux_records(const std::vector<int> &words, ChainTables &t)
     return "";
 }
 
+/* "chain_copy" (DESIGN.md 4.2k), behind check_heads and in front of the stages that rewrite the chains' heads: the host has resolved
+ * the lists (forwarding, the last writer, self-copies); here the finished plan is held to what copy_pairs relies on, whoever made it.
+ * Every source is read from the caller's input block and every destination written to its output block while the chains run, so: the
+ * destinations pairwise distinct, no destination an IO a chain loads (`words`: the mirror's words [mux_lo, mux_hi), the LOAD_MUX
+ * lists) or stores, no source a destination or an IO a chain stores.  The pairs sorted by destination */
+inline std::string copy_list(const avdsp_plan_desc *d, const std::vector<int> &words, ChainTables &t)
+{
+    if (d->ncopy < 0 || (d->ncopy > 0 && (!d->copy_src || !d->copy_dst))) return "bad LOAD_STORE pair list";
+    if (d->ncopy && !d->chain_copy) return "LOAD_STORE pairs have no kernel here";
+    if (!d->ncopy) return "";
+    if (d->instances > 1) return "LOAD_STORE pairs have no chain instances";
+    std::vector<char> stored(kCopyIoLimit, 0), loaded(kCopyIoLimit, 0), dst(kCopyIoLimit, 0);
+    auto mark = [](std::vector<char> &v, int io) { if (io >= 0 && io < kCopyIoLimit) v[(size_t)io] = 1; };
+    for (const avdsp_chain &c : t.chains) {
+        for (int k = 0; k < c.n_out && k < AVDSP_MAX_STORES; k++) mark(stored, c.out_io[k]);
+        if (c.load_mode == AVDSP_LOAD_MUX)
+            for (int k = 0; k < c.mux_count; k++) mark(loaded, words[(size_t)(c.mux_word - t.mux_lo) + 2 * k]);
+        else if (c.load_mode != AVDSP_LOAD_MEM) mark(loaded, c.in_io);
+    }
+    t.copy.resize((size_t)d->ncopy);
+    for (int i = 0; i < d->ncopy; i++) {
+        const CopyPair p{d->copy_src[i], d->copy_dst[i]};
+        if (p.src < 0 || p.src >= kCopyIoLimit || p.dst < 0 || p.dst >= kCopyIoLimit) return text("pair %d: IO %d -> %d outside [0,%d)", i, p.src, p.dst, kCopyIoLimit);
+        if (dst[(size_t)p.dst]) return text("pair %d: IO %d is the destination of two pairs", i, p.dst);
+        if (loaded[(size_t)p.dst] || stored[(size_t)p.dst]) return text("pair %d: its destination IO %d is loaded or stored by a chain", i, p.dst);
+        if (stored[(size_t)p.src]) return text("pair %d: its source IO %d is stored by a chain", i, p.src);
+        dst[(size_t)p.dst] = 1;
+        t.copy[(size_t)i] = p;
+    }
+    for (int i = 0; i < d->ncopy; i++)
+        if (dst[(size_t)t.copy[(size_t)i].src]) return text("pair %d: its source IO %d is the destination of a pair", i, t.copy[(size_t)i].src);
+    std::sort(t.copy.begin(), t.copy.end(), [](const CopyPair &a, const CopyPair &b) { return a.dst < b.dst; });
+    for (const CopyPair &p : t.copy) {
+        t.io_in_min = std::min(t.io_in_min, p.src); t.io_in_max = std::max(t.io_in_max, p.src);
+        t.io_out_min = std::min(t.io_out_min, p.dst); t.io_out_max = std::max(t.io_out_max, p.dst);
+    }
+    return "";
+}
+
 /* "chain_mem" (DESIGN.md 4.2j), behind check_heads in a plan with trunks or branches: the trees in program order (those with a trunk
  * first, then the words nobody here writes), every word index against the buffer, the hand-over rows the stage reads or fills, the
  * columns of the branch block -- consecutive within a tree -- and mem_stage's tiles.  A branch with sections becomes a kLoadRaw chain of
@@ -248,7 +295,7 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.load_mode != AVDSP_LOAD_MEM) continue;
-        if (c.mem_store || c.fir_taps || c.n_out < 1) return text("chain %d: not a branch", i);
+        if (c.mem_store || c.fir_taps || (c.n_out < 1 && !(d->chain_copy && c.delay_slot))) return text("chain %d: not a branch", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
         int exact;
         if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
@@ -297,7 +344,9 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
     for (int i = 0; i < d->nchains; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.sec_base < 0 || c.nsec < 0 || c.sec_base + c.nsec > d->nsections) return text("chain %d: bad section range", i);
-        if ((c.n_out < 1 && t.mem_kind[i] != 1) || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return text("chain %d: bad IO", i);
+        /* ("chain_copy": a chain whose every STORE a later chain repeats keeps none -- only where chain_tail finishes it, for its line) */
+        const bool storeless = t.mem_kind[i] == 1 || (d->chain_copy && c.delay_slot && d->instances <= 1);
+        if ((c.n_out < 1 && !storeless) || c.n_out > AVDSP_MAX_STORES || c.in_io < 0) return text("chain %d: bad IO", i);
         if (!t.has_mux && t.mem_kind[i] != 2) { t.io_in_min = std::min(t.io_in_min, c.in_io); t.io_in_max = std::max(t.io_in_max, c.in_io); }
         for (int k = 0; k < c.n_out; k++) {
             if (c.out_io[k] < 0) return text("chain %d: bad IO", i);
@@ -548,10 +597,11 @@ inline int fir_groups_per_chunk(int max_taps)
 inline int ring_length(int max_taps) { return pow2ceil(max_taps + kRingAhead * kFirChunk + 16 * fir_groups_per_chunk(max_taps) + 16 * (kNG + 4) + 64); }
 /* doubles of a chain's row in the f64 copy of the taps */
 constexpr int taps64_pitch(int max_taps) { return (kTapsLead + max_taps + kTapsTail + 1) & ~1; }
-/* every IO of [io_out_min, io_out_max] is stored by some chain (check_independent, host: no IO is stored twice) */
+/* every IO of [io_out_min, io_out_max] is stored by some chain or is the destination of a live pair ("chain_copy": they are in the
+ * span, so they are in the count) (check_independent, host: no IO is stored twice) */
 inline bool stores_whole_window(const ChainTables &t)
 {
-    long long nout = 0;
+    long long nout = (long long)t.copy.size();
     for (const avdsp_chain &c : t.chains) nout += c.n_out;
     return t.io_out_max >= t.io_out_min && nout == (long long)t.io_out_max - t.io_out_min + 1;
 }

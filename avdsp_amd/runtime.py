@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeCopyInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -138,6 +138,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "dspRuntimeMemInfo"):              # (tools/memtree_bench.py --parent loads a library from before the call)
             L.dspRuntimeMemInfo.restype = i32
             L.dspRuntimeMemInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "dspRuntimeCopyInfo"):             # (tools/copy_bench.py --parent loads a library from before the call)
+            L.dspRuntimeCopyInfo.restype = i32
+            L.dspRuntimeCopyInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -287,6 +290,13 @@ class Runtime:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeMemInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
         return (a.value, b.value, c.value)
+
+    def copy_info(self, core_index: int = 0):
+        """dspRuntimeCopyInfo (host-only): in a core that "chain_copy" puts on the chain kernels, (the pairs its DSP_LOAD_STORE lists write,
+        the live pairs the plan copies -- forwarding, the last writer and self-copies resolved)."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeCopyInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):
         """dspRuntimeTagOutput on a host block [frames][out_stride] of int32, in place (linux/avdsp_plugin.c:133-137)."""

@@ -103,6 +103,13 @@ typedef struct avdsp_plan_desc {
                                         (the stage finishes or hands over those without a filter behind the head); 0: such a plan is refused */
     int32_t  chain_mem;              /* 1 ("chain_mem", formats 2, 4 and 6): the plan may hold trunks and AVDSP_LOAD_MEM branches (mem_stage between their
                                         cascades); 0: such a chain is refused */
+    /* "chain_copy" (dsp_runtime.c:738-747): the live pairs of the core's DSP_LOAD_STORE lists, resolved by the host -- every source an
+     * input of the frame, the destinations pairwise distinct, no IO both, none of them an IO a chain stores and no destination one a
+     * chain loads.  copy_pairs moves the raw sample word of every frame of a block call, once per call; nchains may then be 0 */
+    int32_t  chain_copy;             /* 1 ("chain_copy"): the plan may hold pairs; 0: pairs are refused */
+    int32_t  ncopy;
+    const int32_t *copy_src;         /* [ncopy]: IO read from the input window ... */
+    const int32_t *copy_dst;         /* [ncopy]: ... IO written in the output window */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

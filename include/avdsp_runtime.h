@@ -382,6 +382,22 @@ int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *
  * the core writes.  A core without memory words and a core the interpreter runs report zeros. */
 int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches);
 
+/* "chain_copy" (dspRuntimeSetOption, 0 or 1, default 0): DSP_LOAD_STORE lists (dsp_runtime.c:738-747, samples[out] =
+ * samples[in] pair by pair: the raw 32-bit word, no accumulator, no conversion, no store mask) in a core of chains, formats 2 to 6 --
+ * in front of a head TPDF_CALC, between chains, behind a trunk's STORE_MEM, behind the last chain, or alone in a core.  The host
+ * resolves the list's sequential meaning: a pair that reads an earlier pair's destination takes that pair's source, of two writers of
+ * one IO the last wins, a pair that ends as a -> a is dropped.  What is left -- the live pairs -- is copied from the input window to the
+ * output window by one launch per block call, beside the chains.  Refused with -8 and a text of its own, the core then on the
+ * interpreter as with 0: a list between a chain's LOAD and its first STORE, a list of odd length, an IO number out of range, a pair
+ * that reads an IO a chain of the core stores, a pair that writes an IO a chain of the core loads or stores, an IO that is source and
+ * destination of live pairs, instances, a set shard.  Both windows of a block call must cover the live pairs' IOs
+ * (dspRuntimeShardInfo's spans include them).  By the same reading, with the option on two chains of a core may STORE one IO: the
+ * last one's words arrive, the earlier STORE is dropped (a chain left without any is lowered only where it has a DSP_DELAY, whose line
+ * goes on; else -8 with its text).
+ * dspRuntimeCopyInfo is host-only, nothing runs on the GPU: the pairs the core writes and the live pairs.  A core without lists and a
+ * core the interpreter runs report zeros. */
+int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live);
+
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
 /* Several programs in one process.  dspRuntimeInit(codePtr, ...) loads a program into a context of its own, keyed by the
