@@ -14,6 +14,7 @@
 #include "avdsp_hip.h"
 
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -275,134 +276,156 @@ static int replan(void)
     return 0;
 }
 
+/* ---- the options: one row per key.  dspRuntimeSetOption, dspRuntimeGetOption, the defaults a program starts from
+ * (dspRuntimeInit) and the replay onto a fresh device copy (ensure_device) all walk this table; a new option is a row here and an int
+ * in avdsp_ctx.  The rows of the options the device library holds stand in the order ensure_device sends them. ---- */
+enum { OPT_HOST,        /* an int of the context */
+       OPT_REPLAN,      /* ... that changes how cores are lowered: replan() */
+       OPT_DEV,         /* ... that the device copy holds too, under AVDSP_OPT_*: pushed when there is one, replayed onto a fresh one */
+       OPT_DEV_RO,      /* read from the device copy; `def` without one */
+       OPT_CTX_RO };    /* read from the context */
+enum { REPLAY_NEVER, REPLAY_ALWAYS, REPLAY_IF_SET /* (the "was set" companion) */, REPLAY_CHANGED /* differs from the built-in `def` */ };
+enum { OF_BOOL = 1,          /* stores value != 0 (the device gets the value as it came) */
+       OF_INVERTED = 2,      /* stores !value, reads back !stored */
+       OF_WRITE_ONLY = 4,    /* reads as -1, like an unknown key */
+       OF_SAYS_READ_ONLY = 8, /* a read-only key that says so when it is set (the others are unknown options there) */
+       OF_AT_LEAST_1 = 16 }; /* replayed as 1 while it is below */
+enum { HOOK_NONE, HOOK_DEVICE, HOOK_PROFILE, HOOK_READY_TIMEOUTS, HOOK_RATE_STATIC, HOOK_TIMING_PAIRS };
+typedef struct {
+    const char *key;
+    int         kind;
+    size_t      off, set_off;        /* the int in avdsp_ctx (0: none); its "was set" companion: reads -1 until set (0: none) */
+    int         dev_key;             /* AVDSP_OPT_* */
+    const char *range_text;          /* lo <= value <= hi, else -1 with this text (0: any value) */
+    int         lo, hi;
+    int         flags, hook, replay, def;
+} option_row;
+#define SLOT(f) offsetof(avdsp_ctx, f)
+#define ZERO_OR_ONE(k) .range_text = k ": 0 or 1", .lo = 0, .hi = 1
+#define DEV_RO(k, id, without) { k, OPT_DEV_RO, .dev_key = id, .def = without }
+static const option_row g_options[] = {
+    { "fir_impl",     OPT_HOST, .off = SLOT(opt_fir_impl) },
+    { "biquad_impl",  OPT_HOST, .off = SLOT(opt_biquad_impl) },
+    { "device",       OPT_HOST, .off = SLOT(opt_device), .hook = HOOK_DEVICE },               /* ... and the GPU is chosen again */
+    { "profile",      OPT_HOST, .off = SLOT(opt_profile), .hook = HOOK_PROFILE },             /* avdsp_hip_profile_enable */
+    { "generic",      OPT_REPLAN, .off = SLOT(opt_generic) },
+    { "interp_impl",  OPT_REPLAN, .off = SLOT(opt_interp_impl) },
+    { "strand_split", OPT_REPLAN, .off = SLOT(opt_strand_split) },
+    { "strand_lanes", OPT_REPLAN, .off = SLOT(opt_strand_lanes) },
+    /* what the chain lowering takes (lower_gates); 0: such cores on the interpreter.  DESIGN.md 4.2f (SAT0DB_TPDF / _GAIN / _TPDF_GAIN
+     * and a head TPDF_CALC), 4.2g (one DSP_DELAY behind a chain's banks), 4.2h (both behind a DSP_FIR), 4.2i (all of it in cores with
+     * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call) */
+    { "chain_finish", OPT_REPLAN, .off = SLOT(opt_chain_finish), ZERO_OR_ONE("chain_finish") },
+    { "chain_delay",  OPT_REPLAN, .off = SLOT(opt_chain_delay),  ZERO_OR_ONE("chain_delay") },
+    { "fir_tail",     OPT_REPLAN, .off = SLOT(opt_fir_tail),     ZERO_OR_ONE("fir_tail") },
+    { "mux_tail",     OPT_REPLAN, .off = SLOT(opt_mux_tail),     ZERO_OR_ONE("mux_tail") },
+    { "chain_mem",    OPT_REPLAN, .off = SLOT(opt_chain_mem),    ZERO_OR_ONE("chain_mem") },
+    { "chain_copy",   OPT_REPLAN, .off = SLOT(opt_chain_copy),   ZERO_OR_ONE("chain_copy") },
+    /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it: what
+     * dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
+    { "rate_count_static", OPT_HOST, .hook = HOOK_RATE_STATIC, .flags = OF_WRITE_ONLY },
+    /* launch arrangement of the chain kernels, in ensure_device's order */
+    { "profile_stride", OPT_DEV, .off = SLOT(opt_profile_stride), .dev_key = AVDSP_OPT_PROFILE_STRIDE, .range_text = "profile_stride: every n-th launch, n >= 1", .lo = 1, .hi = 0x7FFFFFFF,
+      .flags = OF_WRITE_ONLY | OF_AT_LEAST_1, .replay = REPLAY_ALWAYS },
+    { "overlap",      OPT_DEV, .off = SLOT(opt_overlap),     .dev_key = AVDSP_OPT_OVERLAP,     .replay = REPLAY_ALWAYS },
+    { "fir_rows",     OPT_DEV, .off = SLOT(opt_fir_rows),    .dev_key = AVDSP_OPT_FIR_ROWS,    .replay = REPLAY_ALWAYS },
+    { "ready_words",  OPT_DEV, .off = SLOT(opt_ready_words), .dev_key = AVDSP_OPT_READY_WORDS, .replay = REPLAY_ALWAYS },
+    { "lane_hw",      OPT_DEV, .off = SLOT(opt_lane_hw),     .dev_key = AVDSP_OPT_LANE_HW,     .replay = REPLAY_ALWAYS },
+    { "fir_split",    OPT_DEV, .off = SLOT(opt_fir_split),   .dev_key = AVDSP_OPT_FIR_SPLIT,   .replay = REPLAY_ALWAYS },
+    { "fir_launch",   OPT_DEV, .off = SLOT(opt_fir_launch), .set_off = SLOT(opt_fir_launch_set), .dev_key = AVDSP_OPT_FIR_LAUNCH, .replay = REPLAY_IF_SET },
+    { "fir_lean",     OPT_DEV, .off = SLOT(opt_fir_lean), .set_off = SLOT(opt_fir_lean_set),     .dev_key = AVDSP_OPT_FIR_LEAN,   .replay = REPLAY_IF_SET },
+    { "ring_wait",    OPT_DEV, .off = SLOT(opt_ring_wait),   .dev_key = AVDSP_OPT_RING_WAIT, .flags = OF_BOOL, .replay = REPLAY_ALWAYS },
+    /* staged FIR launches under "overlap" 1 */
+    { "fir_ahead",    OPT_DEV, .off = SLOT(opt_fir_ahead),   .dev_key = AVDSP_OPT_FIR_AHEAD, .range_text = "fir_ahead: -1 (by plan), 0 (never) or 1 (whenever it is legal)", .lo = -1, .hi = 1,
+      .replay = REPLAY_CHANGED, .def = -1 },
+    { "host_split",   OPT_DEV, .off = SLOT(opt_host_split),  .dev_key = AVDSP_OPT_HOST_SPLIT,  .replay = REPLAY_ALWAYS },
+    { "host_pin",     OPT_DEV, .off = SLOT(opt_host_pin),    .dev_key = AVDSP_OPT_HOST_PIN,    .replay = REPLAY_ALWAYS },
+    /* experiment: the cascades' stream on `value` CUs of its own (applies to the program's device copy as it is) */
+    { "cu_split",     OPT_DEV, .off = SLOT(opt_cu_split),    .dev_key = AVDSP_OPT_CU_SPLIT, .replay = REPLAY_CHANGED, .def = 0 },
+    /* 0: a plan's cascade launches (one per section count) one after the other, as through round 4 */
+    { "group_fanout", OPT_DEV, .off = SLOT(opt_group_serial), .dev_key = AVDSP_OPT_GROUP_FANOUT, .flags = OF_INVERTED, .replay = REPLAY_CHANGED, .def = 1 },
+    /* one-frame calls of interpreter cores through a resident server */
+    { "frame_server", OPT_DEV, .off = SLOT(opt_frame_server), .dev_key = AVDSP_OPT_FRAME_SERVER, ZERO_OR_ONE("frame_server"), .replay = REPLAY_CHANGED, .def = 0 },
+    /* chains of one impulse bank on fir_shared; 0: every chain as before */
+    { "fir_shared",   OPT_DEV, .off = SLOT(opt_fir_shared),  .dev_key = AVDSP_OPT_FIR_SHARED, ZERO_OR_ONE("fir_shared"), .replay = REPLAY_CHANGED, .def = 1 },
+    { "frame_server_idle_us", OPT_DEV, .off = SLOT(opt_frame_server_idle_us), .dev_key = AVDSP_OPT_FRAME_SERVER_IDLE_US, .range_text = "frame_server_idle_us: 50 .. 20000", .lo = 50, .hi = 20000,
+      .replay = REPLAY_CHANGED, .def = 1000 },
+    { "ready_test",   OPT_DEV, .dev_key = AVDSP_OPT_READY_TEST, .flags = OF_WRITE_ONLY },      /* tests only */
+    /* read from the device copy; setting 0 acknowledges the time-outs (the caller has heard of them, and has re-uploaded a state it trusts) */
+    { "ready_timeouts", OPT_DEV_RO, .hook = HOOK_READY_TIMEOUTS, .range_text = "ready_timeouts can only be set to 0 (acknowledge)", .lo = 0, .hi = 0 },
+    { "timing_pairs_", OPT_DEV_RO, .hook = HOOK_TIMING_PAIRS },                        /* timing_pairs_0 .. _7, of the latest dspRuntimeKernelTime(kind) */
+    { "fir_shared_chains", OPT_DEV_RO, .dev_key = AVDSP_OPT_FIR_SHARED_CHAINS, .flags = OF_SAYS_READ_ONLY },
+    { "fir_shared_groups", OPT_DEV_RO, .dev_key = AVDSP_OPT_FIR_SHARED_GROUPS, .flags = OF_SAYS_READ_ONLY },
+    { "fir_shared_rows",   OPT_DEV_RO, .dev_key = AVDSP_OPT_FIR_SHARED_ROWS,   .flags = OF_SAYS_READ_ONLY },
+    { "fir_ahead_now",     OPT_DEV_RO, .dev_key = AVDSP_OPT_FIR_AHEAD_NOW,     .flags = OF_SAYS_READ_ONLY },
+    { "fir_ahead_apart",   OPT_DEV_RO, .dev_key = AVDSP_OPT_FIR_AHEAD_APART,   .flags = OF_SAYS_READ_ONLY, .def = -1 },
+    DEV_RO("side_by_side", AVDSP_OPT_SIDE_BY_SIDE, -1), DEV_RO("streams_remade", AVDSP_OPT_STREAMS_REMADE, 0), DEV_RO("ready_mode", AVDSP_OPT_READY_MODE, 0),
+    DEV_RO("frame_server_frames", AVDSP_OPT_FRAME_SERVER_FRAMES, 0), DEV_RO("frame_server_launches", AVDSP_OPT_FRAME_SERVER_LAUNCHES, 0),
+    DEV_RO("frame_server_fallbacks", AVDSP_OPT_FRAME_SERVER_FALLBACKS, 0),
+    /* of the latest dspRuntimeBlockAll; dspRuntimeSetShard's */
+    { "levels", OPT_CTX_RO, .off = SLOT(last_levels) }, { "cores", OPT_CTX_RO, .off = SLOT(last_cores) }, { "pieces", OPT_CTX_RO, .off = SLOT(last_pieces) },
+    { "strands", OPT_CTX_RO, .off = SLOT(last_strands) }, { "shard_rank", OPT_CTX_RO, .off = SLOT(shard_rank) }, { "shard_world", OPT_CTX_RO, .off = SLOT(shard_world) },
+};
+#define N_OPTIONS ((int)(sizeof g_options / sizeof g_options[0]))
+#define OPT_INT(c, off) (*(int *)((char *)(c) + (off)))
+
+static const option_row *option_find(const char *key)
+{
+    for (int i = 0; i < N_OPTIONS; i++) {
+        const option_row *o = &g_options[i];
+        if (o->hook == HOOK_TIMING_PAIRS ? (!strncmp(key, o->key, 13) && key[13] >= '0' && key[13] <= '7' && !key[14]) : !strcmp(key, o->key)) return o;
+    }
+    return 0;
+}
+
+/* an option as the caller wrote it, from the int the context keeps */
+static int option_value(const avdsp_ctx *c, const option_row *o)
+{
+    const int v = OPT_INT(c, o->off);
+    return (o->flags & OF_INVERTED) ? !v : v;
+}
+
+/* the options of the device library onto a fresh device copy: the same calls in the same order as ever.  Every one synchronises the
+ * device and some remake streams, so an option that still has the device library's own default is not sent */
+static int replay_options(void)
+{
+    for (int i = 0; i < N_OPTIONS; i++) {
+        const option_row *o = &g_options[i];
+        int v = o->replay ? option_value(&G, o) : 0;
+        if (o->replay == REPLAY_NEVER || (o->replay == REPLAY_IF_SET && !OPT_INT(&G, o->set_off)) || (o->replay == REPLAY_CHANGED && v == o->def)) continue;
+        if ((o->flags & OF_AT_LEAST_1) && v < 1) v = 1;
+        if (avdsp_hip_prog_set_option(G.dev, o->dev_key, v)) return -1;
+    }
+    return 0;
+}
+
+/* a fresh program starts from the template's options */
+static void inherit_options(avdsp_ctx *c, const avdsp_ctx *from)
+{
+    for (int i = 0; i < N_OPTIONS; i++) {
+        const option_row *o = &g_options[i];
+        if (o->kind > OPT_DEV || !o->off) continue;
+        OPT_INT(c, o->off) = OPT_INT(from, o->off);
+        if (o->set_off) OPT_INT(c, o->set_off) = OPT_INT(from, o->set_off);
+    }
+}
+
 static int set_option_here(const char *key, int value)
 {
     device_current();
-    if (!strcmp(key, "fir_impl"))    { G.opt_fir_impl = value; return 0; }
-    if (!strcmp(key, "biquad_impl")) { G.opt_biquad_impl = value; return 0; }
-    if (!strcmp(key, "device"))      { G.opt_device = value; G.device_selected = 0; return 0; }
-    if (!strcmp(key, "generic"))     { G.opt_generic = value; return replan(); }
-    if (!strcmp(key, "interp_impl")) { G.opt_interp_impl = value; return replan(); }
-    if (!strcmp(key, "strand_split")) { G.opt_strand_split = value; return replan(); }
-    if (!strcmp(key, "strand_lanes")) { G.opt_strand_lanes = value; return replan(); }
-    if (!strcmp(key, "overlap") || !strcmp(key, "fir_rows") || !strcmp(key, "host_split") || !strcmp(key, "ready_words") || !strcmp(key, "lane_hw") || !strcmp(key, "fir_split")) {
-        const int split = !strcmp(key, "fir_split");
-        int *slot = split ? &G.opt_fir_split : key[0] == 'o' ? &G.opt_overlap : key[0] == 'f' ? &G.opt_fir_rows : key[0] == 'r' ? &G.opt_ready_words : key[0] == 'l' ? &G.opt_lane_hw : &G.opt_host_split;
-        const int dev_key = split ? AVDSP_OPT_FIR_SPLIT : key[0] == 'o' ? AVDSP_OPT_OVERLAP : key[0] == 'f' ? AVDSP_OPT_FIR_ROWS : key[0] == 'r' ? AVDSP_OPT_READY_WORDS : key[0] == 'l' ? AVDSP_OPT_LANE_HW : AVDSP_OPT_HOST_SPLIT;
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, dev_key, value)) return hip_fail();
-        *slot = value;
-        return 0;
-    }
-    /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it:
-     * what dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
-    if (!strcmp(key, "rate_count_static")) { g_rate_static = value; return 0; }
-    if (!strcmp(key, "host_pin")) {
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_PIN, value)) return hip_fail();
-        G.opt_host_pin = value;
-        return 0;
-    }
-    if (!strcmp(key, "fir_lean")) {
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LEAN, value)) return hip_fail();
-        G.opt_fir_lean = value; G.opt_fir_lean_set = 1;
-        return 0;
-    }
-    if (!strcmp(key, "fir_shared")) {                    /* chains of one impulse bank on fir_shared; 0: every chain as before */
-        if (value != 0 && value != 1) return fail(-1, "fir_shared: 0 or 1");
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SHARED, value)) return hip_fail();
-        G.opt_fir_shared = value;
-        return 0;
-    }
-    if (!strcmp(key, "fir_shared_chains") || !strcmp(key, "fir_shared_groups") || !strcmp(key, "fir_shared_rows")) return fail(-1, "%s is read-only", key);
-    if (!strcmp(key, "chain_finish")) {                  /* SAT0DB_TPDF / _GAIN / _TPDF_GAIN and a head TPDF_CALC on the chain kernels; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "chain_finish: 0 or 1");
-        G.opt_chain_finish = value;
-        return replan();
-    }
-    if (!strcmp(key, "chain_delay")) {                   /* one DSP_DELAY behind a chain's banks on the chain kernels; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "chain_delay: 0 or 1");
-        G.opt_chain_delay = value;
-        return replan();
-    }
-    if (!strcmp(key, "fir_tail")) {                      /* delay and dressed finish behind a DSP_FIR; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "fir_tail: 0 or 1");
-        G.opt_fir_tail = value;
-        return replan();
-    }
-    if (!strcmp(key, "mux_tail")) {                      /* dressed finishes, delay lines and a head TPDF_CALC in cores with LOAD_MUX heads; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "mux_tail: 0 or 1");
-        G.opt_mux_tail = value;
-        return replan();
-    }
-    if (!strcmp(key, "chain_mem")) {                     /* STORE_MEM trunks and LOAD_MEM branches on the chain kernels; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "chain_mem: 0 or 1");
-        G.opt_chain_mem = value;
-        return replan();
-    }
-    if (!strcmp(key, "chain_copy")) {                    /* DSP_LOAD_STORE lists beside the chains, one copy_pairs launch per block call; 0: such cores on the interpreter */
-        if (value != 0 && value != 1) return fail(-1, "chain_copy: 0 or 1");
-        G.opt_chain_copy = value;
-        return replan();
-    }
-    if (!strcmp(key, "ring_wait")) {
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, value)) return hip_fail();
-        G.opt_ring_wait = value != 0;
-        return 0;
-    }
-    if (!strcmp(key, "fir_ahead")) {                     /* staged FIR launches under "overlap" 1: -1 by the plan, 0 never, 1 whenever legal */
-        if (value < -1 || value > 1) return fail(-1, "fir_ahead: -1 (by plan), 0 (never) or 1 (whenever it is legal)");
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_AHEAD, value)) return hip_fail();
-        G.opt_fir_ahead = value;
-        return 0;
-    }
-    if (!strcmp(key, "fir_ahead_now") || !strcmp(key, "fir_ahead_apart")) return fail(-1, "%s is read-only", key);
-    if (!strcmp(key, "fir_launch")) {
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LAUNCH, value)) return hip_fail();
-        G.opt_fir_launch = value; G.opt_fir_launch_set = 1;
-        return 0;
-    }
-    if (!strcmp(key, "profile_stride")) {
-        if (value < 1) return fail(-1, "profile_stride: every n-th launch, n >= 1");
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_PROFILE_STRIDE, value)) return hip_fail();
-        G.opt_profile_stride = value;
-        return 0;
-    }
-    if (!strcmp(key, "ready_timeouts")) {                /* 0: the caller has heard of them (and has re-uploaded a state it trusts) */
-        if (value) return fail(-1, "ready_timeouts can only be set to 0 (acknowledge)");
-        if (G.dev && avdsp_hip_ready_clear(G.dev)) return hip_fail();
-        return 0;
-    }
-    if (!strcmp(key, "group_fanout")) {                  /* 0: a plan's cascade launches (one per section count) one after the other, as through round 4 */
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_GROUP_FANOUT, value)) return hip_fail();
-        G.opt_group_serial = !value;
-        return 0;
-    }
-    if (!strcmp(key, "cu_split")) {                      /* experiment: the cascades' stream on `value` CUs of its own (applies to the program's device copy as it is) */
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_CU_SPLIT, value)) return hip_fail();
-        G.opt_cu_split = value;
-        return 0;
-    }
-    if (!strcmp(key, "frame_server")) {                  /* one-frame calls of interpreter cores through a resident server */
-        if (value != 0 && value != 1) return fail(-1, "frame_server: 0 or 1");
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER, value)) return hip_fail();
-        G.opt_frame_server = value;
-        return 0;
-    }
-    if (!strcmp(key, "frame_server_idle_us")) {
-        if (value < 50 || value > 20000) return fail(-1, "frame_server_idle_us: 50 .. 20000");
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER_IDLE_US, value)) return hip_fail();
-        G.opt_frame_server_idle_us = value;
-        return 0;
-    }
-    if (!strcmp(key, "ready_test")) {                    /* tests only (AVDSP_OPT_READY_TEST) */
-        if (G.dev && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_READY_TEST, value)) return hip_fail();
-        return 0;
-    }
-    if (!strcmp(key, "profile")) {
-        G.opt_profile = value;
-        if (G.dev) avdsp_hip_profile_enable(G.dev, value);
-        return 0;
-    }
-    return fail(-1, "unknown option '%s'", key);
+    const option_row *o = option_find(key);
+    const int settable = o && (o->kind <= OPT_DEV || o->hook == HOOK_READY_TIMEOUTS);
+    if (o && !settable && (o->flags & OF_SAYS_READ_ONLY)) return fail(-1, "%s is read-only", key);
+    if (!settable) return fail(-1, "unknown option '%s'", key);
+    if (o->range_text && (value < o->lo || value > o->hi)) return fail(-1, "%s", o->range_text);
+    if (o->hook == HOOK_READY_TIMEOUTS) return G.dev && avdsp_hip_ready_clear(G.dev) ? hip_fail() : 0;
+    if (o->hook == HOOK_RATE_STATIC) { g_rate_static = value; return 0; }
+    if (o->kind == OPT_DEV && G.dev && avdsp_hip_prog_set_option(G.dev, o->dev_key, value)) return hip_fail();
+    if (o->off) OPT_INT(&G, o->off) = (o->flags & OF_BOOL) ? value != 0 : (o->flags & OF_INVERTED) ? !value : value;
+    if (o->set_off) OPT_INT(&G, o->set_off) = 1;
+    if (o->hook == HOOK_DEVICE) G.device_selected = 0;
+    if (o->hook == HOOK_PROFILE && G.dev) avdsp_hip_profile_enable(G.dev, value);
+    return o->kind == OPT_REPLAN ? replan() : 0;
 }
 
 /* An option goes to the current program AND becomes the default of programs loaded later (one program per process, the
@@ -419,59 +442,19 @@ int dspRuntimeSetOption(const char *key, int value)
     return rc;
 }
 
+/* (an unknown key reads as -1) */
 int dspRuntimeGetOption(const char *key)
 {
-    if (!strcmp(key, "fir_impl"))    return G.opt_fir_impl;
-    if (!strcmp(key, "biquad_impl")) return G.opt_biquad_impl;
-    if (!strcmp(key, "device"))      return G.opt_device;
-    if (!strcmp(key, "profile"))     return G.opt_profile;
-    if (!strcmp(key, "generic"))     return G.opt_generic;
-    if (!strcmp(key, "interp_impl")) return G.opt_interp_impl;
-    if (!strcmp(key, "levels"))      return G.last_levels;
-    if (!strcmp(key, "cores"))       return G.last_cores;
-    if (!strcmp(key, "pieces"))      return G.last_pieces;
-    if (!strcmp(key, "strand_split")) return G.opt_strand_split;
-    if (!strcmp(key, "strand_lanes")) return G.opt_strand_lanes;
-    if (!strcmp(key, "strands"))     return G.last_strands;
-    if (!strcmp(key, "overlap"))     return G.opt_overlap;
-    if (!strcmp(key, "ready_words")) return G.opt_ready_words;
-    if (!strcmp(key, "lane_hw"))     return G.opt_lane_hw;
-    if (!strcmp(key, "fir_split"))   return G.opt_fir_split;
-    if (!strcmp(key, "fir_launch"))  return G.opt_fir_launch_set ? G.opt_fir_launch : -1;
-    if (!strcmp(key, "fir_lean"))    return G.opt_fir_lean_set ? G.opt_fir_lean : -1;
-    if (!strcmp(key, "ring_wait"))   return G.opt_ring_wait;
-    if (!strcmp(key, "fir_shared"))  return G.opt_fir_shared;
-    if (!strcmp(key, "fir_ahead"))   return G.opt_fir_ahead;
-    if (!strcmp(key, "fir_ahead_now")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_AHEAD_NOW) : 0; }
-    if (!strcmp(key, "fir_ahead_apart")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_AHEAD_APART) : -1; }
-    if (!strcmp(key, "chain_finish")) return G.opt_chain_finish;
-    if (!strcmp(key, "chain_delay"))  return G.opt_chain_delay;
-    if (!strcmp(key, "fir_tail"))     return G.opt_fir_tail;
-    if (!strcmp(key, "mux_tail"))     return G.opt_mux_tail;
-    if (!strcmp(key, "chain_mem"))    return G.opt_chain_mem;
-    if (!strcmp(key, "chain_copy"))   return G.opt_chain_copy;
-    if (!strcmp(key, "fir_shared_chains")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_CHAINS) : 0; }
-    if (!strcmp(key, "fir_shared_groups")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_GROUPS) : 0; }
-    if (!strcmp(key, "fir_shared_rows"))   { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FIR_SHARED_ROWS) : 0; }
-    if (!strncmp(key, "timing_pairs_", 13) && key[13] >= '0' && key[13] <= '7' && !key[14])      /* of the latest dspRuntimeKernelTime(kind) */
-        return G.dev ? avdsp_hip_profile_last_pairs(G.dev, key[13] - '0') : 0;
-    if (!strcmp(key, "ready_timeouts")) { device_current(); return G.dev ? avdsp_hip_ready_timeouts(G.dev) : 0; }
-    if (!strcmp(key, "cu_split"))    return G.opt_cu_split;
-    if (!strcmp(key, "group_fanout")) return !G.opt_group_serial;
-    if (!strcmp(key, "side_by_side")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_SIDE_BY_SIDE) : -1; }
-    if (!strcmp(key, "streams_remade")) { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_STREAMS_REMADE) : 0; }
-    if (!strcmp(key, "ready_mode"))  { device_current(); return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_READY_MODE) : 0; }
-    if (!strcmp(key, "frame_server")) return G.opt_frame_server;
-    if (!strcmp(key, "frame_server_idle_us")) return G.opt_frame_server_idle_us;
-    if (!strcmp(key, "frame_server_frames")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_FRAMES) : 0;
-    if (!strcmp(key, "frame_server_launches")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_LAUNCHES) : 0;
-    if (!strcmp(key, "frame_server_fallbacks")) return G.dev ? avdsp_hip_prog_get_option(G.dev, AVDSP_OPT_FRAME_SERVER_FALLBACKS) : 0;
-    if (!strcmp(key, "fir_rows"))    return G.opt_fir_rows;
-    if (!strcmp(key, "host_split"))  return G.opt_host_split;
-    if (!strcmp(key, "host_pin"))    return G.opt_host_pin;
-    if (!strcmp(key, "shard_rank"))  return G.shard_rank;
-    if (!strcmp(key, "shard_world")) return G.shard_world;
-    return -1;
+    const option_row *o = option_find(key);
+    if (!o || (o->flags & OF_WRITE_ONLY)) return -1;
+    if (o->kind == OPT_DEV_RO) {
+        device_current();
+        if (!G.dev) return o->def;
+        return o->hook == HOOK_READY_TIMEOUTS ? avdsp_hip_ready_timeouts(G.dev) : o->hook == HOOK_TIMING_PAIRS ? avdsp_hip_profile_last_pairs(G.dev, key[13] - '0')
+                                                                                : avdsp_hip_prog_get_option(G.dev, o->dev_key);
+    }
+    if (o->set_off && !OPT_INT(&G, o->set_off)) return -1;
+    return option_value(&G, o);
 }
 
 /* ---- channel sharding ----
@@ -586,10 +569,7 @@ int dspRuntimeInit(opcode_t *codePtr, int maxSize, const int fs, int random, int
         c = (avdsp_ctx *)calloc(1, sizeof *c);
         if (!c) return fail(-9, "out of memory");
         const avdsp_ctx *o = &g_template;
-        c->opt_fir_impl = o->opt_fir_impl; c->opt_biquad_impl = o->opt_biquad_impl; c->opt_device = o->opt_device; c->opt_profile = o->opt_profile;
-        c->opt_generic = o->opt_generic; c->opt_interp_impl = o->opt_interp_impl; c->opt_strand_split = o->opt_strand_split; c->opt_strand_lanes = o->opt_strand_lanes;
-        c->opt_profile_stride = o->opt_profile_stride; c->opt_overlap = o->opt_overlap; c->opt_fir_rows = o->opt_fir_rows; c->opt_host_split = o->opt_host_split; c->opt_host_pin = o->opt_host_pin; c->opt_ready_words = o->opt_ready_words; c->opt_lane_hw = o->opt_lane_hw; c->opt_fir_split = o->opt_fir_split; c->opt_fir_launch = o->opt_fir_launch; c->opt_fir_launch_set = o->opt_fir_launch_set; c->opt_fir_lean = o->opt_fir_lean; c->opt_fir_lean_set = o->opt_fir_lean_set; c->opt_ring_wait = o->opt_ring_wait; c->opt_fir_ahead = o->opt_fir_ahead; c->opt_cu_split = o->opt_cu_split; c->opt_group_serial = o->opt_group_serial;
-        c->opt_frame_server = o->opt_frame_server; c->opt_frame_server_idle_us = o->opt_frame_server_idle_us; c->opt_fir_shared = o->opt_fir_shared; c->opt_chain_finish = o->opt_chain_finish; c->opt_chain_delay = o->opt_chain_delay; c->opt_fir_tail = o->opt_fir_tail; c->opt_mux_tail = o->opt_mux_tail; c->opt_chain_mem = o->opt_chain_mem; c->opt_chain_copy = o->opt_chain_copy;
+        inherit_options(c, o);
         c->shard_rank = o->shard_rank; c->shard_world = o->shard_world;
         c->mantissa = DSP_MANT; c->device_ordinal = -1;
         c->code = codePtr;
@@ -949,6 +929,7 @@ static int dither_width_constant(void)
  * of the core reads (a gain computed on the fly), no LOAD_MUX head and no FIR beside them */
 static int check_mem_words(const lowered *L)
 {
+    if (!L->nmem) return 0;
     long long *w = (long long *)malloc((size_t)L->nmem * sizeof *w);      /* word << 32 | trunk << 31 ... sorted by word, trunks first */
     if (!w) return fail(-9, "out of memory");
     int k = 0, rc = 0;
@@ -976,380 +957,506 @@ static int check_mem_words(const lowered *L)
     return rc;
 }
 
-/* mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used (dspRuntimeMuxInfo tells it from the others) */
-static int lowered_has_mux(const lowered *L);
+/* ---- delay lines: DSP_DELAY's first word is the line's size -- in samples with a parameter word, else in microseconds, which the rate's
+ * factor (2^32 / 10^6 x fs, dsp_runtime.c:81-90) turns into samples ---- */
+static unsigned delay_line_factor(void) { return (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index)); }
+static long long delay_samples(int size, int in_samples, unsigned factor)
+{
+    return in_samples ? (long long)size : (long long)(((unsigned long long)(unsigned)size * factor) >> 32);
+}
+/* the words of a lowered chain's line in the state area: its index word and its samples */
+static long long delay_line_words(const avdsp_chain *c, unsigned factor) { return 1 + delay_samples(c->delay_max, c->delay_us_word != 0, factor); }
+
+/* ---- the gates: which of the opt-in lowerings a core gets in this format, computed once per lowering; the walk, the
+ * checks behind it and the plan (get_plan_range) read nothing else.  A new lowering option gets its gate here. ---- */
+typedef struct {
+    int      finish;          /* "chain_finish": not while the program has instances (each has a generator of its own on the interpreter) */
+    int      delay;           /* "chain_delay" */
+    int      fir_tail;        /* "fir_tail": formats 4 and 6, the chain FIR's */
+    int      mux_tail, mem, copy;      /* "mux_tail", "chain_mem", "chain_copy" */
+    unsigned delay_factor;
+} lower_gates;
+
+static lower_gates gates_of(int format)
+{
+    lower_gates g;
+    g.finish = G.opt_chain_finish && G.ninst <= 1 && (format == 2 || format == 4 || format == 6);
+    g.delay = G.opt_chain_delay;
+    g.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
+    g.mux_tail = G.opt_mux_tail;
+    g.mem = G.opt_chain_mem;
+    g.copy = G.opt_chain_copy;
+    g.delay_factor = delay_line_factor();
+    return g;
+}
+
+static int lowered_has_mux(const lowered *L)
+{
+    for (int i = 0; i < L->nchains; i++) if (L->chains[i].load_mode == AVDSP_LOAD_MUX) return 1;
+    return 0;
+}
+
+/* The checks behind the walk that concern delay lines, each with its own refusal; lower_core_body calls them in this order and the
+ * first refusal wins.  "mux_tail" off: no dressed finish, head TPDF_CALC or delay line beside LOAD_MUX heads */
+static int check_mux_beside_tails(const lowered *L, const lower_gates *g)
+{
+    if (g->mux_tail || !lowered_has_mux(L)) return 0;
+    if (L->ndressed || L->tpdf_calc) return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
+    if (L->ndelayed) return fail(-8, "chains with a DSP_DELAY beside LOAD_MUX heads are not lowered to the HIP path");
+    return 0;
+}
+
+/* ("mux_tail") the mux stage writes a LOAD_MUX result word once per launch, from its last frame, and ahead of chain_tail, where the
+ * reference writes it in every frame between two visits of the line: no line -- index word and samples -- may share a word with one */
+static int check_line_vs_mux_result(const lowered *L, const lower_gates *g)
+{
+    if (!L->ndelayed || !g->mux_tail || !lowered_has_mux(L)) return 0;
+    for (int i = 0; i < L->nchains; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        if (!c->delay_slot) continue;
+        const long long lo = c->delay_word, hi = lo + delay_line_words(c, g->delay_factor);
+        for (int j = 0; j < L->nchains; j++)
+            if (L->chains[j].load_mode == AVDSP_LOAD_MUX && (long long)L->chains[j].mux_result_word < hi && (long long)L->chains[j].mux_result_word + 2 > lo)
+                return fail(-8, "a delay line and a LOAD_MUX result word share words of the state area");
+    }
+    return 0;
+}
+
+/* the chains run side by side: two of them must not share words of a line (the encoder never lets them; the strand lowering checks
+ * the same).  [first word, words] per line, sorted by the first */
+static int check_lines_apart(const lowered *L, const lower_gates *g)
+{
+    if (L->ndelayed < 2) return 0;
+    long long *iv = (long long *)malloc((size_t)L->ndelayed * 2 * sizeof *iv);
+    if (!iv) return fail(-9, "out of memory");
+    int k = 0, clash = 0;
+    for (int i = 0; i < L->nchains; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        if (!c->delay_slot) continue;
+        iv[2 * k] = c->delay_word;
+        iv[2 * k + 1] = delay_line_words(c, g->delay_factor);
+        k++;
+    }
+    qsort(iv, (size_t)k, 2 * sizeof *iv, cmp_ll);
+    for (int i = 1; i < k && !clash; i++) clash = iv[2 * i] < iv[2 * i - 2] + iv[2 * i - 1];
+    free(iv);
+    return clash ? fail(-8, "two delay lines of the core share words of the state area") : 0;
+}
+
+/* ("fir_tail") nor may a line share words with the history of a FIR: chain_tail writes the one while a FIR's history is converted from
+ * and to the other.  Lines and histories sorted by their first word; a line must begin behind everything before it, a history behind
+ * every line before it */
+static int check_lines_vs_fir_history(const lowered *L, const lower_gates *g)
+{
+    int nfir = 0;
+    for (int i = 0; i < L->nchains; i++) nfir += L->chains[i].fir_taps != 0;
+    if (!L->ndelayed || !g->fir_tail || !nfir) return 0;
+    long long *iv = (long long *)malloc((size_t)(L->ndelayed + nfir) * 3 * sizeof *iv);      /* [first word, words, is a line] */
+    if (!iv) return fail(-9, "out of memory");
+    int k = 0, clash = 0;
+    for (int i = 0; i < L->nchains; i++) {
+        const avdsp_chain *c = &L->chains[i];
+        if (c->delay_slot) { iv[3 * k] = c->delay_word; iv[3 * k + 1] = delay_line_words(c, g->delay_factor); iv[3 * k + 2] = 1; k++; }
+        if (c->fir_taps) { iv[3 * k] = c->fir_state_word; iv[3 * k + 1] = c->fir_taps; iv[3 * k + 2] = 0; k++; }
+    }
+    qsort(iv, (size_t)k, 3 * sizeof *iv, cmp_ll);
+    long long end_line = -1, end_any = -1;
+    for (int i = 0; i < k && !clash; i++) {
+        clash = iv[3 * i] < (iv[3 * i + 2] ? end_any : end_line);
+        const long long e = iv[3 * i] + iv[3 * i + 1];
+        if (iv[3 * i + 2] && e > end_line) end_line = e;
+        if (e > end_any) end_any = e;
+    }
+    free(iv);
+    return clash ? fail(-8, "a delay line and a FIR's history share words of the state area") : 0;
+}
+
+/* ---- the walk: one function per kind of opcode, over the state of the walk.  Each returns 0 (go on), LC_NOT_LOWERED (the option that
+ * lowers the opcode is off: the generic "opcode %d (%s) is not lowered" text, as for an opcode nothing lowers) or the code of the
+ * refusal it has written.  The encoder is trusted by the reference; here nothing is dereferenced before it is known to lie inside the
+ * program (the device library checks the word indices of the finished plan once more). ---- */
+typedef struct {
+    int            format, prog_words;
+    lower_gates    g;
+    lowered       *L;
+    int           *mux_damaged;
+    unsigned char **smap;             /* store_mem_map(), built at the first memory opcode under "chain_mem" */
+    avdsp_chain    cur;               /* the open chain */
+    int            open, fir_op;      /* fir_op: the open chain holds a DSP_FIR opcode (with taps or bypassed) */
+    int            after_mem;         /* the opcode before was a trunk's STORE_MEM: a chain head or the core's end must follow */
+    opcode_t      *p;                 /* the opcode at hand: its word index, length and payload */
+    int            op, at;
+    unsigned       skip;
+    const int     *a;
+} lower_walk;
+#define LC_NOT_LOWERED 1
+#define LC_NEED(n) do { if ((unsigned)(1 + (n)) > W->skip) return fail(-8, "word %d: opcode payload shorter than %d words", W->at, (n)); } while (0)
+#define LC_PROG(off, n) do { long long lo_ = (long long)W->at + (off); if (lo_ < 0 || lo_ + (n) > W->prog_words) \
+            return fail(-8, "word %d: program offset %d (+%d) outside the program", W->at, (int)(off), (int)(n)); } while (0)
+#define LC_IO(io) do { if ((io) < 0 || (io) >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", W->at, (io), GENERIC_IO_LIMIT); } while (0)
+#define LC_PREAD(off, n) do { if (W->g.mem && push_pread(W->L, (long long)W->at + (off), (n))) return fail(-9, "out of memory"); } while (0)
 static unsigned char *store_mem_map(void);
-static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_damaged, unsigned char **smap);
+static int chain_kernel_format(int format) { return format == 2 || format == 4 || format == 6; }
+
+/* a chain head: the open chain is complete -- it must have stored -- and joins the list; a fresh one starts */
+static int open_chain(lower_walk *W)
+{
+    if (W->open) {
+        if (W->cur.n_out == 0) return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", W->at);
+        if (push_chain(W->L, &W->cur)) return fail(-9, "out of memory");
+    }
+    memset(&W->cur, 0, sizeof W->cur);
+    W->open = 1; W->fir_op = 0;
+    W->cur.sec_base = W->L->nsec;
+    return 0;
+}
+
+/* behind a trunk's STORE_MEM only a chain head may follow (a list ends nothing) */
+static int lower_behind_trunk(lower_walk *W)
+{
+    const int op = W->op;
+    if (!W->after_mem || op == DSP_NOP || op == DSP_PARAM || op == DSP_PARAM_NUM || op == DSP_SERIAL || (W->g.copy && op == DSP_LOAD_STORE)) return 0;
+    if (op == DSP_BIQUADS) return fail(-8, "word %d: a STORE_MEM in front of the banks or between two banks is not lowered to the HIP path", W->at);
+    if (op != DSP_LOAD && op != DSP_LOAD_GAIN && op != DSP_LOAD_MEM && op != DSP_LOAD_MUX)
+        return fail(-8, "word %d: a STORE_MEM that is not the last opcode of its chain is not lowered to the HIP path", W->at);
+    W->after_mem = 0;
+    return 0;
+}
+
+/* dsp_runtime.c:738-747, "chain_copy": samples[out] = samples[in], pair by pair */
+static int lower_load_store(lower_walk *W)
+{
+    const int at = W->at;
+    const unsigned skip = W->skip;
+    if (!W->g.copy) return LC_NOT_LOWERED;
+    if (G.ninst > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the program has instances", at);
+    if (G.shard_world > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the core is sharded", at);
+    if (W->open && W->cur.n_out == 0)
+        return fail(-8, "word %d: a LOAD_STORE list between a chain's LOAD and its first STORE is not lowered to the HIP path", at);
+    if (!(skip & 1)) return fail(-8, "word %d: a LOAD_STORE list of %u words is no list of pairs (damaged)", at, skip - 1);
+    for (unsigned k = 0; k + 1 < skip; k++) LC_IO(W->a[k]);
+    for (unsigned k = 0; k + 2 < skip; k += 2)
+        if (copy_pair(W->L, W->a[k], W->a[k + 1])) return fail(-9, "out of memory");
+    W->L->ncopy_written += (int)(skip - 1) / 2;
+    return 0;
+}
+
+/* dsp_runtime.c:750-766, "chain_mem": STORE_MEM ends a trunk, LOAD_MEM opens a branch */
+static int lower_mem(lower_walk *W)
+{
+    const int at = W->at, op = W->op;
+    const int *a = W->a;
+    if (!W->g.mem) return LC_NOT_LOWERED;
+    if (op == DSP_LOAD_MEM_DATA)
+        return fail(-8, "word %d: LOAD_MEM_DATA is not lowered to the HIP path (of the memory opcodes only LOAD_MEM and STORE_MEM are)", at);
+    if (!chain_kernel_format(W->format)) return fail(-8, "word %d: a memory word is not lowered to the HIP path in format %d", at, W->format);
+    if (G.ninst > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the program has instances", at);
+    if (G.shard_world > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the core is sharded", at);
+    LC_NEED(1);
+    LC_PROG(a[0], 2);
+    if (!*W->smap && !(*W->smap = store_mem_map())) return fail(-9, "out of memory");
+    for (int k = 0; k < 2; k++)
+        if ((*W->smap)[at + a[0] + k] != 1)
+            return fail(-8, "word %d: %s target (word %d) is not a free word of a PARAM section: it would "
+                            "rewrite %s", at, op == DSP_STORE_MEM ? "STORE_MEM" : "LOAD_MEM", at + a[0] + k,
+                        (*W->smap)[at + a[0] + k] ? "a count, IO number or length other opcodes rely on" : "the opcode stream");
+    if (op == DSP_LOAD_MEM) {
+        const int rc = open_chain(W);
+        if (rc) return rc;
+        W->cur.load_mode = AVDSP_LOAD_MEM;
+        W->cur.mem_word = at + a[0];
+        W->L->nmem++;
+        return 0;
+    }
+    if (!W->open) return fail(-8, "word %d: STORE_MEM without a LOAD", at);
+    if (W->cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a memory word in a chain with a LOAD_MUX head is not lowered to the HIP path", at);
+    if (W->cur.load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a STORE_MEM in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
+    if (W->fir_op) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
+    if (W->cur.n_out || W->cur.sat || W->cur.delay_slot)
+        return fail(-8, "word %d: a STORE_MEM behind a STORE, a SAT0DB or a DSP_DELAY is not lowered to the HIP path", at);
+    W->cur.mem_word = at + a[0]; W->cur.mem_store = 1;
+    if (push_chain(W->L, &W->cur)) return fail(-9, "out of memory");
+    memset(&W->cur, 0, sizeof W->cur);
+    W->open = 0; W->fir_op = 0; W->after_mem = 1;
+    W->L->nmem++;
+    return 0;
+}
+
+/* DSP_LOAD (dsp_runtime.c:565-583), DSP_LOAD_GAIN (:586-607) */
+static int lower_load(lower_walk *W)
+{
+    const int *a = W->a;
+    const int gain = W->op == DSP_LOAD_GAIN;
+    LC_NEED(gain ? 2 : 1);
+    if (gain) LC_PROG(a[1], 1);
+    LC_IO(a[0]);
+    const int rc = open_chain(W);
+    if (rc) return rc;
+    W->cur.in_io = a[0];
+    if (gain) {
+        W->cur.load_mode = AVDSP_LOAD_GAIN;
+        W->cur.gain_bits = W->p[a[1]].u32;
+        LC_PREAD(a[1], 1);
+    }
+    return 0;
+}
+
+/* dsp_runtime.c:871-897: a chain head like LOAD, the accumulator a weighted sum of inputs.  mux_damaged is set while the table has
+ * not passed: dspRuntimeMuxInfo tells such a refusal from the others */
+static int lower_load_mux(lower_walk *W)
+{
+    const int at = W->at;
+    const int *a = W->a;
+    if (!chain_kernel_format(W->format)) return fail(-8, "word %d: LOAD_MUX is not lowered to the HIP path in format %d", at, W->format);
+    *W->mux_damaged = 1;
+    LC_NEED(2);
+    LC_PROG(a[0], 1);
+    const opcode_t *t = W->p + a[0];
+    const int n = (short)t[0].i32;                            /* the reference counts in a `short` */
+    if (n < 1) return fail(-8, "word %d: LOAD_MUX table with %d entries", at, n);
+    LC_PROG(a[0], 1 + 2 * n);
+    for (int k = 0; k < n; k++)
+        if (t[1 + 2 * k].i32 < 0 || t[1 + 2 * k].i32 >= GENERIC_IO_LIMIT)
+            return fail(-8, "word %d: LOAD_MUX entry %d: IO number %d outside [0,%d)", at, k, t[1 + 2 * k].i32, GENERIC_IO_LIMIT);
+    if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
+        return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
+    *W->mux_damaged = 0;
+    LC_PREAD(a[0], 1 + 2 * n);
+    const int rc = open_chain(W);
+    if (rc) return rc;
+    W->cur.in_io = t[1].i32;
+    W->cur.load_mode = AVDSP_LOAD_MUX;
+    W->cur.mux_word = (int)(t - G.code) + 1;
+    W->cur.mux_count = n;
+    W->cur.mux_result_word = W->prog_words + a[1];
+    return 0;
+}
+
+/* dsp_runtime.c:827-849 */
+static int lower_biquads(lower_walk *W)
+{
+    const int at = W->at;
+    const int *a = W->a;
+    avdsp_chain *cur = &W->cur;
+    if (W->open && cur->delay_slot) return fail(-8, "word %d: a DSP_DELAY in front of the banks is not lowered to the HIP path", at);
+    if (!W->open || cur->n_out || cur->sat || cur->fir_taps)
+        return fail(-8, "word %d: BIQUADS outside the supported LOAD->BIQUADS->FIR->SAT0DB->STORE order", at);
+    LC_NEED(2);
+    LC_PROG(a[1], 2);
+    const opcode_t *bank = W->p + a[1];
+    const int num = (short)bank[0].i32;                       /* callee takes `short num` */
+    if (num < 1) return fail(-8, "word %d: biquad bank with %d sections", at, num);
+    const int bank_words = G.biquad_offset + (num - 1) * dspBiquadFreqSkip + 5;
+    LC_PROG(a[1], bank_words);
+    if (a[0] < 0 || (long long)a[0] + 6ll * num > dspHeaderPtr->dataSize)
+        return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[0], 6 * num, dspHeaderPtr->dataSize);
+    LC_PREAD(a[1], bank_words);
+    if (bank[1].i32 != 0)                                     /* 0 = bypass, :837 */
+        for (int s = 0; s < num; s++)
+            if (push_section(W->L, (int)(bank - G.code) + G.biquad_offset + s * dspBiquadFreqSkip, W->prog_words + a[0] + 6 * s))
+                return fail(-9, "out of memory");
+    cur->nsec = W->L->nsec - cur->sec_base;
+    return 0;
+}
+
+/* dsp_runtime.c:928-969 */
+static int lower_fir(lower_walk *W)
+{
+    const int at = W->at;
+    const int *a = W->a;
+    avdsp_chain *cur = &W->cur;
+    if (W->open && cur->delay_slot)
+        return W->g.fir_tail ? fail(-8, "word %d: a DSP_DELAY in front of the chain's DSP_FIR is not lowered to the HIP path", at)
+                             : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
+    if (!W->open || cur->n_out || cur->sat) return fail(-8, "word %d: FIR outside the supported chain order", at);
+    if (cur->load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a DSP_FIR in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
+    if (W->format == DSP_FORMAT_INT64)
+        return fail(-8, "word %d: DSP_FIR in int64 mode is undefined behaviour in the reference "
+                        "(dsp_firSTD.h:8-35) and is not provided", at);
+    LC_NEED(G.num_freq + 1);
+    W->fir_op = 1;
+    const int off = a[G.freq_index];
+    if (!off) return 0;
+    LC_PROG(off, 1);
+    const opcode_t *imp = W->p + off;
+    const int length = imp[0].i32;
+    if (length >> 16) return fail(-8, "word %d: FIR pure-delay variant is not lowered yet", at);
+    if (length <= 0) return 0;
+    LC_PROG(off, 1 + length);
+    LC_PREAD(off, 1 + length);
+    if (a[G.num_freq] < 0 || (long long)a[G.num_freq] + length > dspHeaderPtr->dataSize)
+        return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[G.num_freq], length, dspHeaderPtr->dataSize);
+    if (cur->fir_taps) return fail(-8, "word %d: more than one FIR per chain", at);
+    cur->fir_taps = length;
+    cur->fir_coef_word = (int)(imp - G.code) + 1;
+    cur->fir_state_word = W->prog_words + a[G.num_freq];
+    return 0;
+}
+
+/* a tail -- a delay line or a dressed finish -- behind a DSP_FIR or a LOAD_MUX head needs "fir_tail" / "mux_tail" */
+static int tail_is_gated(const lower_walk *W)
+{
+    return (W->fir_op && !W->g.fir_tail) || (W->cur.load_mode == AVDSP_LOAD_MUX && !W->g.mux_tail);
+}
+
+/* dsp_runtime.c:769-794, "chain_delay": DSP_DELAY once per chain, behind the banks, on either side of the SAT0DB slot; of the delay
+ * lines only DSP_DELAY is lowered */
+static int lower_delay(lower_walk *W)
+{
+    const int at = W->at, op = W->op;
+    const int *a = W->a;
+    avdsp_chain *cur = &W->cur;
+    if (!W->g.delay) return LC_NOT_LOWERED;
+    if (op != DSP_DELAY)
+        return fail(-8, "word %d: %s is not lowered to the HIP path (of the delay lines only DSP_DELAY is)", at, op == DSP_DELAY_1 ? "DSP_DELAY_1" : "DSP_DELAY_DP");
+    if (!chain_kernel_format(W->format)) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path in format %d", at, W->format);
+    if (G.ninst > 1) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path while the program has instances", at);
+    if (!W->open) return fail(-8, "word %d: a DSP_DELAY in front of the chain's LOAD is not lowered to the HIP path", at);
+    if (cur->n_out) return fail(-8, "word %d: a DSP_DELAY behind a STORE is not lowered to the HIP path", at);
+    if (cur->delay_slot) return fail(-8, "word %d: a second DSP_DELAY in one chain is not lowered to the HIP path", at);
+    if (tail_is_gated(W)) return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR or a LOAD_MUX head is not lowered to the HIP path", at);
+    LC_NEED(3);
+    if (a[0] < 0) return fail(-8, "word %d: delay line of negative size %d", at, a[0]);
+    if (a[2]) LC_PROG(a[2], 1);
+    /* with a parameter the first word is the line's size in samples, without it microseconds (the strand lowering's checks) */
+    const long long nline = delay_samples(a[0], a[2] != 0, W->g.delay_factor);
+    if (a[1] < 0 || (long long)a[1] + 1 + nline > dspHeaderPtr->dataSize)
+        return fail(-8, "word %d: data offset %d (+%lld) outside the state area (%d words)", at, a[1], 1 + nline, dspHeaderPtr->dataSize);
+    cur->delay_slot = cur->sat ? AVDSP_DELAY_B : AVDSP_DELAY_A;
+    cur->delay_word = W->prog_words + a[1];
+    cur->delay_us_word = a[2] ? at + a[2] : 0;
+    if (a[2]) LC_PREAD(a[2], 1);
+    cur->delay_max = a[0];
+    W->L->ndelayed++;
+    return 0;
+}
+
+/* dsp_runtime.c:478-534, "chain_finish": SAT0DB_TPDF, SAT0DB_GAIN, SAT0DB_TPDF_GAIN */
+static int lower_finish(lower_walk *W)
+{
+    const int at = W->at, op = W->op;
+    avdsp_chain *cur = &W->cur;
+    if (!W->g.finish) return LC_NOT_LOWERED;
+    if (!W->open || cur->n_out || cur->sat || cur->delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
+    if (tail_is_gated(W)) return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
+    if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
+    cur->finish = op == DSP_SAT0DB_TPDF ? AVDSP_FINISH_TPDF : op == DSP_SAT0DB_GAIN ? AVDSP_FINISH_GAIN : AVDSP_FINISH_TPDF_GAIN;
+    if (op != DSP_SAT0DB_TPDF) {
+        LC_NEED(1);
+        LC_PROG(W->a[0], 1);
+        cur->finish_gain_bits = W->p[W->a[0]].u32;
+        LC_PREAD(W->a[0], 1);
+    }
+    cur->sat = 1;
+    W->L->ndressed++;
+    return 0;
+}
+
+/* dsp_runtime.c:537-545, "chain_finish": once, in front of the first chain */
+static int lower_tpdf_calc(lower_walk *W)
+{
+    const int at = W->at;
+    const int *a = W->a;
+    lowered *L = W->L;
+    if (!W->g.finish) return LC_NOT_LOWERED;
+    if (W->open || L->nchains || L->tpdf_calc) return fail(-8, "word %d: TPDF_CALC behind the head of the core is not lowered to the HIP path", at);
+    LC_NEED(2);
+    if (a[0] != 0 && a[0] != G.dither) return fail(-8, "word %d: TPDF_CALC of width %d under the default %d is not lowered to the HIP path", at, a[0], G.dither);
+    if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
+    if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
+        return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
+    L->tpdf_calc = 1; L->tpdf_calc_arg = a[0]; L->tpdf_calc_word = W->prog_words + a[1];
+    return 0;
+}
+
+/* DSP_SAT0DB (dsp_runtime.c:464-475), DSP_STORE (:610-633) */
+static int lower_sat_store(lower_walk *W)
+{
+    const int at = W->at;
+    avdsp_chain *cur = &W->cur;
+    if (W->op == DSP_SAT0DB) {
+        if (!W->open || cur->n_out || cur->delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
+        cur->sat = 1;
+        return 0;
+    }
+    LC_NEED(1);
+    LC_IO(W->a[0]);
+    if (!W->open) return fail(-8, "word %d: STORE without a LOAD", at);
+    if (cur->n_out == AVDSP_MAX_STORES) return fail(-8, "word %d: more than %d STOREs in a chain", at, AVDSP_MAX_STORES);
+    cur->out_io[cur->n_out++] = W->a[0];
+    return 0;
+}
+#undef LC_NEED
+#undef LC_PROG
+#undef LC_IO
+#undef LC_PREAD
+
+/* The lowering of one core: the gates, the walk, the checks behind it.  -8: not lowered (the text says why), -9: out
+ * of memory, or what ensure_encoding returns.  mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used.
+ * lower_core_ex owns the STORE_MEM map the walk may build. */
+static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_damaged, unsigned char **smap)
+{
+    int damaged_ = 0, rc = 0;
+    lower_walk W;
+    memset(&W, 0, sizeof W);
+    memset(L, 0, sizeof *L);
+    W.format = format; W.L = L; W.smap = smap;
+    W.mux_damaged = mux_damaged ? mux_damaged : &damaged_;
+    *W.mux_damaged = 0;
+    W.prog_words = dspHeaderPtr->totalLength;
+    W.p = dspFindCoreBegin(core);
+    W.g = gates_of(format);
+    if (ensure_encoding(format)) return g_err_code;
+
+    for (;; W.p += W.skip) {
+        const int op = W.op = W.p->op.opcode, at = W.at = (int)(W.p - G.code);
+        W.skip = W.p->op.skip;
+        W.a = (const int *)W.p + 1;
+        if (at < 0 || at >= W.prog_words) return fail(-8, "opcode stream runs past the program (word %d)", at);
+        if (W.skip == 0 || op == DSP_CORE) break;            /* dsp_runtime.c:321-331 */
+        if ((long long)at + W.skip > W.prog_words) return fail(-8, "word %d: opcode longer than the program", at);
+        if ((rc = lower_behind_trunk(&W)) != 0) return rc;
+        switch (op) {
+        case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:          break;
+        case DSP_LOAD_STORE:                                                         rc = lower_load_store(&W); break;
+        case DSP_LOAD_MEM_DATA: case DSP_LOAD_MEM: case DSP_STORE_MEM:               rc = lower_mem(&W); break;
+        case DSP_LOAD: case DSP_LOAD_GAIN:                                           rc = lower_load(&W); break;
+        case DSP_LOAD_MUX:                                                           rc = lower_load_mux(&W); break;
+        case DSP_BIQUADS:                                                            rc = lower_biquads(&W); break;
+        case DSP_FIR:                                                                rc = lower_fir(&W); break;
+        case DSP_DELAY_1: case DSP_DELAY_DP: case DSP_DELAY:                         rc = lower_delay(&W); break;
+        case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:       rc = lower_finish(&W); break;
+        case DSP_TPDF_CALC:                                                          rc = lower_tpdf_calc(&W); break;
+        case DSP_SAT0DB: case DSP_STORE:                                             rc = lower_sat_store(&W); break;
+        default:                                                                     rc = LC_NOT_LOWERED; break;
+        }
+        if (rc == LC_NOT_LOWERED)
+            return fail(-8, "word %d: opcode %d (%s) is not lowered to the HIP path", at, op,
+                        (op >= 0 && op < DSP_MAX_OPCODE) ? dspOpcodeText[op] + (dspOpcodeText[op][0] == '\n') : "?");
+        if (rc) return rc;
+    }
+    if (W.open) {
+        if (W.cur.n_out == 0) return fail(-8, "core ends with a chain that is never stored");
+        if (push_chain(L, &W.cur)) return fail(-9, "out of memory");
+    }
+    /* behind the walk, in this order; the first refusal wins */
+    if (W.g.copy && G.ninst <= 1 && G.shard_world <= 1) rc = drop_dead_stores(L);
+    if (!rc) rc = check_copies(L);
+    if (!rc && L->nchains == 0 && L->ncopy == 0) rc = fail(-8, "core contains no LOAD..STORE chain");
+    if (!rc) rc = check_mem_words(L);
+    if (!rc) rc = check_mux_beside_tails(L, &W.g);
+    if (!rc) rc = check_line_vs_mux_result(L, &W.g);
+    if (!rc) rc = check_lines_apart(L, &W.g);
+    if (!rc) rc = check_lines_vs_fir_history(L, &W.g);
+    return rc ? rc : check_independent(L);
+}
+
 static int lower_core_ex(int format, opcode_t *core, lowered *L, int *mux_damaged)
 {
-    unsigned char *smap = 0;                                 /* store_mem_map(), built at the first memory opcode under "chain_mem" */
+    unsigned char *smap = 0;
     const int rc = lower_core_body(format, core, L, mux_damaged, &smap);
     free(smap);
     return rc;
-}
-static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_damaged, unsigned char **smap)
-{
-    int damaged_ = 0;
-    if (!mux_damaged) mux_damaged = &damaged_;
-    *mux_damaged = 0;
-    const int float_alu = (format != DSP_FORMAT_INT64);
-    const int prog_words = dspHeaderPtr->totalLength;
-    opcode_t *p = dspFindCoreBegin(core);
-    avdsp_chain cur;
-    int open = 0, fir_op = 0;                                /* fir_op: the open chain holds a DSP_FIR opcode (with taps or bypassed) */
-    memset(&cur, 0, sizeof cur);
-    memset(L, 0, sizeof *L);
-    /* dressed finishes and the head TPDF_CALC: opt-in, formats 2, 4 and 6, not while the program has instances (each has a generator
-     * of its own on the interpreter) */
-    const int finish_on = G.opt_chain_finish && G.ninst <= 1 && (format == 2 || format == 4 || format == 6);
-    const unsigned delay_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* dsp_runtime.c:81-90 */
-    /* "fir_tail": the delay and the dressed finish may stand behind a DSP_FIR (formats 4 and 6: the chain FIR's) */
-    const int fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
-    /* "mux_tail": all of that also behind a LOAD_MUX head and beside such chains */
-    const int mux_tail = G.opt_mux_tail;
-    /* "chain_mem": STORE_MEM ends a trunk, LOAD_MEM opens a branch */
-    const int mem_on = G.opt_chain_mem;
-    /* "chain_copy": DSP_LOAD_STORE lists beside the chains */
-    const int copy_on = G.opt_chain_copy;
-    int after_mem = 0;                                       /* the opcode before was a trunk's STORE_MEM: a chain head or the core's end must follow */
-
-    if (ensure_encoding(format)) return g_err_code;
-
-    for (;;) {
-        const int op = p->op.opcode;
-        const unsigned skip = p->op.skip;
-        const int *a = (const int *)p + 1;
-        const int at = (int)(p - G.code);
-        if (at < 0 || at >= prog_words) return fail(-8, "opcode stream runs past the program (word %d)", at);
-        if (skip == 0 || op == DSP_CORE) break;              /* dsp_runtime.c:321-331 */
-        if ((long long)at + skip > prog_words) return fail(-8, "word %d: opcode longer than the program", at);
-        /* the encoder is trusted by the reference; here nothing is dereferenced before it is known to lie inside
-         * the program (the device library checks the word indices of the finished plan once more) */
-#define LC_NEED(n) do { if ((unsigned)(1 + (n)) > skip) return fail(-8, "word %d: opcode payload shorter than %d words", at, (n)); } while (0)
-#define LC_PROG(off, n) do { long long lo_ = (long long)at + (off); if (lo_ < 0 || lo_ + (n) > prog_words) \
-            return fail(-8, "word %d: program offset %d (+%d) outside the program", at, (int)(off), (int)(n)); } while (0)
-        if (after_mem && op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL && !(copy_on && op == DSP_LOAD_STORE)) {      /* (a list ends nothing) */
-            if (op == DSP_BIQUADS) return fail(-8, "word %d: a STORE_MEM in front of the banks or between two banks is not lowered to the HIP path", at);
-            if (op != DSP_LOAD && op != DSP_LOAD_GAIN && op != DSP_LOAD_MEM && op != DSP_LOAD_MUX)
-                return fail(-8, "word %d: a STORE_MEM that is not the last opcode of its chain is not lowered to the HIP path", at);
-            after_mem = 0;
-        }
-        switch (op) {
-        case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:
-            break;
-        case DSP_LOAD_STORE: {                                /* :738-747, "chain_copy": samples[out] = samples[in], pair by pair */
-            if (!copy_on) goto not_lowered;
-            if (G.ninst > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the program has instances", at);
-            if (G.shard_world > 1) return fail(-8, "word %d: a LOAD_STORE list is not lowered to the HIP path while the core is sharded", at);
-            if (open && cur.n_out == 0)
-                return fail(-8, "word %d: a LOAD_STORE list between a chain's LOAD and its first STORE is not lowered to the HIP path", at);
-            if (!(skip & 1)) return fail(-8, "word %d: a LOAD_STORE list of %u words is no list of pairs (damaged)", at, skip - 1);
-            for (unsigned k = 0; k + 1 < skip; k++)
-                if (a[k] < 0 || a[k] >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", at, a[k], GENERIC_IO_LIMIT);
-            for (unsigned k = 0; k + 2 < skip; k += 2)
-                if (copy_pair(L, a[k], a[k + 1])) return fail(-9, "out of memory");
-            L->ncopy_written += (int)(skip - 1) / 2;
-            break; }
-        case DSP_LOAD_MEM_DATA:
-            if (!mem_on) goto not_lowered;
-            return fail(-8, "word %d: LOAD_MEM_DATA is not lowered to the HIP path (of the memory opcodes only LOAD_MEM and STORE_MEM are)", at);
-        case DSP_LOAD_MEM: case DSP_STORE_MEM: {              /* :750-766, "chain_mem" */
-            if (!mem_on) goto not_lowered;
-            if (format != 2 && format != 4 && format != 6) return fail(-8, "word %d: a memory word is not lowered to the HIP path in format %d", at, format);
-            if (G.ninst > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the program has instances", at);
-            if (G.shard_world > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the core is sharded", at);
-            LC_NEED(1);
-            LC_PROG(a[0], 2);
-            if (!*smap && !(*smap = store_mem_map())) return fail(-9, "out of memory");
-            for (int k = 0; k < 2; k++)
-                if ((*smap)[at + a[0] + k] != 1)
-                    return fail(-8, "word %d: %s target (word %d) is not a free word of a PARAM section: it would "
-                                    "rewrite %s", at, op == DSP_STORE_MEM ? "STORE_MEM" : "LOAD_MEM", at + a[0] + k,
-                                (*smap)[at + a[0] + k] ? "a count, IO number or length other opcodes rely on" : "the opcode stream");
-            if (op == DSP_LOAD_MEM) {
-                if (open) {
-                    if (cur.n_out == 0)
-                        return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
-                    if (push_chain(L, &cur)) return fail(-9, "out of memory");
-                }
-                memset(&cur, 0, sizeof cur);
-                open = 1; fir_op = 0;
-                cur.sec_base = L->nsec;
-                cur.load_mode = AVDSP_LOAD_MEM;
-                cur.mem_word = at + a[0];
-                L->nmem++;
-                break;
-            }
-            if (!open) return fail(-8, "word %d: STORE_MEM without a LOAD", at);
-            if (cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a memory word in a chain with a LOAD_MUX head is not lowered to the HIP path", at);
-            if (cur.load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a STORE_MEM in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
-            if (fir_op) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
-            if (cur.n_out || cur.sat || cur.delay_slot)
-                return fail(-8, "word %d: a STORE_MEM behind a STORE, a SAT0DB or a DSP_DELAY is not lowered to the HIP path", at);
-            cur.mem_word = at + a[0]; cur.mem_store = 1;
-            if (push_chain(L, &cur)) return fail(-9, "out of memory");
-            memset(&cur, 0, sizeof cur);
-            open = 0; fir_op = 0; after_mem = 1;
-            L->nmem++;
-            break; }
-        case DSP_LOAD:                                        /* :565-583 */
-        case DSP_LOAD_GAIN:                                   /* :586-607 */
-            LC_NEED(op == DSP_LOAD_GAIN ? 2 : 1);
-            if (op == DSP_LOAD_GAIN) LC_PROG(a[1], 1);
-            if (a[0] < 0 || a[0] >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", at, a[0], GENERIC_IO_LIMIT);
-            if (open) {
-                if (cur.n_out == 0)
-                    return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
-                if (push_chain(L, &cur)) return fail(-9, "out of memory");
-            }
-            memset(&cur, 0, sizeof cur);
-            open = 1; fir_op = 0;
-            cur.in_io = a[0];
-            cur.sec_base = L->nsec;
-            if (op == DSP_LOAD_GAIN) {
-                cur.load_mode = AVDSP_LOAD_GAIN;
-                cur.gain_bits = p[a[1]].u32;
-                if (mem_on && push_pread(L, (long long)at + a[1], 1)) return fail(-9, "out of memory");
-            }
-            break;
-        case DSP_LOAD_MUX: {                                  /* :871-897: a chain head like LOAD, the accumulator a weighted sum of inputs */
-            if (format != 2 && format != 4 && format != 6)
-                return fail(-8, "word %d: LOAD_MUX is not lowered to the HIP path in format %d", at, format);
-            *mux_damaged = 1;                                 /* (taken back below, once the table has passed) */
-            LC_NEED(2);
-            LC_PROG(a[0], 1);
-            const opcode_t *t = p + a[0];
-            const int n = (short)t[0].i32;                    /* the reference counts in a `short` */
-            if (n < 1) return fail(-8, "word %d: LOAD_MUX table with %d entries", at, n);
-            LC_PROG(a[0], 1 + 2 * n);
-            for (int k = 0; k < n; k++)
-                if (t[1 + 2 * k].i32 < 0 || t[1 + 2 * k].i32 >= GENERIC_IO_LIMIT)
-                    return fail(-8, "word %d: LOAD_MUX entry %d: IO number %d outside [0,%d)", at, k, t[1 + 2 * k].i32, GENERIC_IO_LIMIT);
-            if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
-                return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
-            *mux_damaged = 0;
-            if (mem_on && push_pread(L, (long long)at + a[0], 1 + 2 * n)) return fail(-9, "out of memory");
-            if (open) {
-                if (cur.n_out == 0)
-                    return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", at);
-                if (push_chain(L, &cur)) return fail(-9, "out of memory");
-            }
-            memset(&cur, 0, sizeof cur);
-            open = 1; fir_op = 0;
-            cur.in_io = t[1].i32;
-            cur.sec_base = L->nsec;
-            cur.load_mode = AVDSP_LOAD_MUX;
-            cur.mux_word = (int)(t - G.code) + 1;
-            cur.mux_count = n;
-            cur.mux_result_word = prog_words + a[1];
-            break; }
-        case DSP_BIQUADS: {                                   /* :827-849 */
-            if (open && cur.delay_slot) return fail(-8, "word %d: a DSP_DELAY in front of the banks is not lowered to the HIP path", at);
-            if (!open || cur.n_out || cur.sat || cur.fir_taps)
-                return fail(-8, "word %d: BIQUADS outside the supported LOAD->BIQUADS->FIR->SAT0DB->STORE order", at);
-            LC_NEED(2);
-            LC_PROG(a[1], 2);
-            const opcode_t *bank = p + a[1];
-            int num = (short)bank[0].i32;                     /* callee takes `short num` */
-            if (num < 1) return fail(-8, "word %d: biquad bank with %d sections", at, num);
-            LC_PROG(a[1], G.biquad_offset + (num - 1) * dspBiquadFreqSkip + 5);
-            if (a[0] < 0 || (long long)a[0] + 6ll * num > dspHeaderPtr->dataSize)
-                return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[0], 6 * num, dspHeaderPtr->dataSize);
-            if (mem_on && push_pread(L, (long long)at + a[1], G.biquad_offset + (num - 1) * dspBiquadFreqSkip + 5)) return fail(-9, "out of memory");
-            if (bank[1].i32 != 0)                             /* 0 = bypass, :837 */
-                for (int s = 0; s < num; s++)
-                    if (push_section(L, (int)(bank - G.code) + G.biquad_offset + s * dspBiquadFreqSkip,
-                                     prog_words + a[0] + 6 * s))
-                        return fail(-9, "out of memory");
-            cur.nsec = L->nsec - cur.sec_base;
-            break; }
-        case DSP_FIR: {                                       /* :928-969 */
-            if (open && cur.delay_slot)
-                return fir_tail ? fail(-8, "word %d: a DSP_DELAY in front of the chain's DSP_FIR is not lowered to the HIP path", at)
-                                : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
-            if (!open || cur.n_out || cur.sat)
-                return fail(-8, "word %d: FIR outside the supported chain order", at);
-            if (open && cur.load_mode == AVDSP_LOAD_MEM)
-                return fail(-8, "word %d: a DSP_FIR in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
-            if (!float_alu)
-                return fail(-8, "word %d: DSP_FIR in int64 mode is undefined behaviour in the reference "
-                                "(dsp_firSTD.h:8-35) and is not provided", at);
-            LC_NEED(G.num_freq + 1);
-            fir_op = 1;
-            int off = a[G.freq_index];
-            if (off) {
-                LC_PROG(off, 1);
-                const opcode_t *imp = p + off;
-                int length = imp[0].i32;
-                if (length >> 16)
-                    return fail(-8, "word %d: FIR pure-delay variant is not lowered yet", at);
-                if (length > 0) {
-                    LC_PROG(off, 1 + length);
-                    if (mem_on && push_pread(L, (long long)at + off, 1 + length)) return fail(-9, "out of memory");
-                    if (a[G.num_freq] < 0 || (long long)a[G.num_freq] + length > dspHeaderPtr->dataSize)
-                        return fail(-8, "word %d: data offset %d (+%d) outside the state area (%d words)", at, a[G.num_freq], length, dspHeaderPtr->dataSize);
-                    if (cur.fir_taps) return fail(-8, "word %d: more than one FIR per chain", at);
-                    cur.fir_taps = length;
-                    cur.fir_coef_word = (int)(imp - G.code) + 1;
-                    cur.fir_state_word = prog_words + a[G.num_freq];
-                }
-            }
-            break; }
-        case DSP_SAT0DB:                                      /* :464-475 */
-            if (!open || cur.n_out || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
-            cur.sat = 1;
-            break;
-        case DSP_DELAY_1: case DSP_DELAY_DP:                  /* "chain_delay": only DSP_DELAY is lowered */
-            if (!G.opt_chain_delay) goto not_lowered;
-            return fail(-8, "word %d: %s is not lowered to the HIP path (of the delay lines only DSP_DELAY is)", at, op == DSP_DELAY_1 ? "DSP_DELAY_1" : "DSP_DELAY_DP");
-        case DSP_DELAY: {                                     /* :769-794, "chain_delay": once per chain, behind the banks, on either side of the SAT0DB slot */
-            if (!G.opt_chain_delay) goto not_lowered;
-            if (format != 2 && format != 4 && format != 6) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path in format %d", at, format);
-            if (G.ninst > 1) return fail(-8, "word %d: a DSP_DELAY is not lowered to the HIP path while the program has instances", at);
-            if (!open) return fail(-8, "word %d: a DSP_DELAY in front of the chain's LOAD is not lowered to the HIP path", at);
-            if (cur.n_out) return fail(-8, "word %d: a DSP_DELAY behind a STORE is not lowered to the HIP path", at);
-            if (cur.delay_slot) return fail(-8, "word %d: a second DSP_DELAY in one chain is not lowered to the HIP path", at);
-            if ((fir_op && !fir_tail) || (cur.load_mode == AVDSP_LOAD_MUX && !mux_tail))
-                return fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR or a LOAD_MUX head is not lowered to the HIP path", at);
-            LC_NEED(3);
-            if (a[0] < 0) return fail(-8, "word %d: delay line of negative size %d", at, a[0]);
-            if (a[2]) LC_PROG(a[2], 1);
-            /* with a parameter the first word is the line's size in samples, without it microseconds (the strand lowering's checks) */
-            const long long nline = a[2] ? (long long)a[0] : (long long)(((unsigned long long)(unsigned)a[0] * delay_factor) >> 32);
-            if (a[1] < 0 || (long long)a[1] + 1 + nline > dspHeaderPtr->dataSize)
-                return fail(-8, "word %d: data offset %d (+%lld) outside the state area (%d words)", at, a[1], 1 + nline, dspHeaderPtr->dataSize);
-            cur.delay_slot = cur.sat ? AVDSP_DELAY_B : AVDSP_DELAY_A;
-            cur.delay_word = prog_words + a[1];
-            cur.delay_us_word = a[2] ? at + a[2] : 0;
-            if (mem_on && a[2] && push_pread(L, (long long)at + a[2], 1)) return fail(-9, "out of memory");
-            cur.delay_max = a[0];
-            L->ndelayed++;
-            break; }
-        case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:      /* :478-534, "chain_finish" */
-            if (!finish_on) goto not_lowered;
-            if (!open || cur.n_out || cur.sat || cur.delay_slot == AVDSP_DELAY_B) return fail(-8, "word %d: SAT0DB outside the supported chain order", at);
-            if ((fir_op && !fir_tail) || (cur.load_mode == AVDSP_LOAD_MUX && !mux_tail))
-                return fail(-8, "word %d: a dressed SAT0DB behind a FIR or a LOAD_MUX head is not lowered to the HIP path", at);
-            if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
-            cur.finish = op == DSP_SAT0DB_TPDF ? AVDSP_FINISH_TPDF : op == DSP_SAT0DB_GAIN ? AVDSP_FINISH_GAIN : AVDSP_FINISH_TPDF_GAIN;
-            if (op != DSP_SAT0DB_TPDF) {
-                LC_NEED(1);
-                LC_PROG(a[0], 1);
-                cur.finish_gain_bits = p[a[0]].u32;
-                if (mem_on && push_pread(L, (long long)at + a[0], 1)) return fail(-9, "out of memory");
-            }
-            cur.sat = 1;
-            L->ndressed++;
-            break;
-        case DSP_TPDF_CALC:                                   /* :537-545, "chain_finish": once, in front of the first chain */
-            if (!finish_on) goto not_lowered;
-            if (open || L->nchains || L->tpdf_calc) return fail(-8, "word %d: TPDF_CALC behind the head of the core is not lowered to the HIP path", at);
-            LC_NEED(2);
-            if (a[0] != 0 && a[0] != G.dither) return fail(-8, "word %d: TPDF_CALC of width %d under the default %d is not lowered to the HIP path", at, a[0], G.dither);
-            if (!dither_width_constant()) return fail(-8, "word %d: the program changes its dither width (a TPDF_CALC of another width)", at);
-            if (a[1] < 0 || (long long)a[1] + 2 > dspHeaderPtr->dataSize)
-                return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
-            L->tpdf_calc = 1; L->tpdf_calc_arg = a[0]; L->tpdf_calc_word = prog_words + a[1];
-            break;
-        case DSP_STORE:                                       /* :610-633 */
-            LC_NEED(1);
-            if (a[0] < 0 || a[0] >= GENERIC_IO_LIMIT) return fail(-8, "word %d: IO number %d outside [0,%d)", at, a[0], GENERIC_IO_LIMIT);
-            if (!open) return fail(-8, "word %d: STORE without a LOAD", at);
-            if (cur.n_out == AVDSP_MAX_STORES) return fail(-8, "word %d: more than %d STOREs in a chain", at, AVDSP_MAX_STORES);
-            cur.out_io[cur.n_out++] = a[0];
-            break;
-        default: not_lowered:
-            return fail(-8, "word %d: opcode %d (%s) is not lowered to the HIP path", at, op,
-                        (op >= 0 && op < DSP_MAX_OPCODE) ? dspOpcodeText[op] + (dspOpcodeText[op][0] == '\n') : "?");
-        }
-        p += skip;
-    }
-    if (open) {
-        if (cur.n_out == 0) return fail(-8, "core ends with a chain that is never stored");
-        if (push_chain(L, &cur)) return fail(-9, "out of memory");
-    }
-#undef LC_NEED
-#undef LC_PROG
-    if (copy_on && G.ninst <= 1 && G.shard_world <= 1) {
-        const int rc = drop_dead_stores(L);
-        if (rc) return rc;
-    }
-    if (L->ncp_seen) {
-        const int rc = check_copies(L);
-        if (rc) return rc;
-    }
-    if (L->nchains == 0 && L->ncopy == 0) return fail(-8, "core contains no LOAD..STORE chain");
-    if (L->nmem) {
-        const int rc = check_mem_words(L);
-        if (rc) return rc;
-    }
-    if ((L->ndressed || L->tpdf_calc) && !mux_tail && lowered_has_mux(L))
-        return fail(-8, "dressed finishes or a head TPDF_CALC beside LOAD_MUX heads are not lowered to the HIP path");
-    if (L->ndelayed && !mux_tail && lowered_has_mux(L))
-        return fail(-8, "chains with a DSP_DELAY beside LOAD_MUX heads are not lowered to the HIP path");
-    if (L->ndelayed && mux_tail && lowered_has_mux(L)) {
-        /* ("mux_tail") the mux stage writes a LOAD_MUX result word once per launch, from its last frame, and ahead of chain_tail, where
-         * the reference writes it in every frame between two visits of the line: no line -- index word and samples -- may share a
-         * word with one of them */
-        int clash = 0;
-        for (int i = 0; i < L->nchains && !clash; i++) {
-            const avdsp_chain *c = &L->chains[i];
-            if (!c->delay_slot) continue;
-            const long long lo = c->delay_word;
-            const long long hi = lo + 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
-            for (int j = 0; j < L->nchains && !clash; j++)
-                if (L->chains[j].load_mode == AVDSP_LOAD_MUX) clash = (long long)L->chains[j].mux_result_word < hi && (long long)L->chains[j].mux_result_word + 2 > lo;
-        }
-        if (clash) return fail(-8, "a delay line and a LOAD_MUX result word share words of the state area");
-    }
-    if (L->ndelayed > 1) {
-        /* the chains run side by side: two of them must not share words of a line (the encoder never lets them; the strand lowering
-         * checks the same).  [first word, words] per line, sorted by the first */
-        long long *iv = (long long *)malloc((size_t)L->ndelayed * 2 * sizeof *iv);
-        if (!iv) return fail(-9, "out of memory");
-        int k = 0, clash = 0;
-        for (int i = 0; i < L->nchains; i++) {
-            const avdsp_chain *c = &L->chains[i];
-            if (!c->delay_slot) continue;
-            iv[2 * k] = c->delay_word;
-            iv[2 * k + 1] = 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
-            k++;
-        }
-        qsort(iv, (size_t)k, 2 * sizeof *iv, cmp_ll);
-        for (int i = 1; i < k && !clash; i++) clash = iv[2 * i] < iv[2 * i - 2] + iv[2 * i - 1];
-        free(iv);
-        if (clash) return fail(-8, "two delay lines of the core share words of the state area");
-    }
-    if (L->ndelayed && fir_tail) {
-        /* ("fir_tail") nor may a line share words with the history of a FIR: chain_tail writes the one while a FIR's history is
-         * converted from and to the other.  Lines and histories sorted by their first word; a line must begin behind everything
-         * before it, a history behind every line before it */
-        int nfir = 0;
-        for (int i = 0; i < L->nchains; i++) nfir += L->chains[i].fir_taps != 0;
-        long long *iv = nfir ? (long long *)malloc((size_t)(L->ndelayed + nfir) * 3 * sizeof *iv) : 0;
-        if (nfir && !iv) return fail(-9, "out of memory");
-        int k = 0, clash = 0;
-        for (int i = 0; i < L->nchains && nfir; i++) {
-            const avdsp_chain *c = &L->chains[i];
-            if (c->delay_slot) {
-                iv[3 * k] = c->delay_word;
-                iv[3 * k + 1] = 1 + (c->delay_us_word ? (long long)c->delay_max : (long long)(((unsigned long long)(unsigned)c->delay_max * delay_factor) >> 32));
-                iv[3 * k + 2] = 1; k++;
-            }
-            if (c->fir_taps) { iv[3 * k] = c->fir_state_word; iv[3 * k + 1] = c->fir_taps; iv[3 * k + 2] = 0; k++; }
-        }
-        if (nfir) qsort(iv, (size_t)k, 3 * sizeof *iv, cmp_ll);
-        long long end_line = -1, end_any = -1;
-        for (int i = 0; i < k && !clash; i++) {
-            clash = iv[3 * i] < (iv[3 * i + 2] ? end_any : end_line);
-            const long long e = iv[3 * i] + iv[3 * i + 1];
-            if (iv[3 * i + 2] && e > end_line) end_line = e;
-            if (e > end_any) end_any = e;
-        }
-        free(iv);
-        if (clash) return fail(-8, "a delay line and a FIR's history share words of the state area");
-    }
-    return check_independent(L);
 }
 
 static int lower_core(int format, opcode_t *core, lowered *L) { return lower_core_ex(format, core, L, 0); }
@@ -1593,7 +1700,7 @@ static int scan_generic(int format, opcode_t *core, int end_word, avdsp_generic_
     d->prog_words = S.prog_words;
     d->freq_index = fi; d->num_freq = nf;
     d->biquad_freq_skip = dspBiquadFreqSkip; d->biquad_freq_offset = G.biquad_offset;
-    d->delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));   /* dsp_runtime.c:81-90 */
+    d->delay_line_factor = delay_line_factor();
 
     int nreal = 0;                               /* opcodes that do something */
     for (;;) {
@@ -1669,7 +1776,7 @@ static int scan_generic(int format, opcode_t *core, int end_word, avdsp_generic_
             if (!rc) {
                 /* :769-790: with a parameter the first word is the line's size in samples; without
                  * (fixed delay) it is microseconds and the length follows from the sample rate */
-                long long n = a[2] ? (long long)a[0] : (long long)(((unsigned long long)(unsigned)a[0] * d->delay_line_factor) >> 32);
+                long long n = delay_samples(a[0], a[2] != 0, d->delay_line_factor);
                 rc = gs_data(&S, a[1], 1 + n * (op == DSP_DELAY ? 1 : S.aw));
                 if (!rc) ws_state(&S, a[1], 1 + n * (op == DSP_DELAY ? 1 : S.aw));
             }
@@ -1796,8 +1903,6 @@ static int select_device(void)
     return 0;
 }
 
-/* find or build the device plan of (core, format) */
-/* end_word != 0: the plan of a strand group [core, end_word) of an interpreted core (dspRuntimeBlockAll) */
 /* the program's device copy, made at the first call that needs it */
 static int ensure_device(void)
 {
@@ -1811,16 +1916,7 @@ static int ensure_device(void)
     }
     G.dev_state_valid = 1;
     avdsp_hip_profile_enable(G.dev, G.opt_profile);
-    if (avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_PROFILE_STRIDE, G.opt_profile_stride > 0 ? G.opt_profile_stride : 1) ||
-        avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_OVERLAP, G.opt_overlap) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_ROWS, G.opt_fir_rows) ||
-        avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_READY_WORDS, G.opt_ready_words) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_LANE_HW, G.opt_lane_hw) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SPLIT, G.opt_fir_split) || (G.opt_fir_launch_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LAUNCH, G.opt_fir_launch)) || (G.opt_fir_lean_set && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_LEAN, G.opt_fir_lean)) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_RING_WAIT, G.opt_ring_wait) || (G.opt_fir_ahead != -1 && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_AHEAD, G.opt_fir_ahead)) ||
-        avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_SPLIT, G.opt_host_split) || avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_HOST_PIN, G.opt_host_pin) ||
-        (G.opt_cu_split && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_CU_SPLIT, G.opt_cu_split)) ||
-        (G.opt_group_serial && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_GROUP_FANOUT, 0)) ||
-        (G.opt_frame_server && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER, 1)) ||
-        (!G.opt_fir_shared && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FIR_SHARED, 0)) ||
-        (G.opt_frame_server_idle_us != 1000 && avdsp_hip_prog_set_option(G.dev, AVDSP_OPT_FRAME_SERVER_IDLE_US, G.opt_frame_server_idle_us)) ||
-        (G.ninst > 1 && avdsp_hip_set_instances(G.dev, G.ninst))) {
+    if (replay_options() || (G.ninst > 1 && avdsp_hip_set_instances(G.dev, G.ninst))) {
         hip_fail(); drop_device(); return g_err_code;
     }
     return 0;
@@ -1928,12 +2024,9 @@ static int mux_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **m
     *start = st; *members = mem;
     return ng;
 }
-static int lowered_has_mux(const lowered *L)
-{
-    for (int i = 0; i < L->nchains; i++) if (L->chains[i].load_mode == AVDSP_LOAD_MUX) return 1;
-    return 0;
-}
 
+/* find or build the device plan of (core, format) */
+/* end_word != 0: the plan of a strand group [core, end_word) of an interpreted core (dspRuntimeBlockAll) */
 static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
 {
     if (!dspHeaderPtr || !G.code) { fail(-1, "no program loaded"); return 0; }
@@ -2009,11 +2102,10 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.nsections = sec1 - sec0; d.sec_coef_word = L.coef_word + sec0; d.sec_state_word = L.state_word + sec0;
         d.store_mask = G.store_mask;
         d.tpdf_calc = L.tpdf_calc; d.tpdf_calc_arg = L.tpdf_calc_arg; d.tpdf_calc_result_word = L.tpdf_calc_word;
-        d.delay_line_factor = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));      /* (as lower_core_ex checked the lines' extents) */
-        d.fir_tail = G.opt_fir_tail && (format == 4 || format == 6);
-        d.mux_tail = G.opt_mux_tail;
-        d.chain_mem = G.opt_chain_mem;
-        d.chain_copy = G.opt_chain_copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
+        const lower_gates g = gates_of(format);             /* (as the lowering saw them: it checked the lines' extents with this factor) */
+        d.delay_line_factor = g.delay_factor;
+        d.fir_tail = g.fir_tail; d.mux_tail = g.mux_tail; d.chain_mem = g.mem;
+        d.chain_copy = g.copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
             const int ng = fir_groups(d.chains, d.nchains, &fg_start, &fg_chains);
@@ -2091,350 +2183,252 @@ int dspRuntimeKernelTime(int kind, double *total_ms, int *launches)
     return 0;
 }
 
-/* Host-only: lowers the core (no device is touched) and reports what the plan would contain. */
+/* ---- the core reports: host-only calls that lower a core (no device is touched) and count over what the plan would contain ----
+ * What they share: the program the core belongs to becomes current and the call's arguments are checked
+ * (report_preamble); the core is lowered unless "generic" keeps every core on the interpreter or the call has nothing to report in this
+ * format; a core the chain lowering refuses (-8) reports zeros -- L is empty, [lo, hi) is [0, 0), and dspRuntimeLastError() keeps the
+ * lowering's text --, any other failure is the call's.  [lo, hi) are the chains this process runs (dspRuntimeSetShard). */
+typedef struct { lowered L; int lowered_rc, damaged, lo, hi; } core_report;
+
+static int report_preamble(int format, opcode_t *core)
+{
+    (void)ctx_of(core);
+    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
+    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
+    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
+    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    return 0;
+}
+
+/* 0: count over R (core_report_close() it afterwards), else the call's return code.  lowered_rc: 0 lowered, -8 not (what the lowering
+ * said, or nothing was asked), damaged: the refusal is a LOAD_MUX table that cannot be used */
+static int core_report_open(int format, opcode_t *core, int lower, core_report *R)
+{
+    memset(R, 0, sizeof *R);
+    R->lowered_rc = -8;
+    const int rc = report_preamble(format, core);
+    if (rc || G.opt_generic || !lower) return rc;
+    R->lowered_rc = lower_core_ex(format, core, &R->L, &R->damaged);
+    if (R->lowered_rc == 0) shard_range(R->L.nchains, G.shard_world, G.shard_rank, &R->lo, &R->hi);
+    else lowered_free(&R->L);
+    return R->lowered_rc == -8 ? 0 : R->lowered_rc;
+}
+
+static void core_report_close(core_report *R) { lowered_free(&R->L); }
+
+static void put(int *out, int value) { if (out) *out = value; }
+
+/* The chains of the whole core, their longest cascade and FIR; a core the chain lowering does not take is offered to the general
+ * interpreter's scan, whose result is the call's. */
 int dspRuntimeCoreInfo(int format, opcode_t *core, int *nchains, int *max_sections, int *max_taps)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int nc = 0, ms = 0, mt = 0, rc = -8;
-    if (!G.opt_generic) {
-        lowered L;
-        rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            nc = L.nchains;
-            for (int i = 0; i < L.nchains; i++) {
-                if (L.chains[i].nsec > ms) ms = L.chains[i].nsec;
-                if (L.chains[i].fir_taps > mt) mt = L.chains[i].fir_taps;
-            }
-        }
-        lowered_free(&L);
+    core_report R;
+    int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int ms = 0, mt = 0;
+    for (int i = 0; i < R.L.nchains; i++) {
+        if (R.L.chains[i].nsec > ms) ms = R.L.chains[i].nsec;
+        if (R.L.chains[i].fir_taps > mt) mt = R.L.chains[i].fir_taps;
     }
-    if (rc == -8) {
+    const int nc = R.L.nchains;
+    core_report_close(&R);
+    if (R.lowered_rc) {
         avdsp_generic_desc gd;
         rc = scan_generic(format, core, 0, &gd, 0);
+        if (rc) return rc;
     }
-    if (rc) return rc;
-    if (nchains) *nchains = nc;
-    if (max_sections) *max_sections = ms;
-    if (max_taps) *max_taps = mt;
+    put(nchains, nc); put(max_sections, ms); put(max_taps, mt);
     return 0;
 }
 
-/* Host-only: the groups of AVDSP_FIR_GROUP_MIN chains or more that share one impulse bank at the current rate, among the chains of the
- * core this process runs (dspRuntimeSetShard) -- what fir_shared takes.  No device is touched.  A core that is not a set
- * of chains, or a format without the chain FIR (2, 3, 5), has none. */
+/* The groups of AVDSP_FIR_GROUP_MIN chains or more that share one impulse bank at the current rate, among the chains of the core this
+ * process runs -- what fir_shared takes.  A core that is not a set of chains, or a format without the chain FIR (2, 3,
+ * 5), has none. */
 int dspRuntimeFirGroupInfo(int format, opcode_t *core, int *groups, int *grouped_chains, int *largest_group)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int ng = 0, nc = 0, big = 0;
-    if (!G.opt_generic && (format == 4 || format == 6)) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            int32_t *st = 0, *mem = 0;
-            ng = fir_groups(L.chains + lo, hi - lo, &st, &mem);
-            if (ng < 0) { lowered_free(&L); return fail(-9, "out of memory"); }
-            for (int g = 0; g < ng; g++) {
-                const int n = st[g + 1] - st[g];
-                nc += n;
-                if (n > big) big = n;
-            }
-            free(st); free(mem);
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    core_report R;
+    const int rc = core_report_open(format, core, format == 4 || format == 6, &R);
+    if (rc) return rc;
+    int32_t *st = 0, *mem = 0;
+    const int ng = R.lowered_rc ? 0 : fir_groups(R.L.chains + R.lo, R.hi - R.lo, &st, &mem);
+    core_report_close(&R);
+    if (ng < 0) return fail(-9, "out of memory");
+    int nc = 0, big = 0;
+    for (int g = 0; g < ng; g++) {
+        const int n = st[g + 1] - st[g];
+        nc += n;
+        if (n > big) big = n;
     }
-    if (groups) *groups = ng;
-    if (grouped_chains) *grouped_chains = nc;
-    if (largest_group) *largest_group = big;
+    free(st); free(mem);
+    put(groups, ng); put(grouped_chains, nc); put(largest_group, big);
     return 0;
 }
 
-/* Host-only: the LOAD_MUX chain heads among the chains of the core this process runs (dspRuntimeSetShard), the mix groups of
- * AVDSP_MUX_GROUP_MIN chains or more that mux_tile takes, the chains in them and the longest list.  No device is
- * touched.  A core that is not a set of chains (formats 3 and 5 with a LOAD_MUX among them) has none; a damaged table is -8. */
+/* The LOAD_MUX chain heads among the chains of the core this process runs, the mix groups of AVDSP_MUX_GROUP_MIN chains or more that
+ * mux_tile takes, the chains in them and the longest list.  A core that is not a set of chains (formats 3 and 5 with a
+ * LOAD_MUX among them) has none; a damaged table is -8. */
 int dspRuntimeMuxInfo(int format, opcode_t *core, int *mux_chains, int *groups, int *grouped_chains, int *longest_list)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int nm = 0, ng = 0, nc = 0, big = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        int damaged = 0;
-        const int rc = lower_core_ex(format, core, &L, &damaged);
-        if (rc == 0) {
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++)
-                if (L.chains[i].load_mode == AVDSP_LOAD_MUX) { nm++; if (L.chains[i].mux_count > big) big = L.chains[i].mux_count; }
-            int32_t *st = 0, *mem = 0;
-            ng = mux_groups(L.chains + lo, hi - lo, &st, &mem);
-            if (ng < 0) { lowered_free(&L); return fail(-9, "out of memory"); }
-            if (ng) nc = st[ng];
-            free(st); free(mem);
-        }
-        lowered_free(&L);
-        if (rc == -8 && damaged) return rc;
-        if (rc && rc != -8) return rc;
-    }
-    if (mux_chains) *mux_chains = nm;
-    if (groups) *groups = ng;
-    if (grouped_chains) *grouped_chains = nc;
-    if (longest_list) *longest_list = big;
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    if (R.lowered_rc && R.damaged) return R.lowered_rc;
+    int nm = 0, big = 0;
+    for (int i = R.lo; i < R.hi; i++)
+        if (R.L.chains[i].load_mode == AVDSP_LOAD_MUX) { nm++; if (R.L.chains[i].mux_count > big) big = R.L.chains[i].mux_count; }
+    int32_t *st = 0, *mem = 0;
+    const int ng = R.lowered_rc ? 0 : mux_groups(R.L.chains + R.lo, R.hi - R.lo, &st, &mem);
+    core_report_close(&R);
+    if (ng < 0) return fail(-9, "out of memory");
+    const int nc = ng ? st[ng] : 0;
+    free(st); free(mem);
+    put(mux_chains, nm); put(groups, ng); put(grouped_chains, nc); put(longest_list, big);
     return 0;
 }
 
-/* Host-only: what "chain_finish" makes of the core -- the chains with a dressed finish (SAT0DB_TPDF / _GAIN / _TPDF_GAIN) among the
- * chains this process runs (dspRuntimeSetShard) and whether the core begins with a DSP_TPDF_CALC that dither_block runs (DESIGN.md
- * 4.2f).  No device is touched.  A core that is not a set of chains has neither. */
+/* What "chain_finish" makes of the core -- the chains with a dressed finish (SAT0DB_TPDF / _GAIN / _TPDF_GAIN) among the chains this
+ * process runs and whether the core begins with a DSP_TPDF_CALC that dither_block runs. */
 int dspRuntimeFinishInfo(int format, opcode_t *core, int *dressed_chains, int *tpdf_calc)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int nd = 0, calc = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++) nd += L.chains[i].finish != 0;
-            calc = L.tpdf_calc;
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
-    }
-    if (dressed_chains) *dressed_chains = nd;
-    if (tpdf_calc) *tpdf_calc = calc;
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int nd = 0;
+    for (int i = R.lo; i < R.hi; i++) nd += R.L.chains[i].finish != 0;
+    put(dressed_chains, nd); put(tpdf_calc, R.L.tpdf_calc);
+    core_report_close(&R);
     return 0;
 }
 
-/* Host-only: what "chain_delay" makes of the core -- the chains with a lowered DSP_DELAY among the chains this process runs
- * (dspRuntimeSetShard), and the longest of their lines in samples at the current rate (a parameter form counts with the delay its
- * program word asks for now, clamped to the line's size; a line of 0 samples is a bypass).  No device is touched.  A core that is
- * not a set of chains has neither. */
+/* What "chain_delay" makes of the core -- the chains with a lowered DSP_DELAY among the chains this process runs, and the longest of
+ * their lines in samples at the current rate (a parameter form counts with the delay its program word asks for now, clamped to the
+ * line's size; a line of 0 samples is a bypass). */
 int dspRuntimeDelayInfo(int format, opcode_t *core, int *chains_delayed, int *longest_line)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    const unsigned fac = delay_line_factor();
     int nd = 0, longest = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            const unsigned fac = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++) {
-                const avdsp_chain *c = &L.chains[i];
-                if (!c->delay_slot) continue;
-                nd++;
-                unsigned n;
-                if (!c->delay_us_word) n = (unsigned)(((unsigned long long)(unsigned)c->delay_max * fac) >> 32);
-                else {
-                    n = (unsigned)(((unsigned long long)(unsigned short)G.code[c->delay_us_word].i32 * fac) >> 32);
-                    if (n > (unsigned)c->delay_max) n = (unsigned)c->delay_max;
-                }
-                if ((int)n > longest) longest = (int)n;
-            }
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    for (int i = R.lo; i < R.hi; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        if (!c->delay_slot) continue;
+        nd++;
+        unsigned n = (unsigned)delay_samples(c->delay_us_word ? (unsigned short)G.code[c->delay_us_word].i32 : c->delay_max, 0, fac);
+        if (c->delay_us_word && n > (unsigned)c->delay_max) n = (unsigned)c->delay_max;
+        if ((int)n > longest) longest = (int)n;
     }
-    if (chains_delayed) *chains_delayed = nd;
-    if (longest_line) *longest_line = longest;
+    core_report_close(&R);
+    put(chains_delayed, nd); put(longest_line, longest);
     return 0;
 }
 
-/* Host-only: what "fir_tail" makes of the core -- the handed FIR chains (a DSP_FIR with taps at the current rate, and behind it a
- * DSP_DELAY and / or a dressed finish) among the chains this process runs (dspRuntimeSetShard), and how many of them have the delay
- * (DESIGN.md 4.2h).  No device is touched.  A core that is not a set of chains has neither. */
+/* What "fir_tail" makes of the core -- the handed FIR chains (a DSP_FIR with taps at the current rate, and behind it a DSP_DELAY and / or
+ * a dressed finish) among the chains this process runs, and how many of them have the delay. */
 int dspRuntimeFirTailInfo(int format, opcode_t *core, int *handed_chains, int *of_them_delayed)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
     int nh = 0, nd = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++) {
-                const avdsp_chain *c = &L.chains[i];
-                if (!c->fir_taps || (!c->finish && !c->delay_slot)) continue;
-                nh++;
-                nd += c->delay_slot != 0;
-            }
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    for (int i = R.lo; i < R.hi; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        if (!c->fir_taps || (!c->finish && !c->delay_slot)) continue;
+        nh++;
+        nd += c->delay_slot != 0;
     }
-    if (handed_chains) *handed_chains = nh;
-    if (of_them_delayed) *of_them_delayed = nd;
+    core_report_close(&R);
+    put(handed_chains, nh); put(of_them_delayed, nd);
     return 0;
 }
 
-/* Host-only: what "mux_tail" makes of the core -- among the chains this process runs (dspRuntimeSetShard) of a core that holds
- * LOAD_MUX chain heads: those with a dressed finish, those with a DSP_DELAY, and the LOAD_MUX chains without sections and FIR that
- * the mux stage itself finishes (a dressed finish, no delay) or hands to chain_tail (a delay) -- the chains that make the stage's
- * launches the TAIL forms.  No device is touched.  A core without LOAD_MUX heads, or one that is not a set of
- * chains, has none. */
+/* What "mux_tail" makes of the core -- among the chains this process runs of a core that holds LOAD_MUX chain heads: those with a
+ * dressed finish, those with a DSP_DELAY, and the LOAD_MUX chains without sections and FIR that the mux stage itself finishes (a dressed
+ * finish, no delay) or hands to chain_tail (a delay) -- the chains that make the stage's launches the TAIL forms.  A
+ * core without LOAD_MUX heads has none. */
 int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *delayed_chains, int *stage_finished_or_handed)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
     int nf = 0, nd = 0, ns = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0 && lowered_has_mux(&L)) {
-            int lo, hi;
-            shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++) {
-                const avdsp_chain *c = &L.chains[i];
-                nf += c->finish != 0;
-                nd += c->delay_slot != 0;
-                ns += c->load_mode == AVDSP_LOAD_MUX && !c->nsec && !c->fir_taps && (c->finish || c->delay_slot);
-            }
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    const int hi = lowered_has_mux(&R.L) ? R.hi : R.lo;
+    for (int i = R.lo; i < hi; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        nf += c->finish != 0;
+        nd += c->delay_slot != 0;
+        ns += c->load_mode == AVDSP_LOAD_MUX && !c->nsec && !c->fir_taps && (c->finish || c->delay_slot);
     }
-    if (dressed_chains) *dressed_chains = nf;
-    if (delayed_chains) *delayed_chains = nd;
-    if (stage_finished_or_handed) *stage_finished_or_handed = ns;
+    core_report_close(&R);
+    put(dressed_chains, nf); put(delayed_chains, nd); put(stage_finished_or_handed, ns);
     return 0;
 }
 
-/* Host-only: what "chain_mem" makes of the core -- its trunks (chains that end in STORE_MEM), its branches (chains that start with
- * LOAD_MEM) and, of those, the ones whose word no chain of the core writes: they read what the mirror holds when a launch starts
- * (DESIGN.md 4.2j).  No device is touched.  A core that is not a set of chains has none. */
+/* What "chain_mem" makes of the core -- its trunks (chains that end in STORE_MEM), its branches (chains that start with LOAD_MEM) and,
+ * of those, the ones whose word no chain of the core writes: they read what the mirror holds when a launch starts.
+ * Counted over the whole core: a core with memory words is never sharded. */
 int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
     int nt = 0, nb = 0, nc = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0 && L.nmem) {
-            for (int i = 0; i < L.nchains; i++) {
-                const avdsp_chain *c = &L.chains[i];
-                if (c->mem_store) nt++;
-                if (c->load_mode != AVDSP_LOAD_MEM) continue;
-                nb++;
-                int written = 0;
-                for (int j = 0; j < L.nchains && !written; j++) written = L.chains[j].mem_store && L.chains[j].mem_word == c->mem_word;
-                nc += !written;
-            }
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    for (int i = 0; i < R.L.nchains; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        if (c->mem_store) nt++;
+        if (c->load_mode != AVDSP_LOAD_MEM) continue;
+        nb++;
+        int written = 0;
+        for (int j = 0; j < R.L.nchains && !written; j++) written = R.L.chains[j].mem_store && R.L.chains[j].mem_word == c->mem_word;
+        nc += !written;
     }
-    if (trunks) *trunks = nt;
-    if (branches) *branches = nb;
-    if (constant_branches) *constant_branches = nc;
+    core_report_close(&R);
+    put(trunks, nt); put(branches, nb); put(constant_branches, nc);
     return 0;
 }
 
-/* Host-only: what "chain_copy" makes of the core's DSP_LOAD_STORE lists -- the pairs the core writes and the pairs the
- * plan copies once forwarding, the last writer and self-copies are resolved.  No device is touched.  A core without lists and a core
- * the interpreter runs report zeros. */
+/* What "chain_copy" makes of the core's DSP_LOAD_STORE lists -- the pairs the core writes and the pairs the plan copies
+ * once forwarding, the last writer and self-copies are resolved (a core with lists is never sharded). */
 int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int np = 0, nl = 0;
-    if (!G.opt_generic) {
-        lowered L;
-        const int rc = lower_core(format, core, &L);
-        if (rc == 0) { np = L.ncopy_written; nl = L.ncopy; }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
-    }
-    if (pairs) *pairs = np;
-    if (live) *live = nl;
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    put(pairs, R.L.ncopy_written); put(live, R.L.ncopy);
+    core_report_close(&R);
     return 0;
 }
 
-/* Host-only: which chains of the core this process runs under the current dspRuntimeSetShard, and the IO numbers
+/* Which chains of the core this process runs under the current dspRuntimeSetShard, and the IO numbers
  * they load and store -- what the block call's windows must cover, so a host can cut its column slice of a
  * [frames][channels] block for ANY loaded program.  total == 0: not a chain core (it runs whole on every rank). */
+static void span(int *min, int *max, int io)
+{
+    if (*max < *min || io < *min) *min = io;
+    if (*max < *min || io > *max) *max = io;
+}
+
 int dspRuntimeShardInfo(int format, opcode_t *core, int *total_chains, int *first_chain, int *nchains,
                         int *in_io_min, int *in_io_max, int *out_io_min, int *out_io_max)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    int tot = 0, lo = 0, hi = 0, imin = 0, imax = -1, omin = 0, omax = -1;
-    if (!G.opt_generic) {
-        lowered L;
-        int rc = lower_core(format, core, &L);
-        if (rc == 0) {
-            tot = L.nchains;
-            shard_range(tot, G.shard_world, G.shard_rank, &lo, &hi);
-            for (int i = lo; i < hi; i++) {
-                const avdsp_chain *c = &L.chains[i];
-                for (int k = 0; k < (c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : c->load_mode == AVDSP_LOAD_MEM ? 0 : 1); k++) {      /* (a LOAD_MUX head: every IO of its list; a LOAD_MEM branch: none) */
-                    const int io = c->load_mode == AVDSP_LOAD_MUX ? G.code[c->mux_word + 2 * k].i32 : c->in_io;
-                    if (imax < imin || io < imin) imin = io;
-                    if (imax < imin || io > imax) imax = io;
-                }
-                for (int k = 0; k < c->n_out; k++) {
-                    if (omax < omin || c->out_io[k] < omin) omin = c->out_io[k];
-                    if (omax < omin || c->out_io[k] > omax) omax = c->out_io[k];
-                }
-            }
-            for (int i = 0; i < L.ncopy; i++) {               /* ("chain_copy": the live pairs read and write the windows too) */
-                if (imax < imin || L.cp_src[i] < imin) imin = L.cp_src[i];
-                if (imax < imin || L.cp_src[i] > imax) imax = L.cp_src[i];
-                if (omax < omin || L.cp_dst[i] < omin) omin = L.cp_dst[i];
-                if (omax < omin || L.cp_dst[i] > omax) omax = L.cp_dst[i];
-            }
-        }
-        lowered_free(&L);
-        if (rc && rc != -8) return rc;
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int imin = 0, imax = -1, omin = 0, omax = -1;
+    for (int i = R.lo; i < R.hi; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        /* (a LOAD_MUX head: every IO of its list; a LOAD_MEM branch: none) */
+        for (int k = 0; k < (c->load_mode == AVDSP_LOAD_MUX ? c->mux_count : c->load_mode == AVDSP_LOAD_MEM ? 0 : 1); k++)
+            span(&imin, &imax, c->load_mode == AVDSP_LOAD_MUX ? G.code[c->mux_word + 2 * k].i32 : c->in_io);
+        for (int k = 0; k < c->n_out; k++) span(&omin, &omax, c->out_io[k]);
     }
-    if (total_chains) *total_chains = tot;
-    if (first_chain) *first_chain = lo;
-    if (nchains) *nchains = hi - lo;
-    if (in_io_min) *in_io_min = imin;
-    if (in_io_max) *in_io_max = imax;
-    if (out_io_min) *out_io_min = omin;
-    if (out_io_max) *out_io_max = omax;
+    for (int i = 0; i < R.L.ncopy; i++) {                     /* ("chain_copy": the live pairs read and write the windows too) */
+        span(&imin, &imax, R.L.cp_src[i]);
+        span(&omin, &omax, R.L.cp_dst[i]);
+    }
+    put(total_chains, R.L.nchains); put(first_chain, R.lo); put(nchains, R.hi - R.lo);
+    put(in_io_min, imin); put(in_io_max, imax); put(out_io_min, omin); put(out_io_max, omax);
+    core_report_close(&R);
     return 0;
 }
 
@@ -2812,8 +2806,7 @@ static int strand_lower(int format, int start, int end, strand_plan *S)
             case AVDSP_SOP_STORE_MEM: SL_WORD(w[0], aw, 2); row[o->a0] = here + w[0]; break;
             case AVDSP_SOP_DELAY: case AVDSP_SOP_DELAY_DP: {
                 /* :769-790: with a parameter the first word is the line's size in samples, without it microseconds (scan_generic) */
-                const unsigned dfac = (unsigned)(4294.967296 * (double)dspConvertFrequencyFromIndex(G.fs_index));
-                const long long nline = w[2] ? (long long)w[0] : (long long)(((unsigned long long)(unsigned)w[0] * dfac) >> 32);
+                const long long nline = delay_samples(w[0], w[2] != 0, delay_line_factor());
                 const long long words = 1 + nline * (o->op == AVDSP_SOP_DELAY_DP ? aw : 1);
                 if (w[0] < 0) { rc = -8; break; }
                 if (w[1] < 0 || w[1] + words > dspHeaderPtr->dataSize) { rc = -8; break; }
@@ -2924,12 +2917,7 @@ static int strand_lanes_from(void) { return G.opt_strand_lanes >= 2 ? 2 : 65; }
  * stay with the interpreter; ops: micro-operations per strand) */
 int dspRuntimeStrandInfo(int format, opcode_t *core, int *strands, int *ops, int *prefix_words)
 {
-    (void)ctx_of(core);
-    if (!dspHeaderPtr || !G.code) return fail(-1, "no program loaded");
-    if (!G.have_rate) return fail(-1, "dspRuntimeReset(fs) has not selected a sample rate yet");
-    if (format < 2 || format > 6) return fail(-1, "DSP_FORMAT %d is not one of 2..6", format);
-    if (core < G.code || core >= G.code + dspHeaderPtr->totalLength) return fail(-1, "core pointer outside the loaded program");
-    if (ensure_encoding(format)) return g_err_code;
+    if (report_preamble(format, core) || ensure_encoding(format)) return g_err_code;
     opcode_t *begin = dspFindCoreBegin(core);
     strand_plan S;
     int w = 0, e = 0;
