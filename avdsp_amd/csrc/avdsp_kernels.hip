@@ -4574,21 +4574,53 @@ struct avdsp_hip_prog {
     int fir_shared = 1;                  /* chains of one impulse bank as the columns of fir_shared; 0: every chain on fir_launch's kernels */
     int sh_chains_now = 0, sh_groups_now = 0;        /* of the latest FIR launch: chains and groups fir_shared took */
     int sh_rows_now = 0;                             /* ... and the R of the fir_shared<FMT, R> that ran (0: the launch did not take the path) */
-    hipStream_t s_bq = nullptr;
-    hipStream_t s_fir[2] = {nullptr, nullptr};           /* "overlap" 2: the FIRs of consecutive blocks in turn */
     static constexpr int kAhead = kRingAhead;     /* cascade k waits for FIR k - kAhead: it may run under FIR k - 2 and be done before FIR k - 1 ends */
-    hipEvent_t ev_bq[kAhead] = {nullptr, nullptr, nullptr}, ev_fir[kAhead] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fir_now[kAhead] = {nullptr, nullptr, nullptr};   /* what stands for "FIR of this slot has ended": ev_fir[slot], or the stop event of the kernel timer that rode on that launch (no second event on the stream) */
-    hipEvent_t last_ride_stop = nullptr; /* ProfileScope::ride: the stop event the latest timed launch carries */
+    /* what the overlap arrangement alone owns (launch_all and its enqueuers): its streams, the events of the kAhead slots
+     * the blocks take in turn, the staging blocks, what the probes found */
+    struct OverlapState {
+        hipStream_t s_bq = nullptr;                       /* the cascades' stream */
+        hipStream_t s_fir[2] = {nullptr, nullptr};        /* "overlap" 2, "fir_ahead": the FIRs of consecutive blocks in turn */
+        hipEvent_t ev_bq[kAhead] = {nullptr, nullptr, nullptr}, ev_fir[kAhead] = {nullptr, nullptr, nullptr};
+        hipEvent_t ev_fir_now[kAhead] = {nullptr, nullptr, nullptr};   /* what stands for "FIR of this slot has ended": ev_fir[slot], or the stop event of the kernel timer that rode on that launch (no second event on the stream) */
+        bool ev_fir_set[kAhead] = {false, false, false};
+        hipEvent_t ev_out[kAhead] = {nullptr, nullptr, nullptr};        /* behind the copy that last read the slot's staging block, on its caller's stream */
+        bool ev_out_set[kAhead] = {false, false, false};
+        DevArr<unsigned> stage[kAhead]; long long stage_words = 0;      /* the staging block of a slot: kFirChunk frames of the widest output window so far */
+        hipEvent_t launch_ev[16] = {};                    /* "fir_launch" 2: a small ring of start / stop event pairs */
+        unsigned launch_ev_next = 0;
+        unsigned long long blk = 0;                       /* overlapped launches so far: the next one's slot is blk % kAhead */
+        int side_by_side = 0;                             /* kernels of the FIRs' stream and of the cascades' have been seen to run at once (probe_side_by_side): without that no ready words */
+        std::vector<std::pair<hipStream_t, int>> probed;  /* ... per stream the FIRs were launched on */
+        std::vector<hipStream_t> retired;                 /* cascades' streams that shared a hardware queue with a FIRs' stream (probe_side_by_side) */
+        int remade = 0;                                   /* ... how many times the cascades' stream was made anew */
+        std::vector<std::pair<hipStream_t, int>> ahead_probed;       /* per caller's stream: the four streams of a staged launch were seen to run at once (ahead_streams_apart) */
+        int ahead_apart = 0, ahead_remade = 0;            /* ... of the latest staged launch's; streams made anew for it */
+        /* nothing of the calls so far is waited for any more (the device is idle) */
+        void forget_events() { for (bool &f : ev_fir_set) f = false; for (bool &f : ev_out_set) f = false; }
+        /* ... nor a FIR's end that `recycled`, a kernel timer's stop event, stood for (that event goes back to the pool); whether there was one */
+        bool forget_events(hipEvent_t recycled)
+        {
+            bool any = false;
+            for (int k = 0; k < kAhead; k++) if (ev_fir_now[k] == recycled) { ev_fir_now[k] = ev_fir[k]; ev_fir_set[k] = false; any = true; }
+            return any;
+        }
+        /* the side streams and the events between them go (the device is idle): overlap_ready makes them anew, every probe is void */
+        void drop_streams()
+        {
+            if (s_bq) { (void)hipStreamDestroy(s_bq); s_bq = nullptr; }
+            for (auto &fs : s_fir) if (fs) { (void)hipStreamDestroy(fs); fs = nullptr; }
+            for (int i = 0; i < kAhead; i++) {
+                if (ev_bq[i]) { (void)hipEventDestroy(ev_bq[i]); ev_bq[i] = nullptr; }
+                if (ev_fir[i]) { (void)hipEventDestroy(ev_fir[i]); ev_fir[i] = nullptr; }
+                ev_fir_set[i] = false; ev_fir_now[i] = nullptr;
+            }
+            probed.clear(); ahead_probed.clear();
+        }
+    } ov;
     /* "fir_ahead" (launch_all): under "overlap" 1 the FIRs of consecutive blocks on s_fir[] in turn, each into a staging
      * block of the library's own; a copy on the caller's stream behind the FIR's event moves its columns into the caller's block.
      * -1 by the plan (fir_ahead_by_plan), 0 never, 1 whenever it is legal */
     int fir_ahead = -1, fir_ahead_now = 0;                /* (fir_ahead_now: what the latest launch did) */
-    DevArr<unsigned> stage[kAhead]; long long stage_words = 0;      /* the staging block of a slot: kFirChunk frames of the widest output window so far */
-    hipEvent_t ev_out[kAhead] = {nullptr, nullptr, nullptr};        /* behind the copy that last read the slot's staging block, on its caller's stream */
-    bool ev_out_set[kAhead] = {false, false, false};
-    std::vector<std::pair<hipStream_t, int>> ahead_probed;       /* per caller's stream: the four streams of a staged launch were seen to run at once (ahead_streams_apart) */
-    int ahead_apart = 0, ahead_remade = 0;                /* ... of the latest staged launch's; streams made anew for it */
     bool call_in_place = false;                           /* the block call being run has its input and output windows in the same memory (avdsp_hip_run_block) */
     /* How an un-timed FIR launch of the overlap mode is enqueued (launch_all), by what was measured:
      *   1  the event the next cascades wait for rides on the dispatch's own completion signal (hipExtLaunchKernel's stop slot) instead
@@ -4598,19 +4630,13 @@ struct avdsp_hip_prog {
      *      1024 chains 0.1559 -> 0.1464, cfg5's 2048-chain shard 0.1575 -> 0.1477 -- the few microseconds the queue spends on the
      *      marker are microseconds the starved cascade has the chip to itself; on the long launches it only costs (0.5078 -> 0.5202);
      *   0  a plain launch and a recorded event (round 3).
-     * -1 (default): 2 for plans of at most 6 M taps in all (chains x taps), else 1.  AVDSP_OPT_FIR_LAUNCH / AVDSP_FIR_LAUNCH_MODE. */
-    int fir_launch_mode = -1, fir_mode_now = 0;
-    hipEvent_t launch_ev[16] = {};       /* ... mode 2: a small ring of start / stop event pairs */
-    unsigned launch_ev_next = 0;
+     * -1 (default): by the plan and the block (launch_route: kPairLaunchTaps, kPairLaunchFrames).  AVDSP_OPT_FIR_LAUNCH / AVDSP_FIR_LAUNCH_MODE. */
+    int fir_launch_mode = -1;
     int lane_hw = 1;                     /* formats 3 / 5: the hardware's toward-zero product where it is the reference's (fir_lane_hw, chain_rows' fast steps); 0: the integer products throughout */
     int ready_words = -1;                /* "overlap": how the FIR of a block finds its cascades' block in the rings: 0 an event between the two queues, 1 ready words published by
                                             the cascade's waves (slower everywhere), 2 ready words set by a kernel behind the cascade; -1 (default): 2 where the FIR is the
                                             bound, else 0 (launch_all) */
-    int ready_mode_now = 0;              /* (the mode of the launch being made) */
-    int side_by_side = 0;                /* kernels of the FIRs' stream and of the cascades' have been seen to run at once (probe_side_by_side): without that no ready words */
-    std::vector<std::pair<hipStream_t, int>> probed;      /* ... per stream the FIRs were launched on */
-    std::vector<hipStream_t> retired;                     /* cascades' streams that shared a hardware queue with a FIRs' stream (probe_side_by_side) */
-    int remade = 0;                                       /* ... how many times the cascades' stream was made anew */
+    int ready_mode_now = 0;              /* (the mode the latest overlapped launch took: "ready_mode", ready_check's text; nothing reads it to make a launch) */
     /* cascade launch groups of one plan side by side (round 5: launch_cascades) */
     hipStream_t bq_side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t bq_fork = nullptr, bq_join[3] = {nullptr, nullptr, nullptr};
@@ -4639,8 +4665,6 @@ struct avdsp_hip_prog {
     hipEvent_t ev_unpack = nullptr;      /* ... recorded behind the library's own pcm_unpack */
     int host_split = 0;                  /* frames per piece of a host block (0 = one piece; pieces only pay with host_pin) */
     int host_pin = 0;                    /* pin the caller's buffers in place and remember them: only for a host that keeps them allocated */
-    bool ev_fir_set[kAhead] = {false, false, false};
-    unsigned long long blk = 0;
     /* the frame server (frame_server): "frame_server", "frame_server_idle_us" and the counters behind the read-only keys */
     int fs_on = 0, fs_idle_us = 1000;
     unsigned *fs_h = nullptr, *fs_d = nullptr;           /* the mailbox: mapped pinned host words (fsrv::kWords) */
@@ -4782,8 +4806,7 @@ struct ProfileScope {
     {
         if (prog->spans.size() >= 65536) {                 /* nobody reads the timers: forget the oldest half (their events go back to the pool) */
             for (size_t i = 0; i < 32768; i++) {
-                for (int k = 0; k < avdsp_hip_prog::kAhead; k++)
-                    if (prog->ev_fir_now[k] == prog->spans[i].b) { (void)hipEventSynchronize(prog->spans[i].b); prog->ev_fir_now[k] = prog->ev_fir[k]; prog->ev_fir_set[k] = false; }
+                if (prog->ov.forget_events(prog->spans[i].b)) (void)hipEventSynchronize(prog->spans[i].b);
                 prog->free_events.push_back(prog->spans[i].a); prog->free_events.push_back(prog->spans[i].b);
             }
             prog->spans.erase(prog->spans.begin(), prog->spans.begin() + 32768);
@@ -4796,7 +4819,6 @@ struct ProfileScope {
         s = take_event(prog); e = take_event(prog);
         if (!s || !e) { if (s) prog->free_events.push_back(s); if (e) prog->free_events.push_back(e); return false; }
         keep(s, e, false);
-        prog->last_ride_stop = e;
         return true;
     }
     void begin() { if (on && !a && (a = take_event(prog))) (void)hipEventRecord(a, stream); }
@@ -4810,19 +4832,22 @@ struct ProfileScope {
     }
 };
 
-/* a launch that is timed, when it is, by the dispatch's own stamps */
+/* a launch that is timed, when it is, by the dispatch's own stamps.  `stop`: an event of the caller's on the dispatch's completion;
+ * `event_mode` 2 ("fir_launch" 2, launch_route): an un-timed dispatch carries a start and a stop event of the overlap state's ring;
+ * `rode`: where the launch carried its kernel timer's events, the timer's stop event (it says "this kernel has ended" as well) */
 template <typename Args>
-int launch_timed(ProfileScope &scope, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args &a, hipEvent_t stop = nullptr)
+int launch_timed(ProfileScope &scope, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args &a, hipEvent_t stop = nullptr,
+                 int event_mode = 0, hipEvent_t *rode = nullptr)
 {
     void *kargs[] = {(void *)&a};
     hipEvent_t s = nullptr, e = nullptr;
     if (stop) { scope.begin(); HIP_TRY(hipExtLaunchKernel(fn, grid, block, kargs, lds, stream, nullptr, stop, 0)); return 0; }
-    if (scope.ride(s, e)) { HIP_TRY(hipExtLaunchKernel(fn, grid, block, kargs, lds, stream, s, e, 0)); return 0; }
-    if (scope.kind == AVDSP_KERNEL_FIR && scope.prog->fir_mode_now == 2) {
-        avdsp_hip_prog *pg = scope.prog;
-        const unsigned k = (pg->launch_ev_next++ & 7u) * 2;
-        for (unsigned j = k; j < k + 2; j++) if (!pg->launch_ev[j]) HIP_TRY(hipEventCreate(&pg->launch_ev[j]));
-        HIP_TRY(hipExtLaunchKernel(fn, grid, block, kargs, lds, stream, pg->launch_ev[k], pg->launch_ev[k + 1], 0));
+    if (scope.ride(s, e)) { HIP_TRY(hipExtLaunchKernel(fn, grid, block, kargs, lds, stream, s, e, 0)); if (rode) *rode = e; return 0; }
+    if (event_mode == 2) {
+        auto &ov = scope.prog->ov;
+        const unsigned k = (ov.launch_ev_next++ & 7u) * 2;
+        for (unsigned j = k; j < k + 2; j++) if (!ov.launch_ev[j]) HIP_TRY(hipEventCreate(&ov.launch_ev[j]));
+        HIP_TRY(hipExtLaunchKernel(fn, grid, block, kargs, lds, stream, ov.launch_ev[k], ov.launch_ev[k + 1], 0));
         return 0;
     }
     HIP_TRY(hipLaunchKernel(fn, grid, block, kargs, lds, stream));
@@ -5003,12 +5028,12 @@ int fir_opt_in(int format, int gpc)
 }
 
 /* what the launches of fir_tile, fir_stream and fir_flow share: the arguments ... */
-FirTileArgs fir_tile_args(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, bool wait_ready)
+FirTileArgs fir_tile_args(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, bool wait_ready, bool ready_acquire = false)
 {
     FirTileArgs a{};
     a.buf = prog->d_buf; a.chains = pl.d_chains; a.group = ids; a.ngroup = n;
     a.ring = plan_ring(pl); a.io = io; a.taps64 = pl.d_taps64; a.pitch64 = pl.pitch64;
-    if (wait_ready) { a.ready = pl.d_ready; a.seq = pl.seq; a.timeouts = prog->d_ready_timeouts; a.ready_acquire = prog->ready_mode_now != 2 || prog->overlap >= 2; }
+    if (wait_ready) { a.ready = pl.d_ready; a.seq = pl.seq; a.timeouts = prog->d_ready_timeouts; a.ready_acquire = ready_acquire; }
     return a;
 }
 /* ... the operand ring of the latter two (8 bytes per ring entry, every operand twice: Ring), made from the float ring at first use;
@@ -5085,12 +5110,19 @@ int launch_fir_shared(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t st
 
 /* fir_impl: 0 = fir_plain (the reference's loop), 1 = fir_tile (default), 2 = fir_mfma (round 1's workgroup-per-channel kernel),
  * 3 = fir_stream, 4 = fir_flow; which variant of it: fir_choice (avdsp_plan_layout.h).
- * hand: the launch of the plan's handed FIR chains ("fir_tail": fir_hand_choice, the HAND forms, the hand-over block in the arguments) */
+ * hand: the launch of the plan's handed FIR chains ("fir_tail": fir_hand_choice, the HAND forms, the hand-over block in the arguments);
+ * wait_ready, ready_acquire, stop, event_mode: the overlap arrangement's (launch_route); `rode`: as launch_timed's */
+struct FirLaunch {
+    const int *ids; int n; BlockIO io; int fir_impl; hipStream_t stream;
+    bool wait_ready = false, ready_acquire = false; hipEvent_t stop = nullptr; bool hand = false; int event_mode = 0;
+};
 template <int FMT>
-int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io, int fir_impl, hipStream_t stream, bool wait_ready = false, hipEvent_t stop = nullptr, bool hand = false)
+int launch_fir(avdsp_hip_prog *prog, Plan &pl, const FirLaunch &L, hipEvent_t *rode = nullptr)
 {
-    if constexpr (FMT == 2) { (void)prog; (void)pl; (void)ids; (void)n; (void)io; (void)fir_impl; (void)stream; (void)wait_ready; (void)stop; (void)hand; return 0; }
+    if constexpr (FMT == 2) { (void)prog; (void)pl; (void)L; (void)rode; return 0; }
     else {
+        const int *const ids = L.ids; const int n = L.n, fir_impl = L.fir_impl; const BlockIO &io = L.io;
+        const hipStream_t stream = L.stream; const hipEvent_t stop = L.stop; const bool hand = L.hand;
         if (hand && (!pl.d_hand || !pl.d_hand_row)) return set_err("a launch of handed FIR chains without its hand-over block");
         if (ensure_private_taps(prog, pl, stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
@@ -5102,7 +5134,7 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
         const int cus = prog->num_cus > 0 ? prog->num_cus : 256;
         if (c.family == kFirTile || c.family == kFirFlow) {
             if (c.family == kFirFlow && ensure_operand_ring(prog, pl, stream)) return -1;
-            FirTileArgs a = fir_tile_args(prog, pl, ids, n, io, wait_ready);
+            FirTileArgs a = fir_tile_args(prog, pl, ids, n, io, L.wait_ready, L.ready_acquire);
             int wpc = v->wpc;                             /* (fir_flow keeps the 1024-frame arrangement) */
             if (c.family == kFirTile) {
                 /* the tiles a chain has in this launch (a power of two, so that a chain's waves sit in one workgroup): a short block is fewer
@@ -5126,9 +5158,9 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const int *ids, int n, BlockIO io
                 FirTileArgsHand h{};
                 static_cast<FirTileArgs &>(h) = a;
                 h.hand = pl.d_hand; h.hand_row = pl.d_hand_row;
-                return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, h, stop);
+                return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, h, stop, L.event_mode, rode);
             }
-            return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, a, stop);
+            return launch_timed(scope, v->fn, dim3(a.per_xcd * 8), dim3(kBlock), (size_t)v->lds, stream, a, stop, L.event_mode, rode);
         }
         if (c.family == kFirStream) {
             if (ensure_operand_ring(prog, pl, stream)) return -1;
@@ -5242,7 +5274,7 @@ static int probe_pair(avdsp_hip_prog *prog, hipStream_t waiter, hipStream_t sett
     return 0;
 }
 
-static int probe_once(avdsp_hip_prog *prog, hipStream_t fir_stream, bool *ok) { return probe_pair(prog, fir_stream, prog->s_bq, ok); }
+static int probe_once(avdsp_hip_prog *prog, hipStream_t fir_stream, bool *ok) { return probe_pair(prog, fir_stream, prog->ov.s_bq, ok); }
 
 /* Per stream the FIRs are launched on: do its kernels and the cascades' stream's run side by side?  That depends on the hardware
  * queues the runtime gave the two streams -- it has a handful per device and deals them out in turn, so a caller's stream may well
@@ -5255,38 +5287,38 @@ static int probe_once(avdsp_hip_prog *prog, hipStream_t fir_stream, bool *ok) { 
  * left after that (dispatches serialised from outside: a counter-collecting profiler) runs on events, correct anywhere. */
 static int probe_side_by_side(avdsp_hip_prog *prog, hipStream_t fir_stream)
 {
-    for (auto &pr : prog->probed) if (pr.first == fir_stream) { prog->side_by_side = pr.second; return 0; }
-    prog->side_by_side = 0;
-    if (prog->probed.size() >= 16) prog->probed.clear();
+    for (auto &pr : prog->ov.probed) if (pr.first == fir_stream) { prog->ov.side_by_side = pr.second; return 0; }
+    prog->ov.side_by_side = 0;
+    if (prog->ov.probed.size() >= 16) prog->ov.probed.clear();
     bool ok = false;
     for (int attempt = 0; attempt < 6; attempt++) {
         if (probe_once(prog, fir_stream, &ok)) return -1;
-        if (ok || !prog->d_ready_timeouts || prog->remade >= 8) break;
+        if (ok || !prog->d_ready_timeouts || prog->ov.remade >= 8) break;
         /* the pair shares a queue (or nothing runs side by side here at all): another stream for the cascades.  The old one is kept
          * until the program goes (destroying it would hand its queue slot straight back), and every pair tried so far is void. */
         hipStream_t ns = nullptr;
         if (make_side_stream(prog, &ns, true)) return -1;
-        HIP_TRY(hipStreamSynchronize(prog->s_bq));
-        prog->retired.push_back(prog->s_bq);
-        prog->s_bq = ns;
-        prog->probed.clear(); prog->ahead_probed.clear();
-        prog->remade++;
+        HIP_TRY(hipStreamSynchronize(prog->ov.s_bq));
+        prog->ov.retired.push_back(prog->ov.s_bq);
+        prog->ov.s_bq = ns;
+        prog->ov.probed.clear(); prog->ov.ahead_probed.clear();
+        prog->ov.remade++;
     }
-    prog->side_by_side = ok;
-    prog->probed.push_back({fir_stream, ok ? 1 : 0});
+    prog->ov.side_by_side = ok;
+    prog->ov.probed.push_back({fir_stream, ok ? 1 : 0});
     return 0;
 }
 
 static int overlap_ready(avdsp_hip_prog *prog)
 {
-    if (prog->s_bq) return 0;
-    if (make_side_stream(prog, &prog->s_bq, true)) return -1;
-    for (auto &fs : prog->s_fir) if (make_side_stream(prog, &fs, false)) return -1;
+    if (prog->ov.s_bq) return 0;
+    if (make_side_stream(prog, &prog->ov.s_bq, true)) return -1;
+    for (auto &fs : prog->ov.s_fir) if (make_side_stream(prog, &fs, false)) return -1;
     for (int i = 0; i < avdsp_hip_prog::kAhead; i++) {
         /* they order kernels of this device among themselves: no system-scope fence (tools/stream_handover_bench.hip: 8.1 instead of 10.6 us) */
-        HIP_TRY(hipEventCreateWithFlags(&prog->ev_bq[i], hipEventDisableTiming | hipEventDisableSystemFence));
-        HIP_TRY(hipEventCreateWithFlags(&prog->ev_fir[i], hipEventDisableTiming | hipEventDisableSystemFence));
-        if (!prog->ev_out[i]) HIP_TRY(hipEventCreateWithFlags(&prog->ev_out[i], hipEventDisableTiming | hipEventDisableSystemFence));
+        HIP_TRY(hipEventCreateWithFlags(&prog->ov.ev_bq[i], hipEventDisableTiming | hipEventDisableSystemFence));
+        HIP_TRY(hipEventCreateWithFlags(&prog->ov.ev_fir[i], hipEventDisableTiming | hipEventDisableSystemFence));
+        if (!prog->ov.ev_out[i]) HIP_TRY(hipEventCreateWithFlags(&prog->ov.ev_out[i], hipEventDisableTiming | hipEventDisableSystemFence));
     }
     return 0;
 }
@@ -5301,30 +5333,30 @@ static int overlap_ready(avdsp_hip_prog *prog)
  * staged path is still correct, but only taken when forced ("fir_ahead" 1). */
 static int ahead_streams_apart(avdsp_hip_prog *prog, hipStream_t stream)
 {
-    for (auto &pr : prog->ahead_probed) if (pr.first == stream) { prog->ahead_apart = pr.second; return 0; }
-    if (prog->ahead_probed.size() >= 16) prog->ahead_probed.clear();
+    for (auto &pr : prog->ov.ahead_probed) if (pr.first == stream) { prog->ov.ahead_apart = pr.second; return 0; }
+    if (prog->ov.ahead_probed.size() >= 16) prog->ov.ahead_probed.clear();
     bool all = false;
     for (int attempt = 0; attempt < 12 && !all; attempt++) {
-        hipStream_t *const pairs[6][2] = {{&prog->s_fir[0], &stream}, {&prog->s_fir[1], &stream}, {&prog->s_fir[1], &prog->s_fir[0]},
-                                         {&prog->s_fir[0], &prog->s_bq}, {&prog->s_fir[1], &prog->s_bq}, {&prog->s_bq, &stream}};
+        hipStream_t *const pairs[6][2] = {{&prog->ov.s_fir[0], &stream}, {&prog->ov.s_fir[1], &stream}, {&prog->ov.s_fir[1], &prog->ov.s_fir[0]},
+                                         {&prog->ov.s_fir[0], &prog->ov.s_bq}, {&prog->ov.s_fir[1], &prog->ov.s_bq}, {&prog->ov.s_bq, &stream}};
         all = true;
         for (auto &p : pairs) {
             bool ok = false;
             if (probe_pair(prog, *p[0], *p[1], &ok)) return -1;
             if (ok) continue;
             all = false;
-            if (!prog->d_ready_timeouts || prog->ahead_remade >= 10) { attempt = 12; break; }      /* (nothing runs side by side here: a counter-collecting profiler) */
+            if (!prog->d_ready_timeouts || prog->ov.ahead_remade >= 10) { attempt = 12; break; }      /* (nothing runs side by side here: a counter-collecting profiler) */
             hipStream_t ns = nullptr;
-            if (make_side_stream(prog, &ns, p[0] == &prog->s_bq)) return -1;
-            prog->retired.push_back(*p[0]);
+            if (make_side_stream(prog, &ns, p[0] == &prog->ov.s_bq)) return -1;
+            prog->ov.retired.push_back(*p[0]);
             *p[0] = ns;
-            prog->probed.clear(); prog->ahead_probed.clear();
-            prog->ahead_remade++;
+            prog->ov.probed.clear(); prog->ov.ahead_probed.clear();
+            prog->ov.ahead_remade++;
             break;
         }
     }
-    prog->ahead_apart = all ? 1 : 0;
-    prog->ahead_probed.push_back({stream, prog->ahead_apart});
+    prog->ov.ahead_apart = all ? 1 : 0;
+    prog->ov.ahead_probed.push_back({stream, prog->ov.ahead_apart});
     return 0;
 }
 
@@ -5470,183 +5502,185 @@ __global__ void ahead_copy_words(AheadCopyArgs a)
 /* a staging block per slot, kFirChunk frames of `words` words in all; growing them waits for the device (a wider window than any so far: rare) */
 static int ahead_stage_ready(avdsp_hip_prog *prog, long long words)
 {
-    if (words <= prog->stage_words) return 0;
+    if (words <= prog->ov.stage_words) return 0;
     HIP_TRY(hipDeviceSynchronize());
-    prog->stage_words = 0;
-    for (auto &st : prog->stage) if (st.alloc((size_t)words) != hipSuccess) return set_err("hipMalloc(staging block of %lld words)", words);
-    prog->stage_words = words;
+    prog->ov.stage_words = 0;
+    for (auto &st : prog->ov.stage) if (st.alloc((size_t)words) != hipSuccess) return set_err("hipMalloc(staging block of %lld words)", words);
+    prog->ov.stage_words = words;
     return 0;
 }
 
-template <int FMT>
-int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
+/* ---- a block's launches.  What is enqueued is decided by launch_gate / launch_route (avdsp_plan_layout.h) from the
+ * facts below; the enqueuers behind them decide nothing. ---- */
+static LaunchFacts launch_facts(const avdsp_hip_prog *prog, const Plan &pl, const BlockIO &io, int fir_impl, int biquad_impl)
 {
-    const bool under = prog->overlap && pl.overlap_ok && biquad_impl && fir_impl;
-    pl.seq++;                                             /* this launch's number in the plan's ready words */
-    prog->fir_ahead_now = 0;
-    if (under) {
-        prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
-        if (overlap_ready(prog)) return -1;
-        const bool own_fir = prog->overlap >= 2 || prog->cu_split > 0;      /* the FIRs on a stream of the library's own */
-        /* "fir_ahead" (DESIGN.md 4.5c): "overlap" 2's arrangement of the FIRs under "overlap" 1's contract -- compute early, write the
-         * caller's block late.  The FIR of this block goes on s_fir[] in turn like "overlap" 2's and stores into a staging block of the
-         * library's own; the caller's stream waits for its event and copies the columns it stored into the caller's block.  So the
-         * caller's block is only ever written in the caller's stream order, one output block may serve every call, and work the caller
-         * queued between two calls has read it before the later call's words arrive.  Every ordering is an event between streams; no
-         * wave waits for anything.  Not legal, and the call takes the path below as ever: chain instances, an in-place call (the
-         * next call's cascade reads its input at once, from the stream of the cascades), a window over the staging cap, "overlap" 2
-         * (its own contract), "cu_split"; plans with handed FIR chains or a mux stage have no overlap at all (overlap_ok).
-         * Nor a plan with impulse groups (the shared-impulse path's plans: their per-chain taps may still have to be made, by a kernel
-         * on the launch's stream -- ensure_private_taps -- which nothing orders in front of the OTHER stream's FIR), nor a fir_impl
-         * other than fir_tile's (fir_stream and fir_flow make their operand ring the same way: ensure_operand_ring): whatever a
-         * staged launch reads exists since the plan was built. */
-        bool staged = false;
-        if (prog->fir_ahead != 0 && !own_fir && pl.n_ahead_cols > 0 && pl.instances <= 1 && prog->inst_n <= 1 && prog->chain_inst <= 1 &&
-            fir_impl == 1 && pl.n_sh_groups == 0 && pl.d_taps64) {
-            const long long sw = ahead_stage_words(io.out_stride);
-            const bool legal = sw > 0 && !prog->call_in_place;
-            if (legal && (prog->fir_ahead == 1 || fir_ahead_by_plan(pl.n_fir, pl.max_taps, io.nframes))) {
-                if (ahead_streams_apart(prog, stream)) return -1;                      /* (remembered per stream) */
-                staged = prog->fir_ahead == 1 || prog->ahead_apart;                    /* (by the plan: only where it can gain) */
-            }
-            if (staged && ahead_stage_ready(prog, sw)) return -1;
-        }
-        prog->fir_ahead_now = staged ? 1 : 0;
-        if (staged) prog->side_by_side = prog->ahead_apart;
-        else if (probe_side_by_side(prog, prog->overlap >= 2 ? prog->s_fir[prog->blk & 1] : prog->cu_split > 0 ? prog->s_fir[0] : stream)) return -1;     /* (remembered per stream) */
-        /* fir_tile finds its cascades' blocks through the ready words; the other FIR kernels wait for the cascades' event */
-        const bool can_words = (fir_impl == 1 || fir_impl == 4) && pl.d_ready && prog->d_ready_timeouts && prog->side_by_side;
-        /* Mode 2 takes the wait packet off the FIRs' stream (a FIR follows the previous one like any kernel of a queue): 4096 chains
-         * 0.5025 -> 0.4980 ms per step.  Where the cascades are the bound that packet's ~9 us are bubbles they live on: 2048 chains
-         * 0.2594 -> 0.2686, 512 chains 0.0864 -> 0.0933 (one box) -- so by default only where a launch is more than one round of waves */
-        /* (not with "overlap" 2: two FIRs in flight, the later one's waves would sit on their SIMDs looking at words of a cascade that
-         * both of them starve -- 0.496 -> 0.547 ms) */
-        /* (nor with a staged launch, for the same reason: the event, whatever "ready_words" says) */
-        const int rw = staged ? 0 : prog->ready_words >= 0 ? prog->ready_words : (prog->overlap == 1 && (long long)pl.n_fir * pl.max_taps >= 12000000ll ? 2 : 0);
-        const bool behind = rw == 2 && can_words;                            /* a kernel behind the cascade publishes */
-        const bool words = (rw == 1 && fir_impl == 1 && can_words) || behind;      /* the FIR looks at the words: no event wait on its stream */
-        prog->ready_mode_now = behind ? 2 : words ? 1 : 0;
-        const bool wt = words && !behind;                                  /* the cascade's own waves publish: write-through ring stores */
-        const int slot = (int)(prog->blk % avdsp_hip_prog::kAhead);
-        if (prog->ev_fir_set[slot]) {                           /* FIR k-3: the ring positions this block's cascade appends are free once it has read its window */
-            /* The HOST waits for it ("ring_wait" 1, the default), not the cascades' stream.  A wait packet costs a queue ~9 us even when
-             * its signal is long down, and the cascades' stream of a small shard has none to spare: a cascade beside an MFMA stream
-             * lasts about a step, so with the packet in front of every cascade that stream's period -- not the FIRs' -- was the step
-             * (512 chains: cascade 88.7 + packet ~9 = the 98 us measured; tools/step_gaps.py), and a run settled in that state or in
-             * the one where the cascades are a block ahead (86 us) by chance.  The host is the natural place: it only has to stay
-             * within three blocks of the device, and in steady state that IS this wait.  Bounded (1 ms), then the packet after all:
-             * a caller whose stream waits on something it will enqueue later must not hang here. */
-            bool done = false;
-            if (prog->ring_wait_host) {
-                const auto t0 = std::chrono::steady_clock::now();
-                for (;;) {
-                    const hipError_t q = hipEventQuery(prog->ev_fir_now[slot]);
-                    if (q == hipSuccess) { done = true; break; }
-                    (void)hipGetLastError();
-                    if (q != hipErrorNotReady) break;
-                    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) break;
-                    std::this_thread::yield();
-                }
-            }
-            if (!done) HIP_TRY(hipStreamWaitEvent(prog->s_bq, prog->ev_fir_now[slot], 0));
-        }
-        if (prog->input_ready) HIP_TRY(hipStreamWaitEvent(prog->s_bq, prog->input_ready, 0));           /* (queued host blocks: the copy of this block) */
-        if (launch_cascades<FMT>(prog, pl, io, biquad_impl, prog->s_bq, !words ? prog->ev_bq[slot] : nullptr, wt)) return -1;
-        if (behind && prog->ready_test > 0) prog->ready_test--;       /* (tests: this launch's words are never set) */
-        else if (behind) {
-            hipLaunchKernelGGL(ready_set, dim3((unsigned)((pl.n_fir + kBlock - 1) / kBlock)), dim3(kBlock), 0, prog->s_bq, pl.d_ready, pl.d_fir_ids, pl.n_fir, pl.seq);
-            HIP_TRY(hipGetLastError());
-        }
-        if (staged) {
-            hipStream_t fs = prog->s_fir[prog->blk & 1];
-            HIP_TRY(hipStreamWaitEvent(fs, prog->ev_bq[slot], 0));
-            /* the slot's staging block is free once the copy of the call three back has read it.  Its event is asked first: a wait
-             * packet costs the queue ~9 us even when its signal is long down.  Where the packet is needed it falls under the other
-             * stream's FIR as long as the host runs a call ahead. */
-            if (prog->ev_out_set[slot] && hipEventQuery(prog->ev_out[slot]) != hipSuccess) {
-                (void)hipGetLastError();
-                HIP_TRY(hipStreamWaitEvent(fs, prog->ev_out[slot], 0));
-            }
-            BlockIO sio = io;
-            sio.out = prog->stage[slot];
-            if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, sio, fir_impl, fs, false)) return -1;
-            HIP_TRY(hipEventRecord(prog->ev_fir[slot], fs));
-            prog->ev_fir_now[slot] = prog->ev_fir[slot];
-            HIP_TRY(hipStreamWaitEvent(stream, prog->ev_fir[slot], 0));
-            AheadCopyArgs ca{prog->stage[slot], io.out, pl.d_ahead_cols, pl.n_ahead_cols, pl.ahead_lo, io.out_stride, io.out_base, io.nframes};
-            const bool run = pl.ahead_run && ((pl.ahead_lo - io.out_base) & 3) == 0 && (pl.n_ahead_cols & 3) == 0 && (io.out_stride & 3) == 0 &&
-                             (reinterpret_cast<size_t>(io.out) & 15) == 0;
-            const long long total = (long long)io.nframes * (run ? pl.n_ahead_cols >> 2 : pl.n_ahead_cols);
-            const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096));
-            if (run) hipLaunchKernelGGL(ahead_copy_run, grid, dim3(kBlock), 0, stream, ca);
-            else     hipLaunchKernelGGL(ahead_copy_words, grid, dim3(kBlock), 0, stream, ca);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(prog->ev_out[slot], stream));
-            prog->ev_out_set[slot] = true;
-        } else if (own_fir) {
-            /* ("cu_split": ONE stream of the library's own, on the CUs the cascades' stream does not have)
-             * the FIRs of consecutive blocks on two streams of the library's own, in turn: FIR k+1 needs nothing of FIR k, and on one
-             * stream it would start a queue hand-over (~10 us) after FIR k's last wave; here its first workgroups fill the chip as FIR
-             * k's last ones leave.  The caller's stream only waits for each FIR's end.  (The mode's contract then covers the output
-             * too: the block a call writes must not be one an earlier call's FIR may still be writing.) */
-            hipStream_t fs = prog->s_fir[prog->overlap >= 2 ? (prog->blk & 1) : 0];
-            if (!words) HIP_TRY(hipStreamWaitEvent(fs, prog->ev_bq[slot], 0));
-            if (launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, fs, words)) return -1;
-            HIP_TRY(hipEventRecord(prog->ev_fir[slot], fs));
-            prog->ev_fir_now[slot] = prog->ev_fir[slot];
-            HIP_TRY(hipStreamWaitEvent(stream, prog->ev_fir[slot], 0));
-        } else {
-            /* The FIR follows the previous block's FIR on the caller's stream with nothing in between: an event wait here -- a barrier
-             * packet on another queue's signal -- holds the next dispatch back by ~9 us even when the signal is long down
-             * (tools/step_gaps.py: 10.7 us between two FIRs of the 4096-chain program, 1.5-2 us between two kernels of one queue). */
-            if (!words) HIP_TRY(hipStreamWaitEvent(stream, prog->ev_bq[slot], 0));
-            /* (round 5, tools/shard_blocks_ab.sh: mode 2's empty microseconds only pay where the cascades are the clock, and that takes
-             * a block long enough for them to be -- shards of 512 / 1024 chains, mode 2 against mode 1: 86.9 / 90.8 and 146.5 / 148.6 us at
-             * 1024 frames, but 150.4 / 138.0 at 768, 91.2 / 78.1 and 57.6 / 51.6 at 512, 58.1 / 47.9 and 56.6 / 45.4 at 256) */
-            const int mode = fir_impl != 1 && fir_impl != 4 ? 0 : prog->fir_launch_mode >= 0 ? prog->fir_launch_mode
-                           : ((long long)pl.n_fir * pl.max_taps <= 6000000ll && io.nframes > 768) ? 2 : 1;
-            /* (a launch whose kernel timer is sampled carries the timer's events instead; its event is then recorded behind it) */
-            const bool rides = mode == 1 && !((prog->profile >> AVDSP_KERNEL_FIR & 1u) && prog->profile_seen[AVDSP_KERNEL_FIR & 7] % (unsigned)prog->profile_stride == 0);
-            prog->fir_mode_now = mode;
-            prog->last_ride_stop = nullptr;
-            const int rc_fir = launch_fir<FMT>(prog, pl, pl.d_fir_ids, pl.n_fir, io, fir_impl, stream, words, rides ? prog->ev_fir[slot] : nullptr);
-            prog->fir_mode_now = 0;
-            if (rc_fir) return -1;
-            /* (round 5: a launch that carries its kernel timer's stop event needs no second event behind it -- that one says "this FIR
-             * has ended" just as well, and a recorded event is a marker packet the next dispatch queues behind: with every launch of a
-             * 0.5-ms FIR timed the step was 0.5110 ms against 0.5045 with every fourth) */
-            prog->ev_fir_now[slot] = prog->ev_fir[slot];
-            static const bool timer_doubles = !getenv("AVDSP_TIMER_DOUBLES") || atoi(getenv("AVDSP_TIMER_DOUBLES")) != 0;
-            if (!rides && mode == 1 && prog->last_ride_stop && timer_doubles) prog->ev_fir_now[slot] = prog->last_ride_stop;
-            else if (!rides) HIP_TRY(hipEventRecord(prog->ev_fir[slot], stream));
-        }
-        prog->ev_fir_set[slot] = true;
-        prog->blk++;
-    } else if (pl.has_mem) {
-        /* ("chain_mem": the trunks' cascades and the ordinary chains' on the caller's block, joined; the stage; the branches' cascades on the
-         * branch block, joined.  Such a plan has no FIR) */
-        if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false, 0)) return -1;
-        if (launch_mem<FMT>(prog, pl, io, stream)) return -1;
-        BlockIO bio = io;
-        bio.in = pl.d_mem_scratch; bio.in_stride = pl.n_mem_cols; bio.in_base = 0;
-        if (pl.n_mem_cols && launch_cascades<FMT>(prog, pl, bio, biquad_impl, stream, nullptr, false, 1)) return -1;
-    } else {
-        if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false)) return -1;
-        /* (a plan with handed FIR chains: the plain ones have a list of their own; else it is every FIR chain, as ever) */
-        const int n_plain = pl.n_fir - pl.n_fir_hand;
-        const int *plain_ids = pl.n_fir_hand ? pl.d_fir_plain.get() : pl.d_fir_ids.get();
-        if (n_plain && shared_path(prog, pl, fir_impl)) {
-            /* chains of one bank on fir_shared, the others on fir_tile as ever: two launches on the stream */
-            if (pl.n_fir_rest && launch_fir<FMT>(prog, pl, pl.d_fir_rest, pl.n_fir_rest, io, fir_impl, stream)) return -1;
-            if (launch_fir_shared<FMT>(prog, pl, io, stream)) return -1;
-            prog->sh_chains_now = pl.n_sh_chains; prog->sh_groups_now = pl.n_sh_groups;
-        } else if (pl.n_fir) {
-            if (n_plain && launch_fir<FMT>(prog, pl, plain_ids, n_plain, io, fir_impl, stream)) return -1;
-            prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;
-        }
-        /* the handed FIR chains ("fir_tail"): their accumulators into the hand-over block, chain_tail below takes them up */
-        if (pl.n_fir_hand && launch_fir<FMT>(prog, pl, pl.d_fir_hand, pl.n_fir_hand, io, fir_impl, stream, false, nullptr, true)) return -1;
+    LaunchFacts f{};
+    f.overlap = prog->overlap; f.cu_split = prog->cu_split; f.fir_ahead = prog->fir_ahead; f.ready_words = prog->ready_words; f.fir_launch = prog->fir_launch_mode;
+    f.fir_impl = fir_impl; f.biquad_impl = biquad_impl; f.nframes = io.nframes; f.out_stride = io.out_stride; f.in_place = prog->call_in_place;
+    f.overlap_ok = pl.overlap_ok; f.n_fir = pl.n_fir; f.max_taps = pl.max_taps; f.n_ahead_cols = pl.n_ahead_cols; f.instances = pl.instances; f.n_sh_groups = pl.n_sh_groups;
+    f.has_taps64 = pl.d_taps64 != nullptr; f.has_ready = pl.d_ready != nullptr;
+    f.inst_n = prog->inst_n; f.chain_inst = prog->chain_inst; f.has_timeouts = prog->d_ready_timeouts != nullptr;
+    f.timer_samples = (prog->profile >> AVDSP_KERNEL_FIR & 1u) && prog->profile_seen[AVDSP_KERNEL_FIR & 7] % (unsigned)prog->profile_stride == 0;
+    return f;
+}
+
+/* FIR k-3, the slot's last: the ring positions this block's cascade appends are free once it has read its window.
+ * The HOST waits for it ("ring_wait" 1, the default), not the cascades' stream.  A wait packet costs a queue ~9 us even when its signal
+ * is long down, and the cascades' stream of a small shard has none to spare: a cascade beside an MFMA stream lasts about a step, so with
+ * the packet in front of every cascade that stream's period -- not the FIRs' -- was the step (512 chains: cascade 88.7 + packet ~9 = the
+ * 98 us measured; tools/step_gaps.py), and a run settled in that state or in the one where the cascades are a block ahead (86 us) by
+ * chance.  The host is the natural place: it only has to stay within three blocks of the device, and in steady state that IS this wait.
+ * Bounded (1 ms), then the packet after all: a caller whose stream waits on something it will enqueue later must not hang here. */
+static int wait_fir_three_back(avdsp_hip_prog *prog, int slot)
+{
+    auto &ov = prog->ov;
+    if (!ov.ev_fir_set[slot]) return 0;
+    for (const auto t0 = std::chrono::steady_clock::now(); prog->ring_wait_host; std::this_thread::yield()) {
+        const hipError_t q = hipEventQuery(ov.ev_fir_now[slot]);
+        if (q == hipSuccess) return 0;
+        (void)hipGetLastError();
+        if (q != hipErrorNotReady || std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) break;
     }
+    HIP_TRY(hipStreamWaitEvent(ov.s_bq, ov.ev_fir_now[slot], 0));
+    return 0;
+}
+
+/* what every overlapped path starts with, on the cascades' stream: the wait for FIR k-3, the cascades of this block, and with
+ * "ready_words" 2 the kernel behind them that publishes */
+template <int FMT>
+int enqueue_cascades_ahead(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, const LaunchRoute &r, int slot)
+{
+    auto &ov = prog->ov;
+    if (wait_fir_three_back(prog, slot)) return -1;
+    if (prog->input_ready) HIP_TRY(hipStreamWaitEvent(ov.s_bq, prog->input_ready, 0));           /* (queued host blocks: the copy of this block) */
+    if (launch_cascades<FMT>(prog, pl, io, biquad_impl, ov.s_bq, r.cascade_event ? ov.ev_bq[slot] : nullptr, r.write_through)) return -1;
+    if (r.ready_mode != 2) return 0;
+    if (prog->ready_test > 0) { prog->ready_test--; return 0; }       /* (tests: this launch's words are never set) */
+    hipLaunchKernelGGL(ready_set, dim3((unsigned)((pl.n_fir + kBlock - 1) / kBlock)), dim3(kBlock), 0, ov.s_bq, pl.d_ready, pl.d_fir_ids, pl.n_fir, pl.seq);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* the copy behind a staged FIR launch: ahead_copy_run where the columns are one run and everything is 16-byte aligned, else ahead_copy_words */
+static int launch_ahead_copy(Plan &pl, const unsigned *stage, BlockIO io, hipStream_t stream)
+{
+    AheadCopyArgs ca{stage, io.out, pl.d_ahead_cols, pl.n_ahead_cols, pl.ahead_lo, io.out_stride, io.out_base, io.nframes};
+    const bool run = pl.ahead_run && ((pl.ahead_lo - io.out_base) & 3) == 0 && (pl.n_ahead_cols & 3) == 0 && (io.out_stride & 3) == 0 &&
+                     (reinterpret_cast<size_t>(io.out) & 15) == 0;
+    const long long total = (long long)io.nframes * (run ? pl.n_ahead_cols >> 2 : pl.n_ahead_cols);
+    const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, 4096));
+    if (run) hipLaunchKernelGGL(ahead_copy_run, grid, dim3(kBlock), 0, stream, ca);
+    else     hipLaunchKernelGGL(ahead_copy_words, grid, dim3(kBlock), 0, stream, ca);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* "fir_ahead" (DESIGN.md 4.5c): "overlap" 2's arrangement of the FIRs under "overlap" 1's contract -- compute early, write the caller's
+ * block late.  The FIR of this block goes on s_fir[] in turn like "overlap" 2's and stores into a staging block of the library's own; the
+ * caller's stream waits for its event and copies the columns it stored into the caller's block.  So the caller's block is only ever
+ * written in the caller's stream order, one output block may serve every call, and work the caller queued between two calls has read it
+ * before the later call's words arrive.  Every ordering is an event between streams; no wave waits for anything. */
+template <int FMT>
+int enqueue_staged(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hipStream_t stream, int slot)
+{
+    auto &ov = prog->ov;
+    hipStream_t fs = ov.s_fir[ov.blk & 1];
+    HIP_TRY(hipStreamWaitEvent(fs, ov.ev_bq[slot], 0));
+    /* the slot's staging block is free once the copy of the call three back has read it.  Its event is asked first: a wait packet costs
+     * the queue ~9 us even when its signal is long down.  Where the packet is needed it falls under the other stream's FIR as long as
+     * the host runs a call ahead. */
+    if (ov.ev_out_set[slot] && hipEventQuery(ov.ev_out[slot]) != hipSuccess) {
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamWaitEvent(fs, ov.ev_out[slot], 0));
+    }
+    BlockIO sio = io;
+    sio.out = ov.stage[slot];
+    if (launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_ids, .n = pl.n_fir, .io = sio, .fir_impl = fir_impl, .stream = fs})) return -1;
+    HIP_TRY(hipEventRecord(ov.ev_fir[slot], fs));
+    ov.ev_fir_now[slot] = ov.ev_fir[slot];
+    HIP_TRY(hipStreamWaitEvent(stream, ov.ev_fir[slot], 0));
+    if (launch_ahead_copy(pl, ov.stage[slot], io, stream)) return -1;
+    HIP_TRY(hipEventRecord(ov.ev_out[slot], stream));
+    ov.ev_out_set[slot] = true;
+    return 0;
+}
+
+/* The FIRs on `fs`, a stream of the library's own.  "cu_split": ONE stream, on the CUs the cascades' stream does not have.  "overlap" 2:
+ * the FIRs of consecutive blocks on two streams in turn: FIR k+1 needs nothing of FIR k, and on one stream it would start a queue
+ * hand-over (~10 us) after FIR k's last wave; here its first workgroups fill the chip as FIR k's last ones leave.  The caller's stream
+ * only waits for each FIR's end.  (The mode's contract then covers the output too: the block a call writes must not be one an earlier
+ * call's FIR may still be writing.) */
+template <int FMT>
+int enqueue_own_fir(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hipStream_t stream, hipStream_t fs, const LaunchRoute &r, int slot)
+{
+    auto &ov = prog->ov;
+    if (r.fir_waits_event) HIP_TRY(hipStreamWaitEvent(fs, ov.ev_bq[slot], 0));
+    if (launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_ids, .n = pl.n_fir, .io = io, .fir_impl = fir_impl, .stream = fs,
+                                   .wait_ready = !r.fir_waits_event, .ready_acquire = r.ready_acquire})) return -1;
+    HIP_TRY(hipEventRecord(ov.ev_fir[slot], fs));
+    ov.ev_fir_now[slot] = ov.ev_fir[slot];
+    HIP_TRY(hipStreamWaitEvent(stream, ov.ev_fir[slot], 0));
+    return 0;
+}
+
+/* The FIR follows the previous block's FIR on the caller's stream with nothing in between: an event wait here -- a barrier packet on
+ * another queue's signal -- holds the next dispatch back by ~9 us even when the signal is long down (tools/step_gaps.py: 10.7 us between
+ * two FIRs of the 4096-chain program, 1.5-2 us between two kernels of one queue). */
+template <int FMT>
+int enqueue_direct(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hipStream_t stream, const LaunchRoute &r, int slot)
+{
+    auto &ov = prog->ov;
+    if (r.fir_waits_event) HIP_TRY(hipStreamWaitEvent(stream, ov.ev_bq[slot], 0));
+    hipEvent_t rode = nullptr;
+    if (launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_ids, .n = pl.n_fir, .io = io, .fir_impl = fir_impl, .stream = stream, .wait_ready = !r.fir_waits_event,
+                                   .ready_acquire = r.ready_acquire, .stop = r.rides ? ov.ev_fir[slot] : nullptr, .event_mode = r.fir_launch_mode}, &rode)) return -1;
+    /* (round 5: a launch that carries its kernel timer's stop event needs no second event behind it -- that one says "this FIR has ended"
+     * just as well, and a recorded event is a marker packet the next dispatch queues behind: with every launch of a 0.5-ms FIR timed the
+     * step was 0.5110 ms against 0.5045 with every fourth) */
+    ov.ev_fir_now[slot] = ov.ev_fir[slot];
+    static const bool timer_doubles = !getenv("AVDSP_TIMER_DOUBLES") || atoi(getenv("AVDSP_TIMER_DOUBLES")) != 0;
+    if (!r.rides && r.fir_launch_mode == 1 && rode && timer_doubles) ov.ev_fir_now[slot] = rode;
+    else if (!r.rides) HIP_TRY(hipEventRecord(ov.ev_fir[slot], stream));
+    return 0;
+}
+
+/* "chain_mem": the trunks' cascades and the ordinary chains' on the caller's block, joined; the stage; the branches' cascades on the
+ * branch block, joined.  Such a plan has no FIR */
+template <int FMT>
+int enqueue_mem_plan(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, hipStream_t stream)
+{
+    if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false, 0) || launch_mem<FMT>(prog, pl, io, stream)) return -1;
+    BlockIO bio = io;
+    bio.in = pl.d_mem_scratch; bio.in_stride = pl.n_mem_cols; bio.in_base = 0;
+    return pl.n_mem_cols && launch_cascades<FMT>(prog, pl, bio, biquad_impl, stream, nullptr, false, 1) ? -1 : 0;
+}
+
+/* cascades, then FIRs, on the caller's stream */
+template <int FMT>
+int enqueue_back_to_back(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
+{
+    if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false)) return -1;
+    /* (a plan with handed FIR chains: the plain ones have a list of their own; else it is every FIR chain, as ever) */
+    const int n_plain = pl.n_fir - pl.n_fir_hand;
+    const int *plain_ids = pl.n_fir_hand ? pl.d_fir_plain.get() : pl.d_fir_ids.get();
+    if (n_plain && shared_path(prog, pl, fir_impl)) {
+        /* chains of one bank on fir_shared, the others on fir_tile as ever: two launches on the stream */
+        if (pl.n_fir_rest && launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_rest, .n = pl.n_fir_rest, .io = io, .fir_impl = fir_impl, .stream = stream})) return -1;
+        if (launch_fir_shared<FMT>(prog, pl, io, stream)) return -1;
+        prog->sh_chains_now = pl.n_sh_chains; prog->sh_groups_now = pl.n_sh_groups;
+    } else if (pl.n_fir) {
+        if (n_plain && launch_fir<FMT>(prog, pl, {.ids = plain_ids, .n = n_plain, .io = io, .fir_impl = fir_impl, .stream = stream})) return -1;
+        prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;
+    }
+    /* the handed FIR chains ("fir_tail"): their accumulators into the hand-over block, chain_tail below takes them up */
+    if (pl.n_fir_hand && launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_hand, .n = pl.n_fir_hand, .io = io, .fir_impl = fir_impl, .stream = stream, .hand = true})) return -1;
+    return 0;
+}
+
+/* what closes every block on the caller's stream: the passthrough chains, the dressed ones, the chains with a delay line */
+template <int FMT>
+int enqueue_finishers(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
+{
     if (pl.n_pass) {
         ProfileScope scope(prog, stream, AVDSP_KERNEL_PASS); scope.begin();
         PassArgs a{pl.d_chains, pl.d_pass_ids, pl.n_pass, io};
@@ -5677,6 +5711,37 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+/* facts, gate, probes, route, the read-backs ("fir_ahead_now", "ready_mode", "side_by_side", "fir_shared_*"), then the route's enqueuer */
+template <int FMT>
+int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
+{
+    const LaunchFacts f = launch_facts(prog, pl, io, fir_impl, biquad_impl);
+    const LaunchGate g = launch_gate(f);
+    pl.seq++;                                             /* this launch's number in the plan's ready words */
+    prog->fir_ahead_now = 0;
+    if (g.under) {
+        auto &ov = prog->ov;
+        prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;   /* (the overlap modes keep every chain on launch_fir's kernels) */
+        if (overlap_ready(prog)) return -1;
+        /* the probes' answers are remembered per stream; a staged launch needs its staging blocks, any other the side-by-side probe */
+        if (g.ahead_candidate && ahead_streams_apart(prog, stream)) return -1;
+        hipStream_t on = g.probe_on == kProbeFirTurn ? ov.s_fir[ov.blk & 1] : g.probe_on == kProbeFirFirst ? ov.s_fir[0] : stream;
+        if (launch_staged(f, g, ov.ahead_apart) ? ahead_stage_ready(prog, ahead_stage_words(io.out_stride)) : probe_side_by_side(prog, on)) return -1;
+        const LaunchRoute r = launch_route(f, g, ov.ahead_apart, ov.side_by_side);
+        prog->fir_ahead_now = r.path == kStaged;
+        ov.side_by_side = r.side_by_side;
+        prog->ready_mode_now = r.ready_mode;
+        const int slot = (int)(ov.blk % avdsp_hip_prog::kAhead);
+        if (enqueue_cascades_ahead<FMT>(prog, pl, io, biquad_impl, r, slot)) return -1;
+        if (r.path == kStaged ? enqueue_staged<FMT>(prog, pl, io, fir_impl, stream, slot)
+          : r.path == kOwnFir ? enqueue_own_fir<FMT>(prog, pl, io, fir_impl, stream, on, r, slot)       /* (the stream that was probed is the FIRs') */
+                              : enqueue_direct<FMT>(prog, pl, io, fir_impl, stream, r, slot)) return -1;
+        ov.ev_fir_set[slot] = true;
+        ov.blk++;
+    } else if (pl.has_mem ? enqueue_mem_plan<FMT>(prog, pl, io, biquad_impl, stream) : enqueue_back_to_back<FMT>(prog, pl, io, fir_impl, biquad_impl, stream)) return -1;
+    return enqueue_finishers<FMT>(prog, pl, io, stream);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -5939,18 +6004,17 @@ void avdsp_hip_prog_destroy(avdsp_hip_prog *p)
         (void)hipFree(sl.d_in); (void)hipFree(sl.d_out);
         for (auto e : {sl.h2d, sl.run, sl.d2h}) if (e) (void)hipEventDestroy(e);
     }
-    if (p->s_bq) (void)hipStreamDestroy(p->s_bq);
-    for (auto st : p->retired) (void)hipStreamDestroy(st);
+    p->ov.drop_streams();
+    for (auto st : p->ov.retired) (void)hipStreamDestroy(st);
     for (auto st : p->bq_side) if (st) (void)hipStreamDestroy(st);
     for (auto e : p->bq_join) if (e) (void)hipEventDestroy(e);
     if (p->bq_fork) (void)hipEventDestroy(p->bq_fork);
-    for (auto fs : p->s_fir) if (fs) (void)hipStreamDestroy(fs);
     if (p->ev_unpack) (void)hipEventDestroy(p->ev_unpack);
-    for (int i = 0; i < avdsp_hip_prog::kAhead; i++) { if (p->ev_bq[i]) (void)hipEventDestroy(p->ev_bq[i]); if (p->ev_fir[i]) (void)hipEventDestroy(p->ev_fir[i]); if (p->ev_out[i]) (void)hipEventDestroy(p->ev_out[i]); }
+    for (auto e : p->ov.ev_out) if (e) (void)hipEventDestroy(e);
     (void)hipFree(p->d_buf); (void)hipFree(p->d_in); (void)hipFree(p->d_out); (void)hipFree(p->d_tpdf); (void)hipFree(p->d_frame);
     (void)hipHostFree(p->h_small); (void)hipHostFree(p->h_ready_flag);
     (void)hipHostFree(p->fs_h); (void)hipFree(p->fs_table);
-    for (auto e : p->launch_ev) if (e) (void)hipEventDestroy(e);
+    for (auto e : p->ov.launch_ev) if (e) (void)hipEventDestroy(e);
     (void)hipFree(p->d_tpdf_seq); (void)hipFree(p->d_addend); (void)hipFree(p->d_ready_timeouts); for (auto &x : p->alias) (void)hipFree(x.buf);
     (void)hipFree(p->d_inst_buf); (void)hipFree(p->d_inst_tpdf); (void)hipFree(p->d_inst_frame); (void)hipFree(p->d_inst_seq);
     delete p;
@@ -7501,10 +7565,10 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
     FS_STOP(prog);
     HIP_TRY(hipDeviceSynchronize());                    /* nothing in flight when the launch arrangement changes */
     switch (key) {
-    case AVDSP_OPT_OVERLAP:  prog->overlap = value; for (bool &f : prog->ev_fir_set) f = false; for (bool &f : prog->ev_out_set) f = false; return 0;
+    case AVDSP_OPT_OVERLAP:  prog->overlap = value; prog->ov.forget_events(); return 0;
     /* (the staged copies of the calls so far have run: the device is idle, above) */
     case AVDSP_OPT_FIR_AHEAD: if (value < -1 || value > 1) return set_err("fir_ahead: -1 (by plan), 0 (never) or 1 (whenever it is legal)");
-                              prog->fir_ahead = value; for (bool &f : prog->ev_out_set) f = false; return 0;
+                              prog->fir_ahead = value; prog->ov.forget_events(); return 0;
     case AVDSP_OPT_READY_WORDS: if (value < -1 || value > 2) return set_err("ready_words: -1 (by plan), 0 (events), 1 (the cascade's waves publish) or 2 (a kernel behind the cascade publishes)"); prog->ready_words = value; return 0;
     case AVDSP_OPT_LANE_HW: prog->lane_hw = value != 0; return 0;
     case AVDSP_OPT_FIR_SPLIT: prog->fir_split = value != 0; return 0;
@@ -7518,14 +7582,7 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
     case AVDSP_OPT_CU_SPLIT:
         if (value < -128 || value > 128 || (value & 7)) return set_err("cu_split: 0 (off) or 8, 16, ... 128 CUs for the cascades' stream (negative: the FIRs stay on the caller's stream, unmasked)");
         if (value != prog->cu_split) {                   /* the side streams are made anew with their masks at the next overlapped launch */
-            if (prog->s_bq) { (void)hipStreamDestroy(prog->s_bq); prog->s_bq = nullptr; }
-            for (auto &fs : prog->s_fir) if (fs) { (void)hipStreamDestroy(fs); fs = nullptr; }
-            for (int i = 0; i < avdsp_hip_prog::kAhead; i++) {
-                if (prog->ev_bq[i]) { (void)hipEventDestroy(prog->ev_bq[i]); prog->ev_bq[i] = nullptr; }
-                if (prog->ev_fir[i]) { (void)hipEventDestroy(prog->ev_fir[i]); prog->ev_fir[i] = nullptr; }
-                prog->ev_fir_set[i] = false; prog->ev_fir_now[i] = nullptr;
-            }
-            prog->probed.clear(); prog->ahead_probed.clear();
+            prog->ov.drop_streams();
             prog->cu_split = value;
         }
         return 0;
@@ -7549,12 +7606,12 @@ int avdsp_hip_prog_set_option(avdsp_hip_prog *prog, int key, int value)
 int avdsp_hip_prog_get_option(avdsp_hip_prog *prog, int key)
 {
     switch (key) {
-    case AVDSP_OPT_SIDE_BY_SIDE: return prog->s_bq ? prog->side_by_side : -1;      /* -1: not probed yet (no overlapped launch so far) */
+    case AVDSP_OPT_SIDE_BY_SIDE: return prog->ov.s_bq ? prog->ov.side_by_side : -1;      /* -1: not probed yet (no overlapped launch so far) */
     case AVDSP_OPT_READY_MODE:   return prog->ready_mode_now;
     case AVDSP_OPT_FIR_AHEAD:    return prog->fir_ahead;
     case AVDSP_OPT_FIR_AHEAD_NOW: return prog->fir_ahead_now;
-    case AVDSP_OPT_FIR_AHEAD_APART: return prog->ahead_probed.empty() ? -1 : prog->ahead_apart;
-    case AVDSP_OPT_STREAMS_REMADE: return prog->remade;
+    case AVDSP_OPT_FIR_AHEAD_APART: return prog->ov.ahead_probed.empty() ? -1 : prog->ov.ahead_apart;
+    case AVDSP_OPT_STREAMS_REMADE: return prog->ov.remade;
     case AVDSP_OPT_FRAME_SERVER: return prog->fs_on;
     case AVDSP_OPT_FRAME_SERVER_IDLE_US: return prog->fs_idle_us;
     case AVDSP_OPT_FRAME_SERVER_FRAMES: return (int)std::min(prog->fs_frames, 0x7FFFFFFFll);
@@ -7608,8 +7665,7 @@ int avdsp_hip_profile_read(avdsp_hip_prog *prog, int kind, double *total_ms, int
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, sp.a, sp.b));
         sum += ms; n++; pairs += sp.pair;
-        for (int i = 0; i < avdsp_hip_prog::kAhead; i++)       /* (an event that stood for a FIR's end goes back to the pool: that FIR HAS ended) */
-            if (prog->ev_fir_now[i] == sp.b) { prog->ev_fir_now[i] = prog->ev_fir[i]; prog->ev_fir_set[i] = false; }
+        (void)prog->ov.forget_events(sp.b);                 /* (an event that stood for a FIR's end goes back to the pool: that FIR HAS ended) */
         prog->free_events.push_back(sp.a); prog->free_events.push_back(sp.b);
     }
     prog->last_read_pairs[kind & 7] = pairs;

@@ -645,9 +645,101 @@ inline bool fir_ahead_by_plan(long long n_fir, int max_taps, int frames) { retur
 constexpr long long kAheadStageCapWords = 16ll << 20;
 inline long long ahead_stage_words(int out_stride) { const long long w = (long long)kFirChunk * out_stride; return out_stride > 0 && w <= kAheadStageCapWords ? w : 0; }
 
-/* ---- which FIR kernel a launch takes (DESIGN.md 4.8) ---- */
 /* fir_impl's values, and fir_shared, which launch_all takes for the grouped chains of a plan (shared_path) */
 enum FirFamily { kFirPlain = 0, kFirTile = 1, kFirMfma = 2, kFirStream = 3, kFirFlow = 4, kFirShared = 5 };
+
+/* ---- the route of a block launch: what launch_all (avdsp_kernels.hip) enqueues, decided here and nowhere else ---- */
+/* everything the decision reads */
+struct LaunchFacts {
+    int overlap, cu_split, fir_ahead, ready_words, fir_launch;                  /* the options of those names */
+    int fir_impl, biquad_impl, nframes, out_stride; bool in_place;              /* the call */
+    bool overlap_ok; int n_fir, max_taps, n_ahead_cols, instances, n_sh_groups; /* the plan ... */
+    bool has_taps64, has_ready;                                                 /* ... its per-chain f64 taps, its ready words */
+    int inst_n, chain_inst; bool has_timeouts;                                  /* the program; its time-out words */
+    bool timer_samples;                                                         /* this launch's FIR kernel timer is sampled */
+};
+enum LaunchPath { kBackToBack = 0, kDirect = 1, kOwnFir = 2, kStaged = 3 };
+enum ProbeOn { kProbeCaller = 0, kProbeFirTurn = 1, kProbeFirFirst = 2 };       /* the caller's stream, s_fir[blk & 1], s_fir[0] */
+struct LaunchGate { bool under, own_fir, ahead_candidate; int probe_on; };
+struct LaunchRoute {
+    int path, ready_mode;
+    bool cascade_event, write_through, fir_waits_event, ready_acquire;
+    int fir_launch_mode;                                  /* (the direct path's; 0 elsewhere) */
+    bool rides;
+    int side_by_side;                                     /* what the program remembers of the probes: a staged launch's is its ahead_apart */
+};
+
+/* "ready_words" by the plan (-1).  Mode 2 takes the wait packet off the FIRs' stream (a FIR follows the previous one like any kernel of a
+ * queue): 4096 chains 0.5025 -> 0.4980 ms per step.  Where the cascades are the bound that packet's ~9 us are bubbles they live on: 2048
+ * chains 0.2594 -> 0.2686, 512 chains 0.0864 -> 0.0933 (one box) -- so by default only where a launch is more than one round of waves:
+ * plans of `kReadyBehindTaps` taps in all or more.  (fir_choice's kLeanPlanTaps is the same figure and the same two plans either side of
+ * it, but another experiment -- the chunk boundary, not the wait packet: two names, so that measuring one again does not move the other.) */
+constexpr long long kReadyBehindTaps = 12000000ll;
+constexpr long long kLeanPlanTaps = 12000000ll;         /* fir_tile's lean chunk boundary by the plan: the measurements are in fir_choice */
+/* "fir_launch" by the plan (-1): mode 2 (a start and a stop event on the dispatch) where the cascade of the next blocks is what the step
+ * waits for -- plans of at most `kPairLaunchTaps` taps in all: 512 chains 0.0971 -> 0.0868 ms, 1024 chains 0.1559 -> 0.1464, cfg5's
+ * 2048-chain shard 0.1575 -> 0.1477; on the long launches it only costs (0.5078 -> 0.5202) -- and blocks of more than `kPairLaunchFrames`
+ * frames (round 5, tools/shard_blocks_ab.sh: mode 2's empty microseconds only pay where the cascades are the clock, and that takes a block
+ * long enough for them to be -- shards of 512 / 1024 chains, mode 2 against mode 1: 86.9 / 90.8 and 146.5 / 148.6 us at 1024 frames, but
+ * 150.4 / 138.0 at 768, 91.2 / 78.1 and 57.6 / 51.6 at 512, 58.1 / 47.9 and 56.6 / 45.4 at 256); else mode 1. */
+constexpr long long kPairLaunchTaps = 6000000ll;
+constexpr int kPairLaunchFrames = 768;
+
+/* Phase 1, before any probe.  `ahead_candidate`: the staged path ("fir_ahead") is eligible, legal and either forced or
+ * wanted by the plan; only then are its four streams probed (ahead_streams_apart).  Not eligible, and the call takes another path as
+ * ever: chain instances, "overlap" 2 (its own contract), "cu_split"; a plan with impulse groups (the shared-impulse path's plans: their
+ * per-chain taps may still have to be made, by a kernel on the launch's stream -- ensure_private_taps -- which nothing orders in front of
+ * the OTHER stream's FIR), a fir_impl other than fir_tile's (fir_stream and fir_flow make their operand ring the same way:
+ * ensure_operand_ring): whatever a staged launch reads exists since the plan was built.  Not legal: an in-place call (the next call's
+ * cascade reads its input at once, from the stream of the cascades), a window over the staging cap.  (Plans with handed FIR chains or a
+ * mux stage have no overlap at all: overlap_ok.) */
+inline LaunchGate launch_gate(const LaunchFacts &f)
+{
+    LaunchGate g{};
+    g.under = f.overlap && f.overlap_ok && f.biquad_impl && f.fir_impl;
+    g.own_fir = f.overlap >= 2 || f.cu_split > 0;       /* the FIRs on a stream of the library's own */
+    const bool eligible = g.under && f.fir_ahead != 0 && !g.own_fir && f.n_ahead_cols > 0 && f.instances <= 1 && f.inst_n <= 1 && f.chain_inst <= 1 &&
+                          f.fir_impl == kFirTile && f.n_sh_groups == 0 && f.has_taps64;
+    const bool legal = ahead_stage_words(f.out_stride) > 0 && !f.in_place;
+    g.ahead_candidate = eligible && legal && (f.fir_ahead == 1 || fir_ahead_by_plan(f.n_fir, f.max_taps, f.nframes));
+    g.probe_on = f.overlap >= 2 ? kProbeFirTurn : f.cu_split > 0 ? kProbeFirFirst : kProbeCaller;
+    return g;
+}
+
+/* Phase 2, after the probes: `ahead_apart` is ahead_streams_apart's answer (asked and read for a candidate only), `side_by_side`
+ * probe_side_by_side's on g.probe_on (asked and read where the launch is not staged: launch_staged says so in between). */
+inline bool launch_staged(const LaunchFacts &f, const LaunchGate &g, int ahead_apart) { return g.ahead_candidate && (f.fir_ahead == 1 || ahead_apart); }      /* (by the plan: only where it can gain) */
+inline LaunchRoute launch_route(const LaunchFacts &f, const LaunchGate &g, int ahead_apart, int side_by_side)
+{
+    LaunchRoute r{};
+    if (!g.under) return r;                               /* kBackToBack: cascades and FIRs on the caller's stream, nothing else applies */
+    const bool staged = launch_staged(f, g, ahead_apart);
+    r.side_by_side = staged ? ahead_apart : side_by_side;
+    const bool tile_or_flow = f.fir_impl == kFirTile || f.fir_impl == kFirFlow;
+    /* fir_tile finds its cascades' blocks through the ready words; the other FIR kernels wait for the cascades' event */
+    const bool can_words = tile_or_flow && f.has_ready && f.has_timeouts && r.side_by_side;
+    /* (kReadyBehindTaps; not with "overlap" 2: two FIRs in flight, the later one's waves would sit on their SIMDs looking at words of a
+     * cascade that both of them starve -- 0.496 -> 0.547 ms; nor with a staged launch, for the same reason: the event, whatever
+     * "ready_words" says) */
+    const int rw = staged ? 0 : f.ready_words >= 0 ? f.ready_words : (f.overlap == 1 && (long long)f.n_fir * f.max_taps >= kReadyBehindTaps ? 2 : 0);
+    const bool behind = rw == 2 && can_words;                                       /* a kernel behind the cascade publishes */
+    const bool words = (rw == 1 && f.fir_impl == kFirTile && can_words) || behind;      /* the FIR looks at the words: no event wait on its stream */
+    r.path = staged ? kStaged : g.own_fir ? kOwnFir : kDirect;
+    r.ready_mode = behind ? 2 : words ? 1 : 0;
+    r.cascade_event = !words;
+    r.write_through = words && !behind;                   /* the cascade's own waves publish: write-through ring stores */
+    r.fir_waits_event = !words;
+    r.ready_acquire = words && (!behind || f.overlap >= 2);
+    if (r.path == kDirect) {
+        r.fir_launch_mode = !tile_or_flow ? 0 : f.fir_launch >= 0 ? f.fir_launch
+                          : ((long long)f.n_fir * f.max_taps <= kPairLaunchTaps && f.nframes > kPairLaunchFrames) ? 2 : 1;
+        /* (a launch whose kernel timer is sampled carries the timer's events instead; its event is then recorded behind it) */
+        r.rides = r.fir_launch_mode == 1 && !f.timer_samples;
+    }
+    return r;
+}
+
+/* ---- which FIR kernel a launch takes (DESIGN.md 4.8) ---- */
 struct FirChoice { int family, R; bool BIG, SPLIT, LEAN; bool HAND = false; };       /* R: row tiles per wave (fir_mfma: its NG); the flags are fir_tile's / fir_flow's, else false;
                                                                                          HAND: the launch of a plan's handed FIR chains (fir_hand_choice) */
 inline bool operator==(const FirChoice &a, const FirChoice &b) { return a.family == b.family && a.R == b.R && a.BIG == b.BIG && a.SPLIT == b.SPLIT && a.LEAN == b.LEAN && a.HAND == b.HAND; }
@@ -702,9 +794,9 @@ inline FirChoice fir_choice(int impl, long long n, int frames, const FirOptions 
         const int rows = fir_rows_for(o.fir_rows, n, 1, frames, 256);
         /* the lean chunk boundary (fir_tile, LEAN) where it was measured to win (tools/fir_boundary_lab.sh, one box, long / lean):
          * plans without cascades in front (256 chains x 4096 taps: 40.9 -> 39.4 us per step) and launches of more than one round of
-         * waves (4096 chains: 0.511 -> 0.506 ms).  In between, the next blocks' cascades run beside the FIR and live on the long
+         * waves (4096 chains: 0.511 -> 0.506 ms; kLeanPlanTaps).  In between, the next blocks' cascades run beside the FIR and live on the long
          * boundary's bubbles: 2048 chains 0.259 -> 0.269 ms, 1024 chains 0.147 -> 0.154, 512 chains 0.0876 -> 0.0966. */
-        const bool lean = o.fir_lean >= 0 ? o.fir_lean != 0 : (!cascades || plan_taps >= 12000000ll);
+        const bool lean = o.fir_lean >= 0 ? o.fir_lean != 0 : (!cascades || plan_taps >= kLeanPlanTaps);
         /* one row tile and at most a wave per SIMD (1024): chunks twice as long (BIG) -- nothing hides a boundary there -- or, with
          * "fir_split" (opt-in, not the reference's summation order), two waves per tile instead */
         const bool few = rows == 1 && waves1 <= 1024;
