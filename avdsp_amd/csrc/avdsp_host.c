@@ -120,6 +120,7 @@ typedef struct avdsp_ctx {
     int             opt_chain_delay;                       /* "chain_delay": one DSP_DELAY per chain, on either side of the SAT0DB slot, lowered to the chain kernels (default 0) */
     int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
     int             opt_chain_mem;                         /* "chain_mem": STORE_MEM trunks and LOAD_MEM branches lowered to the chain kernels (default 0) */
+    int             opt_mem_fir;                           /* "mem_fir": with "chain_mem", a DSP_FIR in a trunk or a branch on the chain kernels, formats 4 and 6 (default 0) */
     int             opt_chain_copy;                        /* "chain_copy": DSP_LOAD_STORE lists lowered to the chain kernels' side as one copy launch (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
@@ -314,13 +315,15 @@ static const option_row g_options[] = {
     { "strand_lanes", OPT_REPLAN, .off = SLOT(opt_strand_lanes) },
     /* what the chain lowering takes (lower_gates); 0: such cores on the interpreter.  DESIGN.md 4.2f (SAT0DB_TPDF / _GAIN / _TPDF_GAIN
      * and a head TPDF_CALC), 4.2g (one DSP_DELAY behind a chain's banks), 4.2h (both behind a DSP_FIR), 4.2i (all of it in cores with
-     * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call) */
+     * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call),
+     * 4.2l (a DSP_FIR in a trunk or a branch) */
     { "chain_finish", OPT_REPLAN, .off = SLOT(opt_chain_finish), ZERO_OR_ONE("chain_finish") },
     { "chain_delay",  OPT_REPLAN, .off = SLOT(opt_chain_delay),  ZERO_OR_ONE("chain_delay") },
     { "fir_tail",     OPT_REPLAN, .off = SLOT(opt_fir_tail),     ZERO_OR_ONE("fir_tail") },
     { "mux_tail",     OPT_REPLAN, .off = SLOT(opt_mux_tail),     ZERO_OR_ONE("mux_tail") },
     { "chain_mem",    OPT_REPLAN, .off = SLOT(opt_chain_mem),    ZERO_OR_ONE("chain_mem") },
     { "chain_copy",   OPT_REPLAN, .off = SLOT(opt_chain_copy),   ZERO_OR_ONE("chain_copy") },
+    { "mem_fir",      OPT_REPLAN, .off = SLOT(opt_mem_fir),      ZERO_OR_ONE("mem_fir") },
     /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it: what
      * dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
     { "rate_count_static", OPT_HOST, .hook = HOOK_RATE_STATIC, .flags = OF_WRITE_ONLY },
@@ -926,8 +929,8 @@ static int dither_width_constant(void)
 
 /* "chain_mem": the memory words of a lowered core against each other and against everything else the core reads.  Words sorted with
  * their chains: two trunks of one word, words one apart, a branch in front of its trunk; then no word under a parameter some opcode
- * of the core reads (a gain computed on the fly), no LOAD_MUX head and no FIR beside them */
-static int check_mem_words(const lowered *L)
+ * of the core reads (a gain computed on the fly), no LOAD_MUX head and -- but under "mem_fir" -- no FIR beside them */
+static int check_mem_words(const lowered *L, int mem_fir)
 {
     if (!L->nmem) return 0;
     long long *w = (long long *)malloc((size_t)L->nmem * sizeof *w);      /* word << 32 | trunk << 31 ... sorted by word, trunks first */
@@ -936,7 +939,7 @@ static int check_mem_words(const lowered *L)
     for (int i = 0; i < L->nchains; i++) {
         const avdsp_chain *c = &L->chains[i];
         if (c->load_mode == AVDSP_LOAD_MUX) { free(w); return fail(-8, "memory words beside LOAD_MUX heads are not lowered to the HIP path"); }
-        if (c->fir_taps) { free(w); return fail(-8, "memory words beside a chain with a DSP_FIR are not lowered to the HIP path"); }
+        if (c->fir_taps && !mem_fir) { free(w); return fail(-8, "memory words beside a chain with a DSP_FIR are not lowered to the HIP path"); }
         if (c->mem_word) w[k++] = ((long long)c->mem_word << 32) | (c->mem_store ? 0 : 1ll << 31) | (long long)i;
     }
     qsort(w, (size_t)k, sizeof *w, cmp_ll);
@@ -974,6 +977,7 @@ typedef struct {
     int      delay;           /* "chain_delay" */
     int      fir_tail;        /* "fir_tail": formats 4 and 6, the chain FIR's */
     int      mux_tail, mem, copy;      /* "mux_tail", "chain_mem", "chain_copy" */
+    int      mem_fir;         /* "mem_fir": only with "chain_mem" */
     unsigned delay_factor;
 } lower_gates;
 
@@ -986,6 +990,7 @@ static lower_gates gates_of(int format)
     g.mux_tail = G.opt_mux_tail;
     g.mem = G.opt_chain_mem;
     g.copy = G.opt_chain_copy;
+    g.mem_fir = G.opt_chain_mem && G.opt_mem_fir;             /* (formats 4 and 6 by what else refuses: lower_fir the int64 model, lower_mem formats 3 and 5) */
     g.delay_factor = delay_line_factor();
     return g;
 }
@@ -1050,7 +1055,8 @@ static int check_lines_vs_fir_history(const lowered *L, const lower_gates *g)
 {
     int nfir = 0;
     for (int i = 0; i < L->nchains; i++) nfir += L->chains[i].fir_taps != 0;
-    if (!L->ndelayed || !g->fir_tail || !nfir) return 0;
+    /* ("mem_fir": FIRs stand beside delayed chains without "fir_tail" too -- a tree's FIR trunk and its delayed IIR ways) */
+    if (!L->ndelayed || !(g->fir_tail || (g->mem_fir && L->nmem)) || !nfir) return 0;
     long long *iv = (long long *)malloc((size_t)(L->ndelayed + nfir) * 3 * sizeof *iv);      /* [first word, words, is a line] */
     if (!iv) return fail(-9, "out of memory");
     int k = 0, clash = 0;
@@ -1171,7 +1177,7 @@ static int lower_mem(lower_walk *W)
     if (!W->open) return fail(-8, "word %d: STORE_MEM without a LOAD", at);
     if (W->cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a memory word in a chain with a LOAD_MUX head is not lowered to the HIP path", at);
     if (W->cur.load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a STORE_MEM in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
-    if (W->fir_op) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
+    if (W->fir_op && !W->g.mem_fir) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
     if (W->cur.n_out || W->cur.sat || W->cur.delay_slot)
         return fail(-8, "word %d: a STORE_MEM behind a STORE, a SAT0DB or a DSP_DELAY is not lowered to the HIP path", at);
     W->cur.mem_word = at + a[0]; W->cur.mem_store = 1;
@@ -1269,7 +1275,7 @@ static int lower_fir(lower_walk *W)
         return W->g.fir_tail ? fail(-8, "word %d: a DSP_DELAY in front of the chain's DSP_FIR is not lowered to the HIP path", at)
                              : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
     if (!W->open || cur->n_out || cur->sat) return fail(-8, "word %d: FIR outside the supported chain order", at);
-    if (cur->load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a DSP_FIR in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
+    if (cur->load_mode == AVDSP_LOAD_MEM && !W->g.mem_fir) return fail(-8, "word %d: a DSP_FIR in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
     if (W->format == DSP_FORMAT_INT64)
         return fail(-8, "word %d: DSP_FIR in int64 mode is undefined behaviour in the reference "
                         "(dsp_firSTD.h:8-35) and is not provided", at);
@@ -1443,7 +1449,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     if (W.g.copy && G.ninst <= 1 && G.shard_world <= 1) rc = drop_dead_stores(L);
     if (!rc) rc = check_copies(L);
     if (!rc && L->nchains == 0 && L->ncopy == 0) rc = fail(-8, "core contains no LOAD..STORE chain");
-    if (!rc) rc = check_mem_words(L);
+    if (!rc) rc = check_mem_words(L, W.g.mem_fir);
     if (!rc) rc = check_mux_beside_tails(L, &W.g);
     if (!rc) rc = check_line_vs_mux_result(L, &W.g);
     if (!rc) rc = check_lines_apart(L, &W.g);
@@ -1942,9 +1948,11 @@ static int fir_groups(const avdsp_chain *ch, int n, int32_t **start, int32_t **m
     int32_t *first = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
     int32_t *len = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n / AVDSP_FIR_GROUP_MIN + 2));
     if (!idx || !st || !mem || !first || !len) { free(idx); free(st); free(mem); free(first); free(len); return -1; }
-    int m = 0;
+    int m = 0, has_mem = 0;
+    /* ("mem_fir": the chains of a core that holds a memory word are in no group -- trunks hand over, branches follow the stage) */
+    for (int i = 0; i < n; i++) has_mem |= ch[i].mem_word != 0;
     /* (handed FIR chains -- "fir_tail": a delay or a dressed finish behind the FIR -- are in no group: fir_shared stores, it hands nothing over) */
-    for (int i = 0; i < n; i++) if (ch[i].fir_taps > 0 && !ch[i].finish && !ch[i].delay_slot) idx[m++] = i;
+    for (int i = 0; i < n && !has_mem; i++) if (ch[i].fir_taps > 0 && !ch[i].finish && !ch[i].delay_slot) idx[m++] = i;
     g_fg_chains = ch;
     qsort(idx, (size_t)m, sizeof(int32_t), fir_group_cmp);
     int ng = 0;
@@ -2105,6 +2113,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         const lower_gates g = gates_of(format);             /* (as the lowering saw them: it checked the lines' extents with this factor) */
         d.delay_line_factor = g.delay_factor;
         d.fir_tail = g.fir_tail; d.mux_tail = g.mux_tail; d.chain_mem = g.mem;
+        d.mem_fir = g.mem_fir;
         d.chain_copy = g.copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
@@ -2384,6 +2393,28 @@ int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, in
     }
     core_report_close(&R);
     put(trunks, nt); put(branches, nb); put(constant_branches, nc);
+    return 0;
+}
+
+/* What "mem_fir" makes of the core -- its trunks with a DSP_FIR (taps at the current rate) in front of the STORE_MEM, its branches with
+ * one, and how many of those branches are handed FIR chains ("fir_tail": a DSP_DELAY and / or a dressed finish behind the FIR)
+ * (DESIGN.md 4.2l).  Counted over the whole core, as dspRuntimeMemInfo. */
+int dspRuntimeMemFirInfo(int format, opcode_t *core, int *fir_trunks, int *fir_branches, int *of_them_handed)
+{
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int nt = 0, nb = 0, nh = 0;
+    for (int i = 0; i < R.L.nchains; i++) {
+        const avdsp_chain *c = &R.L.chains[i];
+        if (!c->fir_taps) continue;
+        nt += c->mem_store != 0;
+        if (c->load_mode != AVDSP_LOAD_MEM) continue;
+        nb++;
+        nh += c->finish || c->delay_slot;
+    }
+    core_report_close(&R);
+    put(fir_trunks, nt); put(fir_branches, nb); put(of_them_handed, nh);
     return 0;
 }
 
@@ -3201,7 +3232,7 @@ int dspRuntimeSetInstances(int n)
     G.inst_chain_mode = 0;
     if (G.dev && avdsp_hip_set_instances(G.dev, n > 0 ? n : 1)) return hip_fail();      /* (else: when the device copy is made) */
     /* ("chain_finish": dressed cores are chain cores only while the program has no instances -- lowered again on either side) */
-    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail || G.opt_chain_mem || G.opt_chain_copy) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
+    if ((G.opt_chain_finish || G.opt_chain_delay || G.opt_fir_tail || G.opt_mux_tail || G.opt_chain_mem || G.opt_mem_fir || G.opt_chain_copy) && (n > 1) != (G.ninst > 1) && replan()) return g_err_code;
     G.ninst = n;
     /* The strand plans know nothing of instances: while a program HAS instances its interpreted cores run as the interpreter's pieces
      * ("strand_lanes" 0, the plans rebuilt once, here -- not silently inside a block call), and dspRuntimeSetInstances(0) gives the

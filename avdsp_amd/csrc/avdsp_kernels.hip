@@ -57,17 +57,23 @@ using namespace avdsp_layout;      /* the plan's host-side tables, their records
  * dressed chains look at -- in a table of its own (FinishRec, indexed like the records).  The record every other kernel copies into
  * its registers, and into the stack frame of its replay, stays the 17 words it was. */
 struct DevChain {
+    /* nsec: the sections of the chain's cascade -- or kSecFed (-1, below): none, and a stage in front has fed the chain's FIR ring.
+     * Whoever reads it may test it against 0 or count up to it; arithmetic on it (nsec - 1, sec_base + nsec) must tell kSecFed apart */
     int32_t  in_io, load_mode; uint32_t gain_bits; int32_t nsec, sec_base, fir_taps, fir_coef_word, fir_state_word, sat, n_out;
     int32_t  out_io[AVDSP_MAX_STORES];
     int32_t  mux_word, mux_count, mux_result_word;
 };
 struct FinishRec { int finish; unsigned gain_bits; };      /* avdsp_chain::finish, ::finish_gain_bits */
+/* "mem_fir" (DESIGN.md 4.2l): a branch that is a FIR alone and whose ring mem_stage has fed (kLoadFed) has no section, but its record
+ * says nsec -1: the FIR kernels and fir_feed append the input of a chain with nsec 0 themselves, and a second append would shift its
+ * history by a block.  No cascade kernel ever sees such a record (the launch groups are made of the host's section counts) */
+constexpr int kSecFed = -1;
 inline std::vector<DevChain> dev_records(const std::vector<avdsp_chain> &v)
 {
     std::vector<DevChain> o(v.size());
     for (size_t i = 0; i < v.size(); i++) {
         const avdsp_chain &c = v[i];
-        o[i] = DevChain{c.in_io, c.load_mode, c.gain_bits, c.nsec, c.sec_base, c.fir_taps, c.fir_coef_word, c.fir_state_word, c.sat, c.n_out,
+        o[i] = DevChain{c.in_io, c.load_mode, c.gain_bits, c.load_mode == kLoadFed ? kSecFed : c.nsec, c.sec_base, c.fir_taps, c.fir_coef_word, c.fir_state_word, c.sat, c.n_out,
                         {c.out_io[0], c.out_io[1], c.out_io[2], c.out_io[3]}, c.mux_word, c.mux_count, c.mux_result_word};
     }
     return o;
@@ -3605,9 +3611,20 @@ struct MemArgs {
     unsigned *scratch; int scratch_stride; /* the branch block */
     BlockIO io;
 };
-template <int FMT>
-__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgs a)
+/* FEED ("mem_fir", DESIGN.md 4.2l, formats 4 and 6): the plan has branches that are a FIR alone.  Such a branch has no column: the word
+ * its FIR takes of a frame's accumulator -- (float)X, subnormals flushed, what fir_input_word makes of a kLoadRaw column -- goes
+ * straight into the chain's ring, from the lane that holds the frame.  A wave's 64 lanes are 64 consecutive frames, so a feed is a run
+ * of 256 bytes of the float row (and its copy R floats on) and of 512 of the operand row.  The branch's record says kSecFed sections: no
+ * FIR kernel appends its input again.  FEED false is the kernel as it was. */
+struct MemArgsFeed : MemArgs {
+    Ring ring;
+    const int *feed_start; const MemFeed *feed;      /* the feeds of tree k: feed[feed_start[k] .. feed_start[k + 1]) */
+};
+template <bool FEED> using MemArgsF = std::conditional_t<FEED, MemArgsFeed, MemArgs>;
+template <int FMT, bool FEED = false>
+__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsF<FEED> a)
 {
+    static_assert(!FEED || FMT == 4 || FMT == 6, "the chain FIR's formats");
     using alu_t = typename Alu<FMT>::type;
     if constexpr (FMT != 2) flush_f32_subnormals_like_the_reference();
     __shared__ unsigned s_word[kMemTileTrees][kMemFrames + 1];
@@ -3629,6 +3646,10 @@ __global__ __launch_bounds__(kBlock) void mem_stage(const MemArgs a)
             if constexpr (FMT == 2) X = (long long)u; else X = __longlong_as_double((long long)u);
         }
         s_word[tl][lane] = narrow_stage<FMT>(X);
+        if constexpr (FEED) {
+            const unsigned fed = ftz_bits(narrow_stage<FMT>(X));
+            for (int k = a.feed_start[tile.tree0 + tl]; k < a.feed_start[tile.tree0 + tl + 1]; k++) ring_put(a.ring, a.feed[k].cid, f, fed);
+        }
         if (tr.src != kMemSrcRow && tr.row >= 0) a.hand[(size_t)tr.row * kFirChunk + f] = u;
         for (int k = 0; k < tr.n_own; k++) {
             const MemOwn o = a.own[tr.first_own + k];
@@ -4507,6 +4528,11 @@ struct Plan {
     DevArr<MemTree> d_mem_trees; DevArr<MemOwn> d_mem_own; DevArr<MemTile> d_mem_tiles; DevArr<int> d_mem_col_tree;
     DevArr<unsigned> d_mem_scratch;
     int n_mem_tiles = 0, n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
+    /* "mem_fir" (DESIGN.md 4.2l): the trunks with a FIR (a HAND launch in front of the stage); the plain FIR chains of such a plan,
+     * branches among them (d_fir_plain, made whenever the plan has memory words and FIRs); the stage's ring feeds */
+    DevArr<int> d_fir_trunk; int n_fir_trunk = 0, n_fir_plain = 0;
+    int n_append_trunk = 0, n_append_plain = 0, n_append_hand = 0;      /* per list: the chains that append their own input (FirLaunch::appends) */
+    DevArr<MemFeed> d_mem_feed; DevArr<int> d_mem_feed_start; int n_mem_feed = 0;
     /* "chain_copy" (DESIGN.md 4.2k): the live pairs of the core's DSP_LOAD_STORE lists, by destination; copy_pairs once per block call */
     DevArr<CopyPair> d_copy; int n_copy = 0;
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
@@ -5115,6 +5141,8 @@ int launch_fir_shared(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t st
 struct FirLaunch {
     const int *ids; int n; BlockIO io; int fir_impl; hipStream_t stream;
     bool wait_ready = false, ready_acquire = false; hipEvent_t stop = nullptr; bool hand = false; int event_mode = 0;
+    int appends = -1;        /* chains of the list that append their own input (a FIR alone that no stage has fed); -1: not counted per list,
+                                the plan's n_fir_only stands for it ("mem_fir": enqueue_mem_plan's lists have their counts) */
 };
 template <int FMT>
 int launch_fir(avdsp_hip_prog *prog, Plan &pl, const FirLaunch &L, hipEvent_t *rode = nullptr)
@@ -5123,6 +5151,7 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const FirLaunch &L, hipEvent_t *r
     else {
         const int *const ids = L.ids; const int n = L.n, fir_impl = L.fir_impl; const BlockIO &io = L.io;
         const hipStream_t stream = L.stream; const hipEvent_t stop = L.stop; const bool hand = L.hand;
+        const int n_append = L.appends >= 0 ? L.appends : pl.n_fir_only;
         if (hand && (!pl.d_hand || !pl.d_hand_row)) return set_err("a launch of handed FIR chains without its hand-over block");
         if (ensure_private_taps(prog, pl, stream)) return -1;
         ProfileScope scope(prog, stream, AVDSP_KERNEL_FIR);
@@ -5148,7 +5177,7 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const FirLaunch &L, hipEvent_t *r
                  * 91 us, longer than its 1024-frame block): those regroup like everybody else. */
                 const bool quarters = c.SPLIT || (c.BIG && n <= cus);
                 if (!quarters) wpc = tiles <= 1 ? 1 : tiles <= 2 ? std::min(2, wpc) : wpc;
-                a.all_cascaded = pl.n_fir_only == 0;
+                a.all_cascaded = n_append == 0;
             }
             a.wpc_shift = wpc == 4 ? 2 : wpc == 2 ? 1 : 0;
             const int nwg = (n * wpc * (c.SPLIT ? 2 : 1) + 3) / 4;
@@ -5165,7 +5194,7 @@ int launch_fir(avdsp_hip_prog *prog, Plan &pl, const FirLaunch &L, hipEvent_t *r
         if (c.family == kFirStream) {
             if (ensure_operand_ring(prog, pl, stream)) return -1;
             FirTileArgs a = fir_tile_args(prog, pl, ids, n, io, false);
-            if (pl.n_fir_only && launch_fir_feed((const void *)fir_feed<FMT>, a, stream)) return -1;
+            if (n_append && launch_fir_feed((const void *)fir_feed<FMT>, a, stream)) return -1;
             /* one wave per SIMD at most: 256 workgroups of four waves, each wave takes its units in turn */
             const int tiles = (io.nframes + v->fw - 1) / v->fw;
             const int nwg = std::min((n * tiles + 3) / 4, cus);
@@ -5470,7 +5499,17 @@ int launch_mem(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
     a.buf = prog->d_buf; a.trees = pl.d_mem_trees; a.own = pl.d_mem_own; a.tiles = pl.d_mem_tiles; a.col_tree = pl.d_mem_col_tree;
     a.hand = pl.d_hand; a.addend = prog->d_addend ? prog->d_addend + pl.block_f0 : nullptr;
     a.scratch = pl.d_mem_scratch; a.scratch_stride = pl.n_mem_cols; a.io = io;
-    hipLaunchKernelGGL(mem_stage<FMT>, dim3((unsigned)pl.n_mem_tiles, (unsigned)((io.nframes + kMemFrames - 1) / kMemFrames)), dim3(kBlock), 0, stream, a);
+    const dim3 grid((unsigned)pl.n_mem_tiles, (unsigned)((io.nframes + kMemFrames - 1) / kMemFrames));
+    if (pl.n_mem_feed) {
+        /* ("mem_fir": branches that are a FIR alone -- the FEED form puts their input into their rings) */
+        if constexpr (FMT == 4 || FMT == 6) {
+            if (!pl.d_mem_feed || !pl.d_mem_feed_start || !pl.d_ring) return set_err("a memory-word stage that feeds FIR rings without its tables");
+            MemArgsFeed fa{};
+            static_cast<MemArgs &>(fa) = a;
+            fa.ring = plan_ring(pl); fa.feed_start = pl.d_mem_feed_start; fa.feed = pl.d_mem_feed;
+            hipLaunchKernelGGL((mem_stage<FMT, true>), grid, dim3(kBlock), 0, stream, fa);
+        } else return set_err("a memory-word stage that feeds FIR rings: formats 4 and 6 only");
+    } else hipLaunchKernelGGL(mem_stage<FMT>, grid, dim3(kBlock), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -5645,14 +5684,28 @@ int enqueue_direct(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hip
 }
 
 /* "chain_mem": the trunks' cascades and the ordinary chains' on the caller's block, joined; the stage; the branches' cascades on the
- * branch block, joined.  Such a plan has no FIR */
+ * branch block, joined.  "mem_fir"  adds the FIRs, each list a launch of its own on the same stream: the trunks' in
+ * front of the stage -- a HAND form, the sums into the trunks' rows, where the stage finds them as it finds a cascade's -- and behind
+ * the branches' cascades the plain FIR chains (ordinary ones and branches), then the handed ones, whose rows chain_tail takes up.  A
+ * FIR alone appends its input inside its launch as ever (launch_fir); a branch that is one has been fed by the stage.  No shared path,
+ * no overlap: such a plan has neither */
 template <int FMT>
-int enqueue_mem_plan(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biquad_impl, hipStream_t stream)
+int enqueue_mem_plan(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biquad_impl, hipStream_t stream)
 {
-    if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false, 0) || launch_mem<FMT>(prog, pl, io, stream)) return -1;
+    if (launch_cascades<FMT>(prog, pl, io, biquad_impl, stream, nullptr, false, 0)) return -1;
+    if (pl.n_fir_trunk && launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_trunk, .n = pl.n_fir_trunk, .io = io, .fir_impl = fir_impl, .stream = stream, .hand = true,
+                                                    .appends = pl.n_append_trunk})) return -1;
+    if (launch_mem<FMT>(prog, pl, io, stream)) return -1;
     BlockIO bio = io;
     bio.in = pl.d_mem_scratch; bio.in_stride = pl.n_mem_cols; bio.in_base = 0;
-    return pl.n_mem_cols && launch_cascades<FMT>(prog, pl, bio, biquad_impl, stream, nullptr, false, 1) ? -1 : 0;
+    if (pl.n_mem_cols && launch_cascades<FMT>(prog, pl, bio, biquad_impl, stream, nullptr, false, 1)) return -1;
+    if (!pl.n_fir) return 0;
+    prog->sh_chains_now = prog->sh_groups_now = prog->sh_rows_now = 0;
+    if (pl.n_fir_plain && launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_plain, .n = pl.n_fir_plain, .io = io, .fir_impl = fir_impl, .stream = stream,
+                                                    .appends = pl.n_append_plain})) return -1;
+    if (pl.n_fir_hand && launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_hand, .n = pl.n_fir_hand, .io = io, .fir_impl = fir_impl, .stream = stream, .hand = true,
+                                                   .appends = pl.n_append_hand})) return -1;
+    return 0;
 }
 
 /* cascades, then FIRs, on the caller's stream */
@@ -5740,7 +5793,7 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
                               : enqueue_direct<FMT>(prog, pl, io, fir_impl, stream, r, slot)) return -1;
         ov.ev_fir_set[slot] = true;
         ov.blk++;
-    } else if (pl.has_mem ? enqueue_mem_plan<FMT>(prog, pl, io, biquad_impl, stream) : enqueue_back_to_back<FMT>(prog, pl, io, fir_impl, biquad_impl, stream)) return -1;
+    } else if (pl.has_mem ? enqueue_mem_plan<FMT>(prog, pl, io, fir_impl, biquad_impl, stream) : enqueue_back_to_back<FMT>(prog, pl, io, fir_impl, biquad_impl, stream)) return -1;
     return enqueue_finishers<FMT>(prog, pl, io, stream);
 }
 
@@ -6088,9 +6141,12 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         for (size_t i = 0; i < fin.size(); i++) fin[i] = FinishRec{L.dev_chains[i].finish, L.dev_chains[i].finish_gain_bits};
         if (pl.d_finish.upload(fin)) return -1;
     }
-    if (!t.fir_hand.empty()) {
-        pl.n_fir_hand = (int)t.fir_hand.size();
-        if (pl.d_fir_hand.upload(t.fir_hand) || pl.d_fir_plain.upload(t.fir_plain)) return -1;
+    if (!t.fir_hand.empty() || (t.has_mem && !t.fir.empty())) {
+        /* ("mem_fir": a plan with memory words launches its lists one by one -- the trunks' FIRs, the plain ones, the handed ones) */
+        pl.n_fir_hand = (int)t.fir_hand.size(); pl.n_fir_plain = (int)t.fir_plain.size(); pl.n_fir_trunk = (int)t.fir_trunk.size();
+        if (pl.d_fir_hand.upload(t.fir_hand) || pl.d_fir_plain.upload(t.fir_plain) || pl.d_fir_trunk.upload(t.fir_trunk)) return -1;
+        auto appends = [&](const std::vector<int> &ids) { int k = 0; for (int i : ids) k += !t.chains[i].nsec && t.chains[i].load_mode != kLoadFed; return k; };
+        pl.n_append_trunk = appends(t.fir_trunk); pl.n_append_plain = appends(t.fir_plain); pl.n_append_hand = appends(t.fir_hand);
     }
     if (!t.tail.empty() || t.has_mem) {
         /* (a delayed chain's cascade ends in the record of its own index -- of a long one, its last piece; a handed FIR chain's row is
@@ -6188,6 +6244,8 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         pl.n_mem_trunks = t.n_mem_trunks; pl.n_mem_branches = t.n_mem_branches; pl.n_mem_constant = t.n_mem_constant;
         if (pl.d_mem_trees.upload(t.mem_tree_list) || pl.d_mem_own.upload(t.mem_own) || pl.d_mem_tiles.upload(t.mem_tiles) || pl.d_mem_col_tree.upload(t.mem_col_tree)) return -1;
         if (t.n_mem_cols && pl.d_mem_scratch.alloc((size_t)kFirChunk * t.n_mem_cols) != hipSuccess) return set_err("hipMalloc(branch block of %d columns)", t.n_mem_cols);
+        pl.n_mem_feed = (int)t.mem_feed.size();
+        if (pl.n_mem_feed && (pl.d_mem_feed.upload(t.mem_feed) || pl.d_mem_feed_start.upload(t.mem_feed_start))) return -1;
     }
     if (pl.overlap_ok) {                                  /* ready words, all at launch number 0 */
         if (pl.d_ready.alloc((size_t)d->nchains) != hipSuccess ||

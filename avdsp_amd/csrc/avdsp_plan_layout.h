@@ -9,7 +9,8 @@
  *     mux_records      (plans with LOAD_MUX chains) the stage's records from the chains and those words, which the caller downloads; which chains the
  *                      stage stores, finishes or hands over itself ("mux_tail")
  *     copy_list        ("chain_copy") the live DSP_LOAD_STORE pairs against each other and against every IO the chains load and store; sorted by destination
- *     mem_trees        (plans with trunks or AVDSP_LOAD_MEM branches, "chain_mem") the trees, their hand-over rows, the columns of the branch block, mem_stage's tiles
+ *     mem_trees        (plans with trunks or AVDSP_LOAD_MEM branches, "chain_mem") the trees, their hand-over rows, the columns of the branch block, mem_stage's tiles;
+ *                      ("mem_fir") the trunks with a FIR and the stage's ring feeds
  *     check_chains     section ranges, IOs, FIR words, dressed finishes, delay lines, the IO spans, max_taps, the `fir`, `fir_hand`, `pass` and `tail` lists
  *     cascade_groups   launch groups by section count (dressed and delayed chains apart), pieces of long cascades, biquad_row's records, the merged row table
  *     shared_fir_layout, mux_tiles, and the scalars (fir_groups_per_chunk, ring_length, taps64_pitch, stores_whole_window, overlap_ok)
@@ -39,6 +40,10 @@ constexpr int kTapsTail = 384;       /* zeros behind them (the last k-steps and 
  * kStoreRaw (in the chain record's `sat`) stores the last section's result word as it is.  Device-side only; the host's descriptors
  * never hold them (check_heads refuses the load mode). */
 constexpr int kLoadRaw = 2, kStoreRaw = 2;
+/* "mem_fir" (DESIGN.md 4.2l): the load mode of a branch that is a FIR alone.  mem_stage has put the chain's input into its ring (the FEED
+ * form); no FIR kernel and no fir_feed may append it a second time (they append for records with 0 sections: the device record of such a
+ * chain says -1, dev_records in avdsp_kernels.hip).  Never in the host's descriptors, as kLoadRaw */
+constexpr int kLoadFed = 5;
 constexpr int kPieceMax = 16;        /* sections per piece: a cascade of more is cut into pieces that are each one biquad_row launch */
 constexpr int kMuxRows = 64;         /* chains per mux_tile workgroup */
 
@@ -84,6 +89,10 @@ struct MemTree {
 };
 struct MemOwn { int tree, cid, sat, finish; unsigned gain_bits; int n_out, out_io[AVDSP_MAX_STORES]; };
 struct MemTile { int tree0, ntree, col0, ncol; };
+/* "mem_fir" (DESIGN.md 4.2l): a branch with a FIR and no sections has no column -- mem_stage's FEED form puts the word the FIR takes of
+ * every frame's accumulator into the chain's ring.  The feeds tree by tree: those of tree k are mem_feed[mem_feed_start[k] ..
+ * mem_feed_start[k + 1]) (a table beside MemTree, whose layout the stage without feeds keeps) */
+struct MemFeed { int tree, cid; };
 
 /* "chain_copy" (DESIGN.md 4.2k): one live pair of the core's DSP_LOAD_STORE lists -- out[frame][dst] = in[frame][src], the raw word */
 struct CopyPair { int src, dst; };
@@ -132,6 +141,9 @@ struct ChainTables {
      * the accumulators in the hand-over block for chain_tail.  `fir` holds every chain with a FIR, they among them (rings, taps, history);
      * `fir_plain` those that store themselves */
     std::vector<int> fir_hand, fir_plain;
+    /* "mem_fir" (DESIGN.md 4.2l): the trunks with a FIR.  They are in `fir` (ring, taps, history) and in neither list above: their launch,
+     * a HAND form in front of mem_stage, leaves the sums in the trunks' rows, which the stage reads as it reads a cascade's */
+    std::vector<int> fir_trunk;
     /* "chain_mem" (DESIGN.md 4.2j), made by mem_trees: the trees, the columns of the branch block, the branches the stage stores itself.
      * A branch with sections is a kLoadRaw chain of its column (phase 2: its cascade reads the branch block, not the caller's samples);
      * trunks and ordinary chains stay on the caller's block (phase 1) */
@@ -145,6 +157,8 @@ struct ChainTables {
     std::vector<MemTile> mem_tiles;
     std::vector<int> mem_col_tree;       /* per column of the branch block: its tree */
     int n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
+    std::vector<MemFeed> mem_feed;       /* "mem_fir": the branches that are a FIR alone, tree by tree ... */
+    std::vector<int> mem_feed_start;     /* ... [trees + 1]: where each tree's begin (made when there is a feed) */
     /* "chain_copy" (DESIGN.md 4.2k), made by copy_list: the live pairs, sorted by destination (consecutive lanes of copy_pairs store
      * consecutive words where the IOs are).  They count in the IO spans and in stores_whole_window */
     std::vector<CopyPair> copy;
@@ -276,18 +290,22 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
         return true;
     };
     std::vector<int> tree_of(n, -1);
-    for (int i = 0; i < n; i++) if (t.chains[i].fir_taps) return text("chain %d: a FIR beside memory words has no kernel", i);
+    /* ("mem_fir": formats 4 and 6 -- the int64 model has no FIR) */
+    const bool mem_fir = d->mem_fir && (d->format == 4 || d->format == 6);
+    for (int i = 0; i < n && !mem_fir; i++) if (t.chains[i].fir_taps) return text("chain %d: a FIR beside memory words has no kernel", i);
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (!c.mem_store) continue;
-        if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || c.fir_taps || c.in_io < 0) return text("chain %d: not a trunk", i);
+        if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || (c.fir_taps && !mem_fir) || c.in_io < 0) return text("chain %d: not a trunk", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
         int exact;
         if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
         if (exact >= 0) return text("chain %d: a second trunk of memory word %d", i, c.mem_word);
         MemTree tr{};
-        tr.word = c.mem_word; tr.trunk = i; tr.src = c.nsec ? kMemSrcRow : kMemSrcSample;
-        tr.row = c.nsec ? t.n_hand_rows++ : -1;
+        /* (a trunk with a FIR, "mem_fir": its FIR's HAND launch fills the row -- the cascade in front, if any, feeds the ring) */
+        tr.word = c.mem_word; tr.trunk = i; tr.src = c.nsec || c.fir_taps ? kMemSrcRow : kMemSrcSample;
+        tr.row = c.nsec || c.fir_taps ? t.n_hand_rows++ : -1;
+        if (c.fir_taps) t.fir_trunk.push_back(i);
         tr.in_io = c.in_io; tr.load_mode = c.load_mode; tr.gain_bits = c.gain_bits;
         t.mem_kind[i] = 1; t.mem_row[i] = tr.row; t.n_mem_trunks++;
         t.mem_tree_list.push_back(tr);
@@ -295,7 +313,7 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.load_mode != AVDSP_LOAD_MEM) continue;
-        if (c.mem_store || c.fir_taps || (c.n_out < 1 && !(d->chain_copy && c.delay_slot))) return text("chain %d: not a branch", i);
+        if (c.mem_store || (c.fir_taps && !mem_fir) || (c.n_out < 1 && !(d->chain_copy && c.delay_slot))) return text("chain %d: not a branch", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
         int exact;
         if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
@@ -315,10 +333,14 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (size_t k = 0; k < t.mem_tree_list.size(); k++) {
         MemTree &tr = t.mem_tree_list[k];
         tr.col0 = t.n_mem_cols; tr.first_own = (int)t.mem_own.size();
+        t.mem_feed_start.push_back((int)t.mem_feed.size());
         for (int i : members[k]) {
             avdsp_chain &c = t.chains[i];
             c.load_mode = kLoadRaw; c.in_io = 0;
             if (c.nsec) { c.in_io = t.n_mem_cols++; t.mem_col_tree.push_back((int)k); }
+            /* ("mem_fir": a FIR alone -- no column, no record of the stage's own, no row of the tree's: the stage feeds its ring, its FIR
+             * stores it or hands it over like any FIR chain's) */
+            else if (c.fir_taps) { c.load_mode = kLoadFed; t.mem_feed.push_back(MemFeed{(int)k, i}); }
             else if (c.delay_slot) { if (tr.row < 0) tr.row = t.n_hand_rows++; t.mem_row[i] = tr.row; }
             else {
                 MemOwn o{};
@@ -332,7 +354,8 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
             t.mem_tiles.push_back(MemTile{(int)k, 0, tr.col0, 0});
         t.mem_tiles.back().ntree++; t.mem_tiles.back().ncol += tr.ncol;
     }
-    (void)d;
+    t.mem_feed_start.push_back((int)t.mem_feed.size());
+    if (t.mem_feed.empty()) t.mem_feed_start.clear();
     return "";
 }
 
@@ -352,7 +375,6 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             if (c.out_io[k] < 0) return text("chain %d: bad IO", i);
             t.io_out_min = std::min(t.io_out_min, c.out_io[k]); t.io_out_max = std::max(t.io_out_max, c.out_io[k]);
         }
-        if (t.mem_kind[i] == 1) { t.hand_row[i] = t.mem_row[i]; continue; }      /* (a trunk, "chain_mem": its cascade hands over to mem_stage, nothing else follows) */
         if (c.fir_taps) {
             if (d->format == 2) return text("chain %d: FIR has no int64 definition", i);
             if (c.fir_coef_word < 0 || c.fir_coef_word + c.fir_taps > buf_words ||
@@ -361,6 +383,9 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             t.fir.push_back(i);
             t.max_taps = std::max(t.max_taps, c.fir_taps);
         }
+        /* (a trunk, "chain_mem": its cascade -- "mem_fir": or its FIR, which is in `fir` and in mem_trees' `fir_trunk` -- hands over to
+         * mem_stage, nothing else follows) */
+        if (t.mem_kind[i] == 1) { t.hand_row[i] = t.mem_row[i]; continue; }
         if (c.finish) {
             /* a dressed finish (avdsp_chain::finish): the chain kernels of formats 2, 4 and 6, no FIR in front (but under "fir_tail"), no LOAD_MUX plan (but under "mux_tail"), no instances */
             if (c.finish < AVDSP_FINISH_TPDF || c.finish > AVDSP_FINISH_TPDF_GAIN || c.sat != 1) return text("chain %d: finish %d", i, c.finish);
@@ -450,9 +475,10 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
         /* dressed chains: launch groups of their own, next to the others; delayed chains (dressed or not): again groups of their own.
          * Not the cascade of a handed FIR chain ("fir_tail"): delay and finish stand behind its FIR, the cascade feeds the ring like any */
         const bool fir = t.chains[i].fir_taps != 0;
-        /* ("chain_mem": a trunk hands over like a delayed chain; branches are groups of their own, of the second phase) */
+        /* ("chain_mem": a trunk hands over like a delayed chain -- "mem_fir": unless a FIR stands behind its cascade, which then feeds
+         * the ring like any; branches are groups of their own, of the second phase) */
         const int kind = t.has_mem ? t.mem_kind[i] : 0, phase = kind == 2 ? 1 : 0;
-        const bool hand = (!fir && t.chains[i].delay_slot != 0) || kind == 1, wide = hand || (!fir && t.chains[i].finish != 0);
+        const bool hand = !fir && (t.chains[i].delay_slot != 0 || kind == 1), wide = hand || (!fir && t.chains[i].finish != 0);
         auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand && g.phase == phase; });
         if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; it->phase = phase; }
         it->ids.push_back(i);
@@ -527,6 +553,8 @@ struct SharedLayout {
 inline SharedLayout shared_fir_layout(const avdsp_plan_desc *d, const ChainTables &t)
 {
     SharedLayout S;
+    /* ("mem_fir": the chains of a plan with memory words are in no group -- the host offers none) */
+    if (t.has_mem && !t.fir.empty() && d->fir_ngroups > 0) { S.err = "FIR groups beside memory words have no kernel"; return S; }
     if (t.fir.empty() || !(d->fir_ngroups > 0 && d->fir_group_start && d->fir_group_chains && d->instances <= 1 && (d->format == 4 || d->format == 6))) return S;
     std::vector<char> in_group(d->nchains, 0);
     for (int g = 0; g < d->fir_ngroups; g++) {

@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeCopyInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeMemFirInfo", "dspRuntimeCopyInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -138,6 +138,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "dspRuntimeMemInfo"):              # (tools/memtree_bench.py --parent loads a library from before the call)
             L.dspRuntimeMemInfo.restype = i32
             L.dspRuntimeMemInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "dspRuntimeMemFirInfo"):           # (tools/firtree_bench.py --parent loads a library from before the call)
+            L.dspRuntimeMemFirInfo.restype = i32
+            L.dspRuntimeMemFirInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         if hasattr(L, "dspRuntimeCopyInfo"):             # (tools/copy_bench.py --parent loads a library from before the call)
             L.dspRuntimeCopyInfo.restype = i32
             L.dspRuntimeCopyInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
@@ -289,6 +292,14 @@ class Runtime:
         branches -- chains that start with LOAD_MEM --, those of them whose word no chain of the core writes)."""
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeMemInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
+        return (a.value, b.value, c.value)
+
+    def mem_fir_info(self, core_index: int = 0):
+        """dspRuntimeMemFirInfo (host-only): in a core that "chain_mem" and "mem_fir" put on the chain kernels, (trunks with a DSP_FIR in
+        front of their STORE_MEM, branches with a DSP_FIR, those of these branches that are handed FIR chains -- a delay or a dressed
+        finish behind the FIR)."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeMemFirInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b), C.byref(c)))
         return (a.value, b.value, c.value)
 
     def copy_info(self, core_index: int = 0):

@@ -62,7 +62,8 @@ typedef struct avdsp_chain {
     int32_t  delay_max;              /* with a parameter: the line's size in samples (the delay is clamped to it); fixed form: microseconds */
     /* memory words ("chain_mem", dsp_runtime.c:750-766): the first of the two PROGRAM words a DSP_STORE_MEM leaves the accumulator in and
      * a DSP_LOAD_MEM takes it from.  0: none (word 0 is the header's).  A trunk -- LOAD | LOAD_GAIN, [BIQUADS], STORE_MEM -- has
-     * mem_store 1, n_out 0 and no sat / finish / delay; a branch has load_mode AVDSP_LOAD_MEM (in_io unused) and mem_store 0 */
+     * mem_store 1, n_out 0 and no sat / finish / delay; a branch has load_mode AVDSP_LOAD_MEM (in_io unused) and mem_store 0.  Under
+     * "mem_fir" either may have fir_taps: a trunk's FIR stands in front of its STORE_MEM, a branch's behind its sections */
     int32_t  mem_word;
     int32_t  mem_store;
 } avdsp_chain;
@@ -110,6 +111,8 @@ typedef struct avdsp_plan_desc {
     int32_t  ncopy;
     const int32_t *copy_src;         /* [ncopy]: IO read from the input window ... */
     const int32_t *copy_dst;         /* [ncopy]: ... IO written in the output window */
+    int32_t  mem_fir;                /* 1 ("mem_fir", with chain_mem, formats 4 and 6): a trunk or a branch may have fir_taps -- a trunk's FIR
+                                        hands its sums to mem_stage, a branch's FIR takes the word the stage forms; 0: such a chain is refused */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

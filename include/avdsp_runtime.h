@@ -382,6 +382,22 @@ int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *
  * the core writes.  A core without memory words and a core the interpreter runs report zeros. */
 int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches);
 
+/* "mem_fir" (dspRuntimeSetOption, 0 or 1, default 0): a DSP_FIR in a trunk or a branch of a "chain_mem" core, formats 4
+ * and 6; without "chain_mem" the option does nothing.  A FIR trunk is LOAD | LOAD_GAIN, [BIQUADS], FIR, STORE_MEM: the FIR's sum is the
+ * accumulator the STORE_MEM writes.  A FIR branch is LOAD_MEM, [BIQUADS], FIR and behind the FIR what an ordinary FIR chain may have:
+ * nothing or SAT0DB and the STOREs, or, under "fir_tail" (with "chain_finish" / "chain_delay"), a DSP_DELAY on either side of a SAT0DB
+ * or a dressed finish.  Without sections in front a branch's FIR takes the float the reference's FIR makes of the loaded accumulator.
+ * Ordinary FIR chains may stand beside the trees, a bypassed DSP_FIR leaves an ordinary trunk or branch, and a branch of a word no
+ * chain of the core writes may have a FIR like any other.  The chains of a core that holds a memory word are not offered to the
+ * shared-impulse path: dspRuntimeFirGroupInfo reports no group for such a core.  Refused with -8 and a text of its own, the core then
+ * on the interpreter: the FIR pure-delay variant, two FIRs in a chain, a DSP_DELAY in front of the FIR, format 2 (the int64 text),
+ * formats 3 and 5, a delay line that shares words with a FIR's history, and whatever "chain_mem" and "fir_tail" refuse that is not
+ * about a FIR beside memory words.  With 0 every core takes the path and the refusal text it had before the option existed.
+ * dspRuntimeMemFirInfo is host-only, nothing runs on the GPU: over the whole core, the trunks with a FIR (taps at the current rate),
+ * the branches with one, and of those branches the handed ones (a delay or a dressed finish behind the FIR).  A core without such
+ * chains and a core the interpreter runs report zeros. */
+int dspRuntimeMemFirInfo(int format, opcode_t *core, int *fir_trunks, int *fir_branches, int *of_them_handed);
+
 /* "chain_copy" (dspRuntimeSetOption, 0 or 1, default 0): DSP_LOAD_STORE lists (dsp_runtime.c:738-747, samples[out] =
  * samples[in] pair by pair: the raw 32-bit word, no accumulator, no conversion, no store mask) in a core of chains, formats 2 to 6 --
  * in front of a head TPDF_CALC, between chains, behind a trunk's STORE_MEM, behind the last chain, or alone in a core.  The host
