@@ -142,6 +142,11 @@ __device__ __forceinline__ double widen_f32(float v)   { return (double)v; }
 /* the same flush in software, for fir_mfma: there the MODE switch costs the MFMA loop 2.5 % (measured A/B,
  * reason unknown), while its few conversions -- one per output sample -- are off the critical path */
 __device__ __forceinline__ unsigned ftz_bits(unsigned u) { return (u & 0x7F800000u) ? u : (u & 0x80000000u); }
+/* the x word a section writes back into its state.  A format-6 sample loaded without a gain reaches section 0 as its own bits:
+ * (float)(double)sample is the sample to the compiler, no conversion is left to flush it, while the reference's cvtss2sd has read a
+ * subnormal sample as a signed zero before the section keeps it (dsp_biquadSTD.h:112).  The arithmetic never sees the difference (its
+ * widening flushes); the state area did.  Every other x word is a flushed float already */
+template <int FMT> __device__ __forceinline__ unsigned state_x_word(unsigned x) { if constexpr (FMT == 6) return ftz_bits(x); else return x; }
 
 /* dsp_ieee754.h:204-250: int -> float, magnitude TRUNCATED to 24 bits, times 2^-31.  INT_MIN leaves
  * the reference's 7-step normaliser one step short: mantissa 0, exponent 126, i.e. -0.5.       */
@@ -527,7 +532,7 @@ __device__ void cascade_in_reference_order(const BqArgsH<WIDE, HAND> &a, int cid
                 yn = __float_as_uint(narrow_f32(acc));
             }
             st[0] = (int)(unsigned)keep; st[1] = (int)(unsigned)(keep >> 32);
-            st[2] = (int)xin; st[3] = (int)x1; st[4] = (int)yn; st[5] = (int)y1;
+            st[2] = (int)state_x_word<FMT>(xin); st[3] = (int)x1; st[4] = (int)yn; st[5] = (int)y1;
             xin = yn;
         }
         if (c.fir_taps) ring_put(a.ring, cid, n, narrow_stage<FMT>(X), a.ready != nullptr);
@@ -901,7 +906,8 @@ __global__ __launch_bounds__(kBlock) void biquad_pipe(const BqArgsH<WIDE, HAND> 
         if constexpr (FMT == 2) bits = (unsigned long long)acc;
         else bits = (unsigned long long)__double_as_longlong(acc);
         st[0] = (int)(unsigned)bits; st[1] = (int)(unsigned)(bits >> 32);
-        st[2] = (int)x1; st[3] = (int)x2; st[4] = (int)y1; st[5] = (int)y2;
+        st[2] = (int)state_x_word<FMT>(x1); st[3] = (int)(B == 1 ? x2 : state_x_word<FMT>(x2));      /* (B == 1: x2 is the state's own x1, kept as it is) */
+        st[4] = (int)y1; st[5] = (int)y2;
     }
     if constexpr (FMT != 2) {
         if (replay && have_chain && s == 0) {

@@ -5,7 +5,10 @@ like tests/memtree_programs.py's -- cores of [TPDF_CALC] + items in program orde
     branch(key, ...)    LOAD_MEM(word of `key`), [BIQUADS], [FIR], then what firtail_programs.chain() describes behind its FIR
     plain(...)          an ordinary chain, firtail_programs.chain()
 
-A key without a trunk in its core is a word that core only reads.  Every trunk and every ordinary chain takes the next input from IO
+    copies([...])       one DSP_LOAD_STORE list (copy_programs.copies(); a core's `head`: lists in front of its TPDF_CALC)
+
+An item with a "mux" entry, [(input, gain), ...], starts with a LOAD_MUX of that table instead of its LOAD; one with a "store_to" entry
+stores to the IOs named (copy_programs.stores_to()).  A key without a trunk in its core is a word that core only reads.  Every trunk and every ordinary chain takes the next input from IO
 IN, every STORE the next output from IO 0; encoded for 44.1 and 48 kHz with an impulse per rate (another one, of another length, at
 44.1 kHz).  program() returns the words' indices by key."""
 import ctypes as C
@@ -47,20 +50,25 @@ def plain(**kw):
     return c
 
 
-def core(items, calc=None):
-    return dict(items=items, calc=calc)
+def core(items, calc=None, head=()):
+    """head: items (lists) in front of the core's TPDF_CALC"""
+    return dict(items=items, calc=calc, head=list(head))
 
 
-def program(fmt, cores, capacity=1 << 21, pairs=()):
+def program(fmt, cores, capacity=1 << 21, pairs=(), lines_last=False):
     """-> (program words, number of inputs, number of outputs, {key: word index}).  pairs: keys laid out as one dspMem_LocationMultiple(2)
-    each (the second word pair is unused): room to move an opcode's offset by one word"""
+    each (the second word pair is unused): room to move an opcode's offset by one word.  lines_last: the delay parameters in a PARAM
+    region of their own behind every other parameter, as tests/muxtail_programs.py lays them out (the header's maxOpcode takes a
+    [samples : us] word in front of another parameter's head for an opcode, and a line of more samples than there are opcodes makes a
+    program the runtimes refuse)"""
     L = enc.lib()
     _prototypes(L)
     L.dspFir_ImpulseData.argtypes = [C.POINTER(C.c_float), C.c_int]
     L.dsp_LOAD_MEM.argtypes = [C.c_int]
     L.dsp_STORE_MEM.argtypes = [C.c_int]
+    L.dspLoadStore_Data.argtypes = [C.c_int, C.c_int]
     nin, nout, words = [0], [0], {}
-    items = [it for c in cores for it in c["items"]]
+    items = [it for c in cores for it in c["items"] if it["kind"] != "copies"]
 
     def build(L):
         L.dsp_PARAM()
@@ -70,9 +78,13 @@ def program(fmt, cores, capacity=1 << 21, pairs=()):
                 banks[n] = L.dspBiquad_Sections(it["nsec"])
                 for k in range(it["nsec"]):
                     L.dsp_Filter2ndOrder(FPEAK, 120.0 + 37 * (n % 150) + 190.0 * (k % 30), 0.8 + 0.05 * (k % 5), 1.02 if k % 2 else 0.97)
-        for n, it in enumerate(items):
-            if it["slot"] and it["form"] == "param":
-                lines[n] = L.dspDelay_MicroSec_Max_Default(it["max_us"], it["us"])
+        def the_lines():
+            for n, it in enumerate(items):
+                if it["slot"] and it["form"] == "param":
+                    lines[n] = L.dspDelay_MicroSec_Max_Default(it["max_us"], it["us"])
+
+        if not lines_last:
+            the_lines()
         for n, it in enumerate(items):
             key = ("bank", it["bank"]) if it["bank"] is not None else ("chain", n)
             if (it["taps"] or it["odd"] in ("bypass", "pure_delay")) and key not in firs:
@@ -87,6 +99,22 @@ def program(fmt, cores, capacity=1 << 21, pairs=()):
         for it in items:
             if it["key"] is not None and it["key"] not in words:
                 words[it["key"]] = L.dspMem_LocationMultiple(2) if it["key"] in pairs else L.dspMem_Location()
+        tables = {}
+        if any(it.get("mux") for it in items):                 # (the tables in a PARAM region of their own, as muxtail_programs lays them out)
+            L.dsp_PARAM()
+            for n, it in enumerate(items):
+                if it.get("mux"):
+                    tables[n] = L.dspLoadMux_Inputs(len(it["mux"]))
+                    for io, g in it["mux"]:
+                        L.dspLoadMux_Data(IN + io, g)
+        if lines_last and any(it["slot"] and it["form"] == "param" for it in items):
+            L.dsp_PARAM()
+            the_lines()
+
+        def a_list(it):
+            L.dsp_LOAD_STORE()
+            for a, b in it["pairs"]:
+                L.dspLoadStore_Data(a, b)
 
         def delay(it, n):
             if it["form"] == "param":
@@ -101,12 +129,19 @@ def program(fmt, cores, capacity=1 << 21, pairs=()):
         n = 0
         for c in cores:
             L.dsp_CORE()
+            for it in c.get("head", ()):
+                a_list(it)
             if c["calc"] is not None:
                 L.dsp_TPDF_CALC(c["calc"])
             for it in c["items"]:
+                if it["kind"] == "copies":
+                    a_list(it)
+                    continue
                 odd = it["odd"]
                 if it["kind"] == "branch":
                     L.dsp_LOAD_MEM(words[it["key"]])
+                elif it.get("mux"):
+                    L.dsp_LOAD_MUX(tables[n])
                 else:
                     if it["load_gain"] is None:
                         L.dsp_LOAD(IN + nin[0])
@@ -140,8 +175,12 @@ def program(fmt, cores, capacity=1 << 21, pairs=()):
                     L.dsp_SAT0DB_TPDF_GAIN_Fixed(it["gain"])
                 if it["slot"] == "B":
                     delay(it, n)
-                for _ in range(it["stores"]):
-                    store()
+                if it.get("store_to") is not None:
+                    for io in it["store_to"]:
+                        L.dsp_STORE(io)
+                else:
+                    for _ in range(it["stores"]):
+                        store()
                 n += 1
 
     prog = enc.encode(build, 2 if fmt == 2 else 6, F44100, F48000, max_io=1024, capacity=capacity)

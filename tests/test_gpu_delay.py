@@ -305,3 +305,31 @@ def test_option_switched_between_blocks_of_one_stream(fmt):
             assert r.core_info()["chains"] == 0
         same(r.run_block(x[a:a + b], nout, IN), outs[k], f"format {fmt}, option switched, block {k}")
         same_state(r.sync_state(), states[k], f"format {fmt}, option switched, block {k}")
+
+
+@pytest.mark.parametrize("impl", [1, 0])
+def test_subnormal_samples_behind_a_plain_load_leave_signed_zeros_in_the_state(impl):
+    """Format 6, found by tests/dev/gpu_lowered_sweep.py (seeds 2, 10 and 12): a sample loaded WITHOUT a gain reaches section 0 of
+    biquad_pipe's WIDE and HAND forms (a dressed chain, a delayed chain) as its own bits -- the compiler folds (float)(double)sample --
+    and a subnormal one went into the section's x words as it was, where the reference's cvtss2sd has read it as a signed zero.  The
+    outputs never differed (the arithmetic widens and flushes); the state area did.  Blocks of 1, 2 and 3 frames end on subnormal
+    samples of both signs, so x1 and x2 of section 0 hold them; biquad_impl 0 (the reference-order cascade, which has the same
+    expression but kept the conversions) is the control."""
+    chains = [dp.chain(1, "A", "fixed", 1000, finish="gain", load_gain=None), dp.chain(2, None, finish="tpdf", load_gain=None),
+              dp.chain(16, "B", "param", 63, max_us=100, finish="sat", load_gain=None), dp.chain(1, "A", "fixed", 63, finish="none", load_gain=0.5)]
+    prog, nin, nout = dp.program(6, [dp.core(chains, calc=0)])
+    blocks = [1, 2, 3, 64, 1]
+    x = pb.lcg_input(sum(blocks), nin, True, seed=4).copy()
+    sub = np.array([0x00477B3C, 0x80000001, 0x007FFFFF, 0x80400000], dtype=np.uint32)
+    for end in np.cumsum(blocks):
+        x.view(np.uint32)[end - 1, :] = sub
+        if end >= 2:
+            x.view(np.uint32)[end - 2, :] = sub[::-1]
+    o = po.OracleProgram(6, prog, fs=48000, random=1, dither=24)
+    r = delayed_runtime(6, prog)
+    r.set_option("biquad_impl", impl)
+    assert r.core_info()["chains"] == 4 and r.delay_info()[0] == 3 and r.finish_info() == (2, 1)
+    for k, (a, b) in enumerate(cut(blocks)):
+        want = o.run_block(x[a:a + b], nout, IN)
+        same(r.run_block(x[a:a + b], nout, IN), want, f"biquad_impl {impl}, block {k}")
+        same_state(r.sync_state(), o.state, f"biquad_impl {impl}, block {k}")
