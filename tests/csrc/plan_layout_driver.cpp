@@ -13,6 +13,7 @@
  *   nchains x (in_io load_mode gain_bits nsec sec_base fir_taps fir_coef_word fir_state_word sat n_out out_io[4] mux_word mux_count mux_result_word)
  *   nfirgroups x (n, n chain ids), nmuxgroups x (n, n chain ids)
  *   nmirror x (word index, value): the mirror's words that are not 0 (the LOAD_MUX lists)
+ *   optionally: ndressed, ndressed x (chain id, finish): the chains with a dressed finish (AVDSP_FINISH_*)
  */
 #include <cstdlib>
 #include <cstring>
@@ -34,7 +35,7 @@ static void ints(const char *name, const std::vector<int> &v, bool last = false)
 
 static void group_json(const GroupLayout &g)
 {
-    std::cout << "{\"P\": " << g.P << ", \"nsec\": " << g.nsec << ", \"n\": " << g.n << ", \"all_fir\": " << g.all_fir << ", \"raw_out\": " << g.raw_out << ", ";
+    std::cout << "{\"P\": " << g.P << ", \"nsec\": " << g.nsec << ", \"n\": " << g.n << ", \"all_fir\": " << g.all_fir << ", \"raw_out\": " << g.raw_out << ", \"wide\": " << g.wide << ", ";
     ints("ids", g.ids);
     arr("rows", g.rows, [](const RowRec &r) { std::cout << '[' << r.cid << ", " << r.in_io << ", " << r.out_io << ", " << r.flags << ", " << r.gain_bits << ", " << r.pad[0] << ']'; });
     arr("lanes", g.lanes, [](const LaneRec &l) { std::cout << '[' << l.coef_word << ", " << l.state_word << ']'; });
@@ -71,6 +72,13 @@ static int layout(const char *path)
     std::vector<int> mirror((size_t)total_words, 0);
     for (int i = 0; i < nmirror; i++) { int w, v; in >> w >> v; mirror.at((size_t)w) = v; }
     if (!in) { std::cerr << "bad plan file\n"; return 2; }
+    int ndressed = 0;
+    if (in >> ndressed)
+        for (int i = 0; i < ndressed; i++) {
+            int c, f;
+            if (!(in >> c >> f)) { std::cerr << "bad plan file\n"; return 2; }
+            chains.at((size_t)c).finish = f;
+        }
 
     avdsp_plan_desc d{};
     d.format = format; d.nchains = nchains; d.chains = chains.data(); d.nsections = nsections;

@@ -13,6 +13,8 @@ import subprocess
 
 import pytest
 
+from tests import cascade_shapes as cs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOAD_PLAIN, LOAD_MUX, RAW = 0, 3, 2          # RAW: kLoadRaw / kStoreRaw, device-side only
 
@@ -81,6 +83,9 @@ class Desc:
             t += [len(g), *g]
         for w, v in self.mirror.items():
             t += [w, v]
+        dressed = [(i, c["finish"]) for i, c in enumerate(self.chains) if c.get("finish")]
+        if dressed:                                   # (chain(finish=...), with sat=1: a dressed finish)
+            t += [len(dressed)] + [v for p in dressed for v in p]
         return " ".join(map(str, t))
 
 
@@ -127,6 +132,69 @@ def test_sixteen_lane_rows_while_the_chip_has_simds_to_spare(driver, tmp_path, n
     for _ in range(n): d.chain(nsec=8)
     g, = layout(driver, tmp_path, d)["groups"]
     assert (g["P"], g["n"], len(g["rows"]), len(g["lanes"])) == (P, n, nrows, 16 * nrows)
+
+
+def uniform(n, nsec, fmt=6, **over):
+    d = Desc(fmt)
+    for _ in range(n): d.chain(nsec=nsec, **over)
+    return d
+
+
+def narrow_shapes():
+    seen = []
+    for shape in cs.NARROW + cs.NARROW_REPLAY + [s for s in cs.MIXED if s[2] < 16]:
+        if shape not in seen: seen.append(shape)
+    return seen
+
+
+@pytest.mark.parametrize("nsec, n, P", narrow_shapes())
+def test_the_narrow_groups_of_the_gpu_cascade_tests(driver, tmp_path, nsec, n, P):
+    """tests/test_gpu_cascade_forms.py means to launch biquad_pipe<FMT, 1 | 2 | 4 | 8>; the device does not say which cascade kernel
+    ran.  So the rule is held here to the shapes that file imports (tests/cascade_shapes.py): exactly these P, and no biquad_row
+    records.  A failure here says that the GPU tests no longer reach the narrow forms -- move their chain counts with the rule."""
+    assert P < 16 and n * 16 > 65536
+    g, = layout(driver, tmp_path, uniform(n, nsec))["groups"]
+    assert (g["nsec"], g["n"], g["P"], g["wide"], g["rows"], g["lanes"], g["pieces"]) == (nsec, n, P, 0, [], [], []), \
+        "the GPU tests of biquad_pipe's narrow forms no longer reach them"
+
+
+@pytest.mark.parametrize("fmt", [2, 4, 6])
+def test_the_mixed_core_of_the_gpu_cascade_tests(driver, tmp_path, fmt):
+    """Two narrow groups beside chains of three other section counts: the latter are 16-lane rows with records and make the merged
+    table, which holds no row of the narrow groups (their launches go out beside the merged one)."""
+    d = Desc(fmt)
+    for nsec, n, _ in cs.MIXED:
+        for _ in range(n): d.chain(nsec=nsec)
+    L = layout(driver, tmp_path, d)
+    assert [(g["nsec"], g["n"], g["P"]) for g in L["groups"]] == cs.MIXED
+    for g in L["groups"]:
+        assert len(g["rows"]) == (g["n"] if g["P"] == 16 else 0) and len(g["lanes"]) == 16 * len(g["rows"])
+    narrow_ids = {i for g in L["groups"] if g["P"] < 16 for i in g["ids"]}
+    merged_ids = [r[0] for r in L["merged"]["rows"] if r[0] >= 0]
+    assert sorted(merged_ids) == sorted(i for g in L["groups"] if g["P"] == 16 for i in g["ids"]) and not narrow_ids & set(merged_ids)
+
+
+def test_the_row_groups_of_the_gpu_cascade_tests(driver, tmp_path):
+    d = Desc(6)
+    for nsec, n, _ in cs.ROWS:
+        for _ in range(n): d.chain(nsec=nsec)
+    L = layout(driver, tmp_path, d)
+    assert [(g["nsec"], g["n"], g["P"]) for g in L["groups"]] == cs.ROWS
+    assert all(len(g["rows"]) == g["n"] for g in L["groups"]) and L["merged"]["n"] == 64       # 16 runs, each filled up to a wave
+
+
+def test_dressed_short_chains_keep_sixteen_lanes_however_many(driver, tmp_path):
+    """The WIDE form of biquad_pipe exists for 16-lane rows only: a dressed group past the threshold is not narrowed."""
+    g, = layout(driver, tmp_path, uniform(cs.NARROW_CHAINS, 3, sat=1, finish=1))["groups"]
+    assert (g["P"], g["wide"], g["n"], g["rows"]) == (16, 1, cs.NARROW_CHAINS, [])
+    g, = layout(driver, tmp_path, uniform(cs.NARROW_CHAINS, 3, sat=1))["groups"]                 # (the same chains without the finish)
+    assert (g["P"], g["wide"]) == (4, 0)
+
+
+def test_a_shard_of_the_full_chip_runs_sixteen_lane_rows(driver, tmp_path):
+    """set_shard(rank, 8) of 16 384 chains plans 2048 of them: the cfg5 headline tests run biquad_row, not the narrow forms."""
+    g, = layout(driver, tmp_path, uniform(16384 // 8, 8))["groups"]
+    assert (g["P"], g["n"], len(g["rows"])) == (16, 2048, 2048)
 
 
 # ---------------------------------------------------------------- pieces
