@@ -1989,6 +1989,25 @@ template <int R, bool BIG = false> __device__ __forceinline__ constexpr int win_
     /* row part ((-4 j) mod NR) * ROW, entry part -(ceil(4 j / NR)), shifted so that the smallest offset of a group is 0 */
     return ((NR - (4 * j) % NR) % NR) * TileGeom<R, BIG>::ROW - (4 * j + NR - 1) / NR + (64 / NR - 1);
 }
+/* the column ring's (RING below) window doubles: at `off` doubles from an LDS byte address */
+typedef __attribute__((address_space(3))) double lds_f64;
+__device__ __forceinline__ double win_load(unsigned base, int off) { return *(const lds_f64 *)(size_t)(base + 8u * (unsigned)off); }
+__device__ __forceinline__ void win_put(unsigned base, int off, double v) { *(lds_f64 *)(size_t)(base + 8u * (unsigned)off) = v; }
+
+/* RING (R = 4, lean, neither BIG nor SPLIT): the window image is a ring of columns instead of a chunk's picture.
+ * pos(u) = (u mod 64) ROW + u / 64 makes a chunk's image 16 + ckc / 16 columns of 64 samples, one sample per lane, and the next
+ * chunk's image is the same columns but for the ckc / 16 oldest ones: restaged whole, 16 of 22 columns were fetched, converted and
+ * written again as they stood (253 columns staged in the life of a 4096-tap wave that has 81).  So a column keeps its place:
+ *   column D = 0, 1, 2 ...: the 64 frames F0 - 3 + 64 (16 - D) + row -- D counts back from the wave's newest sample;
+ *   it lives in physical column RL - D mod RL of 1 .. RL, RL = ROW - 1 = 22, so that an OLDER column sits one BELOW, cyclically;
+ *   physical column 0 is a guard that always holds a copy of physical column RL: "one below" is an immediate -1 everywhere.
+ * Group G = s / 16 of the k-steps reads column 15 - i16 + G at j = 0 and the one below it at j = 1 .. 15 (win_off), i.e. columns
+ * G .. G + 16, and a chunk of groups [G0, G0 + JT) has columns G0 .. G0 + JT + 15 live: at most 22 consecutive ones, no two of which
+ * share a place.  The prologue stages columns 0 .. 21; the boundary in front of a later chunk stages what that chunk adds,
+ * G0 + 16 .. G0 + JT + 15, over the columns that died with the chunk before (always CKMAX / 16 = 6 of them from the top: where a
+ * chunk is shorter the others are live columns written again with what they hold).  Rows stay (u mod 64) ROW, ROW odd: writes
+ * (lane = row) and reads are as conflict-free as they were.  Operands and their order are the picture's: the bits are. */
+constexpr bool kFirWindowRing = true;
 
 /* SPLIT (R = 1, opt-in "fir_split"): a tile's k-steps cut in two, one wave each, the two partial sums added at the end -- NOT the
  * reference's summation order any more (results within north_star's 1e-6, not its bits), which is why it is an option: a launch
@@ -2083,7 +2102,11 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
 
     /* window element e = lane + 64 t of a chunk's image: row e % NR, entry e / NR */
     const int wrow = lane % NR, went = lane / NR;
-    float wreg[G::NW];
+    constexpr bool RING = kFirWindowRing && R == 4 && LEAN && !BIG && !SPLIT;
+    constexpr int RL = G::ROW - 1, NC = G::CKMAX / 16;     /* RING: the ring's columns, and those a chunk adds at most */
+    static_assert(!RING || (NR == 64 && RL >= 16 + NC), "the column ring: one sample per lane and column, a chunk's columns fit");
+    float wreg[RING ? NC : G::NW];
+    [[maybe_unused]] float wpro[RING ? RL : 1];            /* RING: the prologue's columns */
     /* The boundary between two chunks is instruction work that the matrix pipe waits for (f64 MFMA and VALU share the datapath:
      * tools/fir_timeline.py shows the SIMD's two waves taking turns, and every boundary instruction is a cycle the pipe idles),
      * so a window sample costs two VALU instructions to request (one masked byte offset, one load from a scalar base) and two to
@@ -2096,7 +2119,8 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
         const unsigned b0 = (unsigned)(a.ring.wpos + F0 - 3 + NR * (went + 1 - 4 * s0 / NR - JT) + wrow) << 2;
         /* ONE masked offset per lane and chunk; the lane's further samples lie 64 frames apart behind it -- immediates -- and run on
          * into the row's second copy where the ring wraps (Ring: every sample is stored twice, R floats apart) */
-        if constexpr (LEAN) {
+        if constexpr (RING) return;
+        else if constexpr (LEAN) {
             const char *p0 = ringbytes + (b0 & rmaskb);
 #pragma unroll
             for (int t = 0; t < G::NW; t++) wreg[t] = *reinterpret_cast<const float *>(p0 + 256 * t);
@@ -2113,17 +2137,78 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
          * they make the tile's sums non-finite, which is seen once, behind the last chunk, and such a tile is summed again the
          * reference's way (exact_tile). */
         bool odd = false;                                   /* (!LEAN) NaN, Inf or subnormal among the samples: the reference's bit-field operand */
+        if constexpr (!RING) {
 #pragma unroll
-        for (int t = 0; t < G::NW; t++)
-            if (t * 64 + 63 < NR * G::ROW || lane + t * 64 < NR * G::ROW) {
-                if constexpr (!LEAN) odd |= __builtin_amdgcn_classf(wreg[t], 0x297);
-                wp[t * (64 / NR)] = (double)wreg[t];
-            }
+            for (int t = 0; t < G::NW; t++)
+                if (t * 64 + 63 < NR * G::ROW || lane + t * 64 < NR * G::ROW) {
+                    if constexpr (!LEAN) odd |= __builtin_amdgcn_classf(wreg[t], 0x297);
+                    wp[t * (64 / NR)] = (double)wreg[t];
+                }
+        }
         if constexpr (!LEAN) {
             if (__builtin_expect(__ballot(odd) != 0, 0)) {      /* (no audio stream gets here) the same again with mulop() */
 #pragma unroll
                 for (int t = 0; t < G::NW; t++)
                     if (t * 64 + 63 < NR * G::ROW || lane + t * 64 < NR * G::ROW) wp[t * (64 / NR)] = mulop(wreg[t]);
+            }
+        }
+    };
+    /* RING: lane = row.  The image's LDS byte address (wave-uniform), the lane's row, and for the k-steps the lane's physical columns
+     * 1 and RL: its column pointer steps down by one per group, from column 1 on to column RL */
+    [[maybe_unused]] const unsigned ws_lds = RING ? __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char *)ws) : 0u;
+    [[maybe_unused]] const unsigned wrow_lds = RING ? ws_lds + (unsigned)(lane * G::ROW) * 8u : 0u;
+    [[maybe_unused]] const unsigned wcol1 = RING ? ws_lds + (unsigned)(((3 - (lane >> 4)) * G::ROW + 1) * 8) : 0u, wcolL = wcol1 + (unsigned)(RL - 1) * 8u;
+    [[maybe_unused]] auto ring_down = [&](unsigned p) { return p == wcol1 ? wcolL : p - 8u; };
+    /* the prologue: columns 0 .. RL-1, wpro[t] = column RL-1 - t (one masked offset at the oldest, ascending from there as win_fetch
+     * does) into physical column 1 + t, the newest -- physical column RL -- into the guard too */
+    [[maybe_unused]] auto ring_fetch_all = [&]() {
+        if constexpr (RING) {
+            const unsigned b0 = (unsigned)(a.ring.wpos + F0 - 3 + 64 * (16 - (RL - 1)) + lane) << 2;
+            const char *p0 = ringbytes + (b0 & rmaskb);
+#pragma unroll
+            for (int t = 0; t < RL; t++) wpro[t] = *reinterpret_cast<const float *>(p0 + 256 * t);
+        }
+    };
+    [[maybe_unused]] auto ring_store_all = [&]() {
+        if constexpr (RING) {
+#pragma unroll
+            for (int t = 0; t < RL; t++) win_put(wrow_lds, 1 + t, (double)wpro[t]);
+            win_put(wrow_lds, 0, (double)wpro[RL - 1]);
+        }
+    };
+    /* the columns the chunk [s0, s0 + ckc) adds, and NC - ckc / 16 live ones above them: wreg[t] = column Dhi - t, Dhi = s0 / 16 +
+     * ckc / 16 + 15 the chunk's oldest; requested a chunk ahead like the picture was, NC registers in flight instead of NW */
+    [[maybe_unused]] auto ring_fetch = [&](int s0, int ckc) {
+        if constexpr (RING) {
+            const int Dhi = (s0 >> 4) + (ckc >> 4) + 15;
+            const unsigned b0 = (unsigned)(a.ring.wpos + F0 - 3 + 64 * (16 - Dhi) + lane) << 2;
+            const char *p0 = ringbytes + (b0 & rmaskb);
+#pragma unroll
+            for (int t = 0; t < NC; t++) wreg[t] = *reinterpret_cast<const float *>(p0 + 256 * t);
+        }
+    };
+    /* ... and written: wreg[t] to physical column pc0 + t, on from RL to 1.  Where the columns land is wave-uniform: mostly they do not
+     * reach RL (one address per lane, then immediates); where they do, every place is a constant given which of them is column RL,
+     * and that one goes into the guard as well. */
+    [[maybe_unused]] auto ring_store = [&](int s0, int ckc) {
+        if constexpr (RING) {
+            const int Dhi = (s0 >> 4) + (ckc >> 4) + 15;
+            const int pc0 = RL - (int)((unsigned)Dhi % (unsigned)RL);
+            double wd[NC];
+#pragma unroll
+            for (int t = 0; t < NC; t++) { wd[t] = (double)wreg[t]; asm volatile("" : "+v"(wd[t])); }      /* (converted once, in front of the branches) */
+            if (pc0 + NC <= RL) {
+                const unsigned at = wrow_lds + (unsigned)pc0 * 8u;
+#pragma unroll
+                for (int t = 0; t < NC; t++) win_put(at, t, wd[t]);
+            } else {
+#pragma unroll
+                for (int tl = 0; tl < NC; tl++)
+                    if (RL - pc0 == tl) {                       /* wreg[tl] is physical column RL */
+#pragma unroll
+                        for (int t = 0; t < NC; t++) win_put(wrow_lds, t <= tl ? RL - tl + t : t - tl, wd[t]);
+                        win_put(wrow_lds, 0, wd[tl]);
+                    }
             }
         }
     };
@@ -2158,6 +2243,24 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
         const unsigned dst = hs_addr + (unsigned)which * (unsigned)(G::HLEN * 8);
         /* (LEAN, whole 1-KiB pieces: what the last one reads beyond the chunk's need lies inside the row's own zero tail -- kTapsTail
          * covers HLEN - HNEED < 128 doubles -- and lands behind the part of the image that is read) */
+        if constexpr (RING) {
+            /* a full chunk's four pieces (every chunk of a long FIR) in ONE statement: M0 saved and restored once per boundary, not
+             * once per piece -- beside a streaming partner every instruction of a boundary costs a slot of its own */
+            static_assert(G::HLEN / 128 == 4, "four pieces");
+            if (np > 192) {
+                unsigned keep;
+                asm volatile("s_mov_b32 %[k], m0\n\t"
+                             "s_mov_b32 m0, %[d0]\n\t" "s_nop 0\n\t" "global_load_lds_dwordx4 %[v], %[s0]\n\t"
+                             "s_mov_b32 m0, %[d1]\n\t" "s_nop 0\n\t" "global_load_lds_dwordx4 %[v], %[s1]\n\t"
+                             "s_mov_b32 m0, %[d2]\n\t" "s_nop 0\n\t" "global_load_lds_dwordx4 %[v], %[s2]\n\t"
+                             "s_mov_b32 m0, %[d3]\n\t" "s_nop 0\n\t" "global_load_lds_dwordx4 %[v], %[s3]\n\t"
+                             "s_mov_b32 m0, %[k]"
+                             : [k] "=&s"(keep)
+                             : [v] "v"(lane16), [s0] "s"(src), [s1] "s"(src + 1024), [s2] "s"(src + 2048), [s3] "s"(src + 3072),
+                               [d0] "s"(dst), [d1] "s"(dst + 1024u), [d2] "s"(dst + 2048u), [d3] "s"(dst + 3072u) : "memory");
+                return;
+            }
+        }
 #pragma unroll
         for (int t = 0; t < G::HLEN / 128; t++)
             if (64 * t < np) {
@@ -2173,13 +2276,17 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
     };
 
     double q[16], bq[4];
+    /* RING: the lane's column pointer of the group at hand (group 0: column 15 - i16, physical RL - 15 + i16); it runs on from chunk to
+     * chunk, and a guarded group (EDGE 2) that ends early leaves it: nothing is multiplied behind such an end */
+    [[maybe_unused]] unsigned wcg = RING ? wcol1 + (unsigned)(RL - 16 + i16) * 8u : 0u;
     /* the queue as a chunk's first step finds it, and the operands of its first two steps
      * lane bases: taps u = (k + i) + 16 (R-1) + 4 sc; window row (3 - k) + ..., entry a + JT - ... (win_off) */
-    auto chunk_begin = [&](const double *hp, const double *wp) {
+    auto chunk_begin = [&](const double *hp, [[maybe_unused]] const double *wp) {
 #pragma unroll
         for (int j = 0; j < G::QD; j++) q[(16 - G::QD + j) & 15] = hp[4 * j];
         q[0] = hp[16 * (R - 1)]; q[1] = hp[16 * (R - 1) + 4];
-        bq[0] = wp[win_off<R, BIG>(0)]; bq[1] = wp[win_off<R, BIG>(1)];
+        if constexpr (RING) { bq[0] = win_load(wcg, win_off<R, BIG>(0)); bq[1] = win_load(wcg, win_off<R, BIG>(1)); }
+        else { bq[0] = wp[win_off<R, BIG>(0)]; bq[1] = wp[win_off<R, BIG>(1)]; }
         if constexpr (LEAN) {
             /* These operands are needed by the first MFMAs anyway.  Waiting for them HERE makes the state at the head of the group loop
              * the same from both its edges -- nothing pending but the read-ahead -- so that the first k-step of a group gets the exact
@@ -2198,12 +2305,18 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
      * reads and all, and looks at the front at run time: a short FIR's only group is both).  The comparisons sit between the reads
      * and never around one, so the waits stay exact.  4096 taps at four row tiles: 48 of a wave's 4160 MFMAs. */
     const int slast = (T - 1 + NR) >> 2;            /* the last k-step with a tap in it (row tile 0) */
-    /* one k-step: the reads of step j + 2 (of the next group for j = 14, 15: the same code, offsets continue), R MFMAs */
-    auto kstep = [&](const double *hg, const double *wg, auto jc, auto ec, [[maybe_unused]] int sg) {
+    /* one k-step: the reads of step j + 2 (of the next group for j = 14, 15: the same code, offsets continue), R MFMAs.
+     * RING: the window reads go from the lane's column pointer wcg, which steps down a column -- and wraps -- in front of step 14,
+     * behind its last use for this group (step 13 reads for step 15): the read-ahead is base plus immediate like every other read,
+     * one guard column is enough, and the step is three 32-bit VALU instructions per 64 MFMAs */
+    auto kstep = [&](const double *hg, [[maybe_unused]] const double *wg, auto jc, auto ec, [[maybe_unused]] int sg) {
         constexpr int j = decltype(jc)::value, EDGE = decltype(ec)::value;
         if (EDGE == 2 && sg + j > slast) return false;      /* no row tile has a tap here or further on: the group ends */
         q[(j + 2) & 15] = hg[4 * (j + 2)];
-        bq[(j + 2) & 3] = j + 2 < 16 ? wg[win_off<R, BIG>((j + 2) & 15)] : (wg - 64 / NR)[win_off<R, BIG>((j + 2) & 15)];
+        if constexpr (RING) {
+            if constexpr (j == 14) wcg = ring_down(wcg);
+            bq[(j + 2) & 3] = win_load(wcg, win_off<R, BIG>((j + 2) & 15));
+        } else bq[(j + 2) & 3] = j + 2 < 16 ? wg[win_off<R, BIG>((j + 2) & 15)] : (wg - 64 / NR)[win_off<R, BIG>((j + 2) & 15)];
         __builtin_amdgcn_sched_barrier(0);          /* the reads stay two steps ahead of their MFMAs */
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -2233,28 +2346,29 @@ __global__ __launch_bounds__(kBlock, 2) void fir_tile(const FirTileArgsH<HAND> a
      * window stays behind the wait. */
     taps_dma(0, Sb, min(ck, S - Sb));
     if (a.ready && c.nsec) chain_ready_wait(a.ready, cid, a.seq, a.timeouts, a.ready_acquire != 0);       /* the chain's cascade of this launch has left its block in the ring */
-    win_fetch(Sb, min(ck, S - Sb));
+    if constexpr (RING) ring_fetch_all(); else win_fetch(Sb, min(ck, S - Sb));
     [[maybe_unused]] int stamp_i = 1;
     int cur = 0;
     for (int s0 = Sb; s0 < S; s0 += ck, cur ^= 1) {
         const int ckc = min(ck, S - s0);
-        const int JT = (4 * (ckc - 1) + NR - 1) / NR;
+        [[maybe_unused]] const int JT = (4 * (ckc - 1) + NR - 1) / NR;
         __builtin_amdgcn_wave_barrier();
         FIR_STAMP_CHUNK();
-        win_store(ws);                                      /* (waits for the window samples requested a chunk ago) */
+        if constexpr (RING) { if (s0 == 0) ring_store_all(); else ring_store(s0, ckc); }
+        else win_store(ws);                                 /* (waits for the window samples requested a chunk ago) */
         if (s0 == Sb + ck) FIR_STAMP(24);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    /* ... and for this chunk's taps image, in flight since then */
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (s0 == Sb + ck) FIR_STAMP(25);
         if (s0 + ckc < S) {
-            win_fetch(s0 + ckc, min(ck, S - s0 - ckc));
+            if constexpr (RING) ring_fetch(s0 + ckc, min(ck, S - s0 - ckc)); else win_fetch(s0 + ckc, min(ck, S - s0 - ckc));
             if (s0 == Sb + ck) FIR_STAMP(26);
             taps_dma(cur ^ 1, s0 + ckc, min(ck, S - s0 - ckc));
         }
         if (s0 == Sb + ck) FIR_STAMP(27);
         const double *hp = hs + cur * G::HLEN + k + i16;                       /* oldest operand of step sc at hp[4 sc] */
-        const double *wp = ws + (3 - k) * G::ROW + i16 + JT - (64 / NR - 1);   /* group g: wp - g * (64 / NR) + win_off(j) */
+        [[maybe_unused]] const double *wp = ws + (3 - k) * G::ROW + i16 + JT - (64 / NR - 1);   /* group g: wp - g * (64 / NR) + win_off(j) */
         chunk_begin(hp, wp);
         FIR_STAMP_CHUNK();
         /* groups [0, gfull) of the chunk lie before the last k-step that every row tile has (slast - 4 (R-1)): the code they always
