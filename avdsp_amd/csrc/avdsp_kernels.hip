@@ -1754,10 +1754,18 @@ constexpr int kWRegs = (kFirPad + 16 * kMaxGpc + 16 * (kNG + 2) + kBlock - 1) / 
 
 /* the word a FIR-only chain appends for one sample word: (float)X of the load stage -- or the word as it is where a stage in front of
  * the chain has formed (float)X already (kLoadRaw: the mux stage's column) */
+/* Format 6, a plain LOAD: (float)(double)sample is the sample itself to the compiler, no conversion is left -- but the reference's
+ * cvtss2sd has quieted a signalling NaN (mantissa bit 22 set) before its FIR keeps the float, and dspMulFloatDouble reads the mantissa
+ * of an exponent-255 word: 0x7F812345 is 2^128 x 1.009 as it stands and 2^128 x 1.509 quieted.  Found by
+ * tests/test_gpu_fir_ring_routes.py::test_memory_word_trees_odd_samples (sums of another sign behind such a sample).  A word that did go
+ * through the conversions is quiet already. */
 template <int FMT>
 __device__ __forceinline__ unsigned fir_input_word(unsigned raw, int load_mode, unsigned gain_bits)
 {
-    return ftz_bits(load_mode == kLoadRaw ? raw : narrow_stage<FMT>(load_stage<FMT>(raw, load_mode, gain_bits)));
+    if (load_mode == kLoadRaw) return ftz_bits(raw);
+    unsigned w = ftz_bits(narrow_stage<FMT>(load_stage<FMT>(raw, load_mode, gain_bits)));
+    if constexpr (FMT == 6) { if ((w & 0x7F800000u) == 0x7F800000u && (w & 0x007FFFFFu)) w |= 0x00400000u; }
+    return w;
 }
 
 /* FIR-only chains: the FIR's input is (float)X of the load stage; append it to the ring first */
@@ -5680,6 +5688,7 @@ static LaunchFacts launch_facts(const avdsp_hip_prog *prog, const Plan &pl, cons
     f.has_taps64 = pl.d_taps64 != nullptr; f.has_ready = pl.d_ready != nullptr;
     f.inst_n = prog->inst_n; f.chain_inst = prog->chain_inst; f.has_timeouts = prog->d_ready_timeouts != nullptr;
     f.timer_samples = (prog->profile >> AVDSP_KERNEL_FIR & 1u) && prog->profile_seen[AVDSP_KERNEL_FIR & 7] % (unsigned)prog->profile_stride == 0;
+    f.n_fir_only = pl.n_fir_only;
     return f;
 }
 
@@ -5720,6 +5729,15 @@ int enqueue_cascades_ahead(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int biqua
     return 0;
 }
 
+/* LaunchRoute::fir_follows_fir: the FIRs' stream of this block behind the FIR of the block before (the slot before this one's) */
+static int wait_fir_one_back(avdsp_hip_prog *prog, hipStream_t fs, int slot)
+{
+    auto &ov = prog->ov;
+    const int prev = (slot + avdsp_hip_prog::kAhead - 1) % avdsp_hip_prog::kAhead;
+    if (ov.ev_fir_set[prev]) HIP_TRY(hipStreamWaitEvent(fs, ov.ev_fir_now[prev], 0));
+    return 0;
+}
+
 /* the copy behind a staged FIR launch: ahead_copy_run where the columns are one run and everything is 16-byte aligned, else ahead_copy_words */
 static int launch_ahead_copy(Plan &pl, const unsigned *stage, BlockIO io, hipStream_t stream)
 {
@@ -5740,11 +5758,12 @@ static int launch_ahead_copy(Plan &pl, const unsigned *stage, BlockIO io, hipStr
  * written in the caller's stream order, one output block may serve every call, and work the caller queued between two calls has read it
  * before the later call's words arrive.  Every ordering is an event between streams; no wave waits for anything. */
 template <int FMT>
-int enqueue_staged(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hipStream_t stream, int slot)
+int enqueue_staged(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hipStream_t stream, const LaunchRoute &r, int slot)
 {
     auto &ov = prog->ov;
     hipStream_t fs = ov.s_fir[ov.blk & 1];
     HIP_TRY(hipStreamWaitEvent(fs, ov.ev_bq[slot], 0));
+    if (r.fir_follows_fir && wait_fir_one_back(prog, fs, slot)) return -1;
     /* the slot's staging block is free once the copy of the call three back has read it.  Its event is asked first: a wait packet costs
      * the queue ~9 us even when its signal is long down.  Where the packet is needed it falls under the other stream's FIR as long as
      * the host runs a call ahead. */
@@ -5774,6 +5793,7 @@ int enqueue_own_fir(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, hi
 {
     auto &ov = prog->ov;
     if (r.fir_waits_event) HIP_TRY(hipStreamWaitEvent(fs, ov.ev_bq[slot], 0));
+    if (r.fir_follows_fir && wait_fir_one_back(prog, fs, slot)) return -1;
     if (launch_fir<FMT>(prog, pl, {.ids = pl.d_fir_ids, .n = pl.n_fir, .io = io, .fir_impl = fir_impl, .stream = fs,
                                    .wait_ready = !r.fir_waits_event, .ready_acquire = r.ready_acquire})) return -1;
     HIP_TRY(hipEventRecord(ov.ev_fir[slot], fs));
@@ -5908,7 +5928,7 @@ int launch_all(avdsp_hip_prog *prog, Plan &pl, BlockIO io, int fir_impl, int biq
         prog->ready_mode_now = r.ready_mode;
         const int slot = (int)(ov.blk % avdsp_hip_prog::kAhead);
         if (enqueue_cascades_ahead<FMT>(prog, pl, io, biquad_impl, r, slot)) return -1;
-        if (r.path == kStaged ? enqueue_staged<FMT>(prog, pl, io, fir_impl, stream, slot)
+        if (r.path == kStaged ? enqueue_staged<FMT>(prog, pl, io, fir_impl, stream, r, slot)
           : r.path == kOwnFir ? enqueue_own_fir<FMT>(prog, pl, io, fir_impl, stream, on, r, slot)       /* (the stream that was probed is the FIRs') */
                               : enqueue_direct<FMT>(prog, pl, io, fir_impl, stream, r, slot)) return -1;
         ov.ev_fir_set[slot] = true;

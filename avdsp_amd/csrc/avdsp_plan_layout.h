@@ -685,6 +685,7 @@ struct LaunchFacts {
     bool has_taps64, has_ready;                                                 /* ... its per-chain f64 taps, its ready words */
     int inst_n, chain_inst; bool has_timeouts;                                  /* the program; its time-out words */
     bool timer_samples;                                                         /* this launch's FIR kernel timer is sampled */
+    int n_fir_only;                                                             /* the plan's FIR chains without a cascade in front: they append their input inside the FIR launch */
 };
 enum LaunchPath { kBackToBack = 0, kDirect = 1, kOwnFir = 2, kStaged = 3 };
 enum ProbeOn { kProbeCaller = 0, kProbeFirTurn = 1, kProbeFirFirst = 2 };       /* the caller's stream, s_fir[blk & 1], s_fir[0] */
@@ -695,6 +696,7 @@ struct LaunchRoute {
     int fir_launch_mode;                                  /* (the direct path's; 0 elsewhere) */
     bool rides;
     int side_by_side;                                     /* what the program remembers of the probes: a staged launch's is its ahead_apart */
+    bool fir_follows_fir;                                 /* this block's FIR waits for the previous block's: see launch_route */
 };
 
 /* "ready_words" by the plan (-1).  Mode 2 takes the wait packet off the FIRs' stream (a FIR follows the previous one like any kernel of a
@@ -764,6 +766,13 @@ inline LaunchRoute launch_route(const LaunchFacts &f, const LaunchGate &g, int a
         /* (a launch whose kernel timer is sampled carries the timer's events instead; its event is then recorded behind it) */
         r.rides = r.fir_launch_mode == 1 && !f.timer_samples;
     }
+    /* The staged path and "overlap" 2 put the FIRs of consecutive blocks on two streams in turn: FIR k + 1 needs nothing of FIR k -- as
+     * long as every FIR chain has a cascade in front, whose stream appends the blocks in order.  A FIR alone appends its block's input
+     * inside its own launch (fir_append_input), and FIR k + 1 reads that as history: with such a chain in the plan the FIR's stream
+     * waits for the previous block's FIR (found by tests/test_gpu_fir_ring_routes.py: launches of three workgroups do start side by
+     * side, and block k + 1 was summed over a ring block k had not reached yet).  One stream -- the direct path, "cu_split" -- orders
+     * them by itself. */
+    r.fir_follows_fir = f.n_fir_only > 0 && (r.path == kStaged || (r.path == kOwnFir && f.overlap >= 2));
     return r;
 }
 

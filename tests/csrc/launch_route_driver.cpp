@@ -23,6 +23,7 @@ int main(int argc, char **argv)
         {"max_taps", &f.max_taps, nullptr}, {"n_ahead_cols", &f.n_ahead_cols, nullptr}, {"instances", &f.instances, nullptr}, {"n_sh_groups", &f.n_sh_groups, nullptr},
         {"has_taps64", nullptr, &f.has_taps64}, {"has_ready", nullptr, &f.has_ready}, {"inst_n", &f.inst_n, nullptr}, {"chain_inst", &f.chain_inst, nullptr},
         {"has_timeouts", nullptr, &f.has_timeouts}, {"timer_samples", nullptr, &f.timer_samples}, {"ahead_apart", &ahead_apart, nullptr}, {"side_by_side", &side_by_side, nullptr},
+        {"n_fir_only", &f.n_fir_only, nullptr},
     };
     for (int a = 1; a < argc; a++) {
         const char *eq = strchr(argv[a], '=');
@@ -35,8 +36,8 @@ int main(int argc, char **argv)
     const LaunchGate g = launch_gate(f);
     const LaunchRoute r = launch_route(f, g, ahead_apart, side_by_side);
     printf("{\"under\": %d, \"own_fir\": %d, \"ahead_candidate\": %d, \"probe_on\": %d, \"path\": %d, \"ready_mode\": %d, \"cascade_event\": %d, "
-           "\"write_through\": %d, \"fir_waits_event\": %d, \"ready_acquire\": %d, \"fir_launch_mode\": %d, \"rides\": %d, \"side_by_side\": %d}\n",
+           "\"write_through\": %d, \"fir_waits_event\": %d, \"ready_acquire\": %d, \"fir_launch_mode\": %d, \"rides\": %d, \"side_by_side\": %d, \"fir_follows_fir\": %d}\n",
            g.under, g.own_fir, g.ahead_candidate, g.probe_on, r.path, r.ready_mode, r.cascade_event, r.write_through, r.fir_waits_event,
-           r.ready_acquire, r.fir_launch_mode, r.rides, r.side_by_side);
+           r.ready_acquire, r.fir_launch_mode, r.rides, r.side_by_side, r.fir_follows_fir);
     return 0;
 }

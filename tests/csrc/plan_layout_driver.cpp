@@ -4,6 +4,7 @@
  *   plan_layout_driver layout FILE     the stages of plan building in avdsp_hip_prog_add_plan's order over the plan description in
  *                                      FILE, the layout as one JSON object on stdout -- or {"error": text} and nothing else
  *   plan_layout_driver choice impl n frames fir_rows fir_split fir_lean cascades plan_taps
+ *   plan_layout_driver hand impl n frames fir_rows cascades plan_taps        fir_hand_choice: the launch of a plan's handed FIR chains
  *   plan_layout_driver shared format ntiles frames fir_rows
  *   plan_layout_driver ring max_taps
  *
@@ -135,9 +136,13 @@ int main(int argc, char **argv)
     FirChoice c;
     if (argc == 10 && !strcmp(argv[1], "choice"))
         c = fir_choice((int)num(2), num(3), (int)num(4), FirOptions{(int)num(5), (int)num(6), (int)num(7)}, num(8) != 0, num(9));
+    else if (argc == 8 && !strcmp(argv[1], "hand"))
+        c = fir_hand_choice((int)num(2), num(3), (int)num(4), (int)num(5), num(6) != 0, num(7));
     else if (argc == 6 && !strcmp(argv[1], "shared"))
         c = fir_shared_choice((int)num(2), (int)num(3), (int)num(4), (int)num(5));
     else { std::cerr << "usage: see the head of plan_layout_driver.cpp\n"; return 2; }
-    std::cout << c.family << ' ' << c.R << ' ' << c.BIG << ' ' << c.SPLIT << ' ' << c.LEAN << '\n';
+    std::cout << c.family << ' ' << c.R << ' ' << c.BIG << ' ' << c.SPLIT << ' ' << c.LEAN;
+    if (c.HAND) std::cout << " HAND";
+    std::cout << '\n';
     return 0;
 }

@@ -13,7 +13,7 @@ ON_CALLER, ON_FIR_TURN, ON_FIR_FIRST = 0, 1, 2           # the stream the side-b
 # instances, a call that is not in place into a window of 4096 words, a kernel timer that is not sampled
 DEFAULTS = dict(overlap=1, cu_split=0, fir_ahead=-1, ready_words=-1, fir_launch=-1, fir_impl=1, biquad_impl=1, nframes=1024, out_stride=4096,
                 in_place=0, overlap_ok=1, n_fir=4096, max_taps=4096, n_ahead_cols=4096, instances=0, n_sh_groups=0, has_taps64=1, has_ready=1,
-                inst_n=1, chain_inst=0, has_timeouts=1, timer_samples=0, ahead_apart=0, side_by_side=0)
+                inst_n=1, chain_inst=0, has_timeouts=1, timer_samples=0, n_fir_only=0, ahead_apart=0, side_by_side=0)
 
 
 def build_driver(dirname):

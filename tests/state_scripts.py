@@ -29,7 +29,10 @@ A script is a list of steps; play() applies every step to a po.OracleProgram and
 The modelled ring position: frames of chain-kernel blocks since the plans were last built, modulo the ring length R, which is
 ring_length(longest FIR) as avdsp_plan_layout.h computes it.  The plans are built anew by the first block and after "params",
 "generic", "shards" and "reset".  The device's own position cannot be read; the model only says whether a script reaches the
-positions it is written for and never decides what the device is compared with."""
+positions it is written for and never decides what the device is compared with.
+
+Program DEEP and its cases (scripts A, B, D, E behind RING_PREFIX, and script N) put fir_tile's window ring on both
+sides of every hand-over; tests/fir_ring_cases.py lists their launches and tests/test_fir_ring_reach.py asks fir_choice about each."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -118,6 +121,9 @@ LONG_CHAINS = [(1, 1030), (0, 641)]
 BANK_CHAINS = [(1, 97, "bank")] * 17 + [(0, 97)] * 3
 LANE_CHAINS = [(2, 120), (0, 33), (16, 0), (17, 7), (0, 300)]
 FIXED_CHAINS = [(65, 0), (16, 0), (3, 0), (1, 0)]
+# fir_tile's window ring (four row tiles, lean boundary): FIRs whose column pointer wraps once (1345 taps or more) and twice (2753),
+# the longest one a tap past 4096; the 300-tap chain is what script B's second poke looks for
+DEEP_CHAINS = [(2, 4096), (0, 1345), (1, 2753), (0, 300), (3, 4097)]
 
 PROGRAMS = {                     # name -> (formats, maker(fmt))
     "TIGHT": ((4, 6), lambda fmt: build("TIGHT", fmt, TIGHT_CHAINS)),
@@ -127,6 +133,7 @@ PROGRAMS = {                     # name -> (formats, maker(fmt))
     "LANE": ((3, 5), lambda fmt: build("LANE", fmt, LANE_CHAINS)),
     "FIXED": ((2,), lambda fmt: build("FIXED", fmt, FIXED_CHAINS)),
     "RATES": ((6,), lambda fmt: build("RATES", fmt, MIXED_CHAINS, pb.F44100, pb.F48000, fs=44100)),
+    "DEEP": ((4, 6), lambda fmt: build("DEEP", fmt, DEEP_CHAINS)),
 }
 _programs = {}
 
@@ -419,14 +426,14 @@ def blocks_to(steps, frames, chunk=4096):
         have += n
 
 
-def script_A(prog):
+def script_A(prog, chunk=4096):
     """checkpoints at every phase of the ring"""
     R, T = prog.R, prog.max_taps
     s = [("save", "f0")]
     for total in (1, 1025, R - 1, R, R + 1, R + T - 1):
-        blocks_to(s, total)
+        blocks_to(s, total, chunk)
         s += [("total", total), ("at", total % R), ("save", f"f{total}")]
-    blocks_to(s, 2 * R - 1200)
+    blocks_to(s, 2 * R - 1200, chunk)
     s += [("at", R - 1200), ("block", 2500), ("at", 1300), ("save", "big"), ("block", 100), ("sync",)]
     s += [("fork", n) for n in ["f0"] + [f"f{t}" for t in (1, 1025, R - 1, R, R + 1, R + T - 1)] + ["big"]]
     return s
@@ -440,21 +447,21 @@ def poke_of(prog, chain):
     return {chain: list(zip((0, 1, T // 2, T - 2, T - 1), POKE_WORDS))}
 
 
-def script_B(prog, pokes):
+def script_B(prog, pokes, chunk=4096):
     """upload at a used position; `pokes`: format 6"""
     R = prog.R
     big = max(range(prog.C), key=lambda c: prog.chains[c][1])
     other = [c for c in range(prog.C) if prog.chains[c][1] == 300][0]
     s = [("block", 1), ("block", 1024), ("total", 1025), ("save", "c")]
-    blocks_to(s, 4000)
-    s += [("at", 4000), ("load", "c"), ("block", 100), ("block", 1024), ("sync",)]
+    blocks_to(s, 4000, chunk)
+    s += [("at", 4000 % R), ("load", "c"), ("block", 100), ("block", 1024), ("sync",)]
     if pokes:
         s += [("poke", poke_of(prog, big))]
     s += [("block", 300), ("sync",), ("opt", "fir_impl", 4), ("block", 300)]
     if pokes:
         s += [("poke", poke_of(prog, other))]          # the operand ring exists: the operand of a poked word is the product's
     s += [("block", 300), ("sync",), ("opt", "fir_impl", 1)]
-    blocks_to(s, 2 * R + 200)
+    blocks_to(s, 2 * R + 200, chunk)
     s += [("at", 200), ("load", "c"), ("block", 100), ("block", 1024), ("sync",)]
     return s
 
@@ -513,12 +520,62 @@ def script_D_rates(prog):
     return s
 
 
-def script_E(prog):
+def script_E(prog, chunk=4096):
     """one-frame calls on FIR chains"""
     R = prog.R
     s = []
-    blocks_to(s, R - 2)
+    blocks_to(s, R - 2, chunk)
     s += [("at", R - 2), ("frames", 5), ("at", 3), ("block", 97), ("at", 100), ("frames", 5), ("block", 300), ("sync",)]
+    return s
+
+
+# ---- fir_tile's window ring in the scripts: program DEEP behind RING_PREFIX, whole blocks of 1024 frames -------------------------
+RING_PREFIX = [("opt", "fir_rows", 4), ("opt", "fir_lean", 1)]
+
+
+def script_A_ring(prog):
+    """script A, every 1024-frame block of it a ring launch: checkpoints and forks at ring positions 0, 1, 1025, R - 1, R, R + 1, R + T - 1"""
+    return RING_PREFIX + script_A(prog, 1024)
+
+
+def script_B_ring(prog, pokes):
+    """script B: uploads at used positions between ring launches, pokes at both ends of the 4097-tap line"""
+    return RING_PREFIX + script_B(prog, pokes, 1024)
+
+
+def script_D_ring(prog):
+    return RING_PREFIX + script_D(prog)
+
+
+def script_E_ring(prog):
+    """script E, and a ring block behind the last one-frame calls: they lie between ring launches"""
+    return RING_PREFIX + script_E(prog, 1024) + [("block", 1024), ("sync",)]
+
+
+# (fir_impl, fir_rows, fir_lean) per block: the ring on both sides of every other kernel -- fir_mfma, fir_stream, fir_flow, fir_tile with
+# two row tiles, fir_plain
+N_TABLE = [(1, 4, 1), (2, 0, -1), (1, 4, 1), (3, 4, 0), (1, 4, 1), (4, 0, 0), (1, 4, 1), (1, 2, 1), (1, 4, 1), (0, 0, -1), (1, 4, 1)]
+N_BLOCKS = [1024, 700, 513, 1024, 600]
+
+
+def script_N(prog, wrapped):
+    """the ring kernel taking turns with every other FIR kernel; `wrapped`: the first other kernel's block crosses the float ring's end"""
+    R = prog.R
+    s = list(RING_PREFIX)
+    if wrapped:
+        blocks_to(s, R - 150 - N_BLOCKS[0], 1024)
+    for j, (impl, rows, lean) in enumerate(N_TABLE):
+        s += [("opt", "fir_impl", impl), ("opt", "biquad_impl", (j + 1) % 2), ("opt", "fir_rows", rows), ("opt", "fir_lean", lean)]
+        if j == 1:
+            s += [("at", R - 150 if wrapped else 1024)]
+        if j == 4:
+            s += [("load", "c")]                        # between a fir_stream block and a ring block
+        s += [("block", N_BLOCKS[j % 5])]
+        if j == 0:
+            s += [("save", "c")]
+        if j % 2:
+            s += [("sync",)]
+    s += [("sync",)]
     return s
 
 
@@ -598,6 +655,13 @@ def _cases():
     add("F", "BANK", (6,), script_F)
     add("G", "LANE", (3, 5), script_G)
     add("H", "FIXED", (2,), script_H)
+    add("A", "DEEP", (4, 6), script_A_ring)
+    add("B", "DEEP", (4,), script_B_ring, False)
+    add("B", "DEEP", (6,), script_B_ring, True)
+    add("D", "DEEP", (4, 6), script_D_ring)
+    add("E", "DEEP", (4, 6), script_E_ring)
+    add("N", "DEEP", (4, 6), script_N, False, "inside")
+    add("N", "DEEP", (4, 6), script_N, True, "wrapped")
     return out
 
 
@@ -611,6 +675,8 @@ def case(case_id):
         name, fmt, make, args = CASES[case_id]
         prog = program(name, fmt)
         script = make(prog, *args)
-        seed = 1000 + sorted(CASES).index(case_id)
+        # (the DEEP cases came later: they count on from the others, whose inputs stay what they were)
+        order = sorted(c for c in CASES if "-DEEP-" not in c) + sorted(c for c in CASES if "-DEEP-" in c)
+        seed = 1000 + order.index(case_id)
         _inputs[case_id] = (prog, script, pb.lcg_input(script_frames(script), prog.C, fmt in (5, 6), seed=seed))
     return _inputs[case_id]

@@ -18,6 +18,12 @@ state the whole state area.
     E  one-frame calls across the ring's end
     F  the shared-impulse path and fir_tile taking turns on the same rings
     G  format 3 / 5 lane plans, H the int64 cascades: the same hand-overs where there is no ring
+    N  fir_tile's window ring (four row tiles, lean boundary) taking turns with fir_mfma, fir_stream, fir_flow, two row tiles and
+       fir_plain, a save behind the first block, a load between a fir_stream block and a ring block
+
+Program DEEP (FIRs of 1345, 2753, 4096 and 4097 taps: the ring kernel's column pointer wraps once and twice) runs A, B, D and E with
+"fir_rows" 4 and "fir_lean" 1 forced and 1024-frame blocks, so that the ring kernel stands on both sides of every hand-over
+(tests/test_fir_ring_reach.py asks fir_choice whether it does).
 
 "fir_split" (a tolerance, not bits), "overlap" and "ready_words" (blocks in flight: tests/test_gpu_sweeps.py) are not switched here."""
 import pytest
@@ -84,4 +90,9 @@ def test_lane_plans(case_id):
 
 @pytest.mark.parametrize("case_id", cases("H"))
 def test_fixed_point(case_id):
+    run(case_id)
+
+
+@pytest.mark.parametrize("case_id", cases("N"))
+def test_window_ring_between_the_other_kernels(case_id):
     run(case_id)

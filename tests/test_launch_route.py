@@ -107,6 +107,20 @@ def test_cu_split(route):
     assert pick(route(cu_split=-16, ahead_apart=1), "own_fir", "ahead_candidate", "path") == (0, 1, STAGED)      # (only the cascades' stream is masked)
 
 
+# ---------------------------------------------------------------- FIR chains without a cascade
+def test_fir_only_chains_order_the_firs_of_two_streams(route):
+    """a FIR alone appends its input inside its launch, and the next block's FIR reads it as history: where the FIRs of consecutive
+    blocks take two streams in turn -- staged, "overlap" 2 -- each waits for the one before; one stream orders them by itself"""
+    assert pick(route(n_fir_only=2, ahead_apart=1), "path", "fir_follows_fir") == (STAGED, 1)
+    assert pick(route(n_fir_only=2, fir_ahead=1, n_fir=9, ahead_apart=0), "path", "fir_follows_fir") == (STAGED, 1)
+    assert pick(route(n_fir_only=1, overlap=2, ready_words=2, side_by_side=1), "path", "fir_follows_fir") == (OWN_FIR, 1)
+    assert pick(route(n_fir_only=1, cu_split=16, side_by_side=1), "path", "fir_follows_fir") == (OWN_FIR, 0)
+    assert pick(route(n_fir_only=1, ahead_apart=0, side_by_side=1), "path", "fir_follows_fir") == (DIRECT, 0)
+    assert pick(route(n_fir_only=1, overlap=0), "path", "fir_follows_fir") == (BACK_TO_BACK, 0)
+    for facts in (dict(ahead_apart=1), dict(overlap=2, side_by_side=1), dict(fir_ahead=1)):
+        assert route(**facts)["fir_follows_fir"] == 0           # every chain behind a cascade: FIR k + 1 needs nothing of FIR k
+
+
 # ---------------------------------------------------------------- "ready_words" by implementation
 def test_ready_words_by_implementation(route):
     assert pick(route(ready_words=1, side_by_side=1), "ready_mode", "write_through", "ready_acquire") == (1, 1, 1)

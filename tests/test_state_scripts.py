@@ -62,10 +62,10 @@ def test_scripts_mean_what_they_say(case_id):
 def test_scripts_reach_the_ring_positions_they_name(case_id):
     name, fmt, make, args = ss.CASES[case_id]
     prog, script, x = ss.case(case_id)
-    R = {"TIGHT": 4096, "MIXED": 4096, "LONG": 8192, "BANK": 4096, "LANE": 4096, "FIXED": 0, "RATES": 4096}[name]
+    R = {"TIGHT": 4096, "MIXED": 4096, "LONG": 8192, "BANK": 4096, "LANE": 4096, "FIXED": 0, "RATES": 4096, "DEEP": 8192}[name]
     assert prog.R == R
     m = ss.model(script, R)                                   # asserts every ("at", p) and ("total", n) of the script
-    assert m[-1][1] == len(x) <= (18000 if name == "LONG" else 10000)
+    assert m[-1][1] == len(x) <= (18000 if name in ("LONG", "DEEP") else 10000)
     at = lambda kind: [m[i] for i, s in enumerate(script) if s[0] == kind]
     T = prog.max_taps
     if case_id[0] == "A":
@@ -76,9 +76,9 @@ def test_scripts_reach_the_ring_positions_they_name(case_id):
         assert big == [(R - 1200, 2 * R - 1200)]               # three launches: 1024 + 1024 + 452, the second crosses the ring's end
         assert kinds(script).count("fork") == len(saves) == 8
     if case_id[0] == "B":
-        assert [p for p, _ in at("load")] == [4000, 200]
+        assert [p for p, _ in at("load")] == [4000, 200] and R > 4000
         assert at("load")[1][1] == 2 * R + 200                 # ... the second after two wraps
-        assert [p for p, _ in at("poke")] == ([1028, 1628] if fmt == 6 else [])
+        assert [p for p, _ in at("poke")] == ([5124 % R, 5724 % R] if fmt == 6 else [])      # (1028 and 1628 where R is 4096)
         for i, s in enumerate(script):
             if s[0] == "poke":
                 (chain, pokes), = s[1].items()
@@ -109,7 +109,34 @@ def test_scripts_reach_the_ring_positions_they_name(case_id):
         assert [s for s in script[:i] if s[:2] == ("opt", "fir_impl")][-2][2] == 1          # ... the block in front ran with 1
         syncs = [i for i, s in enumerate(script) if s[0] == "sync"]
         assert len(syncs) == 5
-    if case_id.startswith("D-MIXED"):
+    if case_id[0] == "N":
+        blocks = [(i, s[1]) for i, s in enumerate(script) if s[0] == "block"][-11:]
+        assert [n for _, n in blocks] == [1024, 700, 513, 1024, 600, 1024, 700, 513, 1024, 600, 1024]
+        opt, walk, first_other = dict(fir_impl=1, fir_rows=0, fir_lean=-1), [], None
+        for i, s in enumerate(script):
+            if s[0] == "opt" and s[1] in opt:
+                opt[s[1]] = s[2]
+            if s[0] == "block":
+                walk.append((opt["fir_impl"], opt["fir_rows"], opt["fir_lean"]))
+                if walk[-1] != (1, 4, 1) and first_other is None:
+                    first_other = (m[i][0], s[1])
+        ring = (1, 4, 1)
+        assert walk[-11:] == [ring, (2, 0, -1), ring, (3, 4, 0), ring, (4, 0, 0), ring, (1, 2, 1), ring, (0, 0, -1), ring] and set(walk[:-11]) <= {ring}
+        assert all(n > 512 for (_, n), w in zip(blocks, walk[-11:]) if w == ring)
+        p, n = first_other
+        assert (p < R < p + n) if "wrapped" in case_id else (0 < p and p + n < R)
+        i = kinds(script).index("save")
+        assert kinds(script[:i]).count("block") == len(walk) - 10                # behind the table's first block
+        i = kinds(script).index("load")
+        before = [j for j in range(i) if script[j][0] == "block"][-1]
+        assert walk[kinds(script[:before]).count("block")] == (3, 4, 0)           # the block in front of the load: fir_stream
+        assert [s for s in script[:i] if s[:2] == ("opt", "fir_impl")][-1][2] == 1 and [s for s in script[:i] if s[:2] == ("opt", "fir_lean")][-1][2] == 1
+        assert kinds(script).count("sync") == 6
+    if name == "DEEP" and case_id[0] in "ABDE":
+        assert script[:2] == [("opt", "fir_rows", 4), ("opt", "fir_lean", 1)] and T == 4097
+    if case_id.startswith("E-DEEP"):
+        assert script[-2:] == [("block", 1024), ("sync",)]
+    if case_id.startswith("D-MIXED") or case_id.startswith("D-DEEP"):
         assert [p for p, _ in at("params")] == [1300, 1324] and [p for p, _ in at("generic")] == [1324, 0]
         assert [s[2] for s in script if s[0] == "shards"] == [300, 1, 1024, 257]
         assert at("shards")[0][0] == 1324
@@ -137,7 +164,7 @@ def test_programs_run_on_the_chain_kernels(name, fmt):
     assert r.shard_info() == dict(total_chains=prog.C, first_chain=0, nchains=prog.C, in_io_min=prog.C, in_io_max=2 * prog.C - 1,
                                   out_io_min=0, out_io_max=prog.C - 1)
     worlds = {s[1] for cid, c in ss.CASES.items() if c[:2] == (name, fmt) for s in ss.case(cid)[1] if s[0] == "shards"}
-    assert worlds == {"MIXED": {3}, "BANK": {2}, "LANE": {3}, "FIXED": {2}}.get(name, set())
+    assert worlds == {"MIXED": {3}, "BANK": {2}, "LANE": {3}, "FIXED": {2}, "DEEP": {3}}.get(name, set())
     for world in sorted(worlds):                               # what the "shards" steps of this program's scripts assume
         for rank in range(world):
             r.set_shard(rank, world)
@@ -157,3 +184,4 @@ def test_ring_length_restated():
     assert ss.ring_length(416) == 4096 and ss.ring_length(417) == 8192
     assert ss.ring_length(300) == 4096 and ss.ring_length(4096) == 8192 and ss.ring_length(8192) == 16384
     assert ss.ring_length(1030) == 8192 and ss.ring_length(97) == 4096
+    assert ss.ring_length(4097) == 8192 and ss.program("DEEP", 6).R == 8192 and ss.program("DEEP", 4).max_taps == 4097
