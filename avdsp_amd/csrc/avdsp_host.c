@@ -12,6 +12,7 @@
  */
 #include "avdsp_runtime.h"
 #include "avdsp_hip.h"
+#include "avdsp_shard_cut.h"
 
 #include <stdarg.h>
 #include <stddef.h>
@@ -121,6 +122,7 @@ typedef struct avdsp_ctx {
     int             opt_fir_tail;                          /* "fir_tail": a delay and / or a dressed finish behind a chain's DSP_FIR on the chain kernels, formats 4 and 6 (default 0) */
     int             opt_chain_mem;                         /* "chain_mem": STORE_MEM trunks and LOAD_MEM branches lowered to the chain kernels (default 0) */
     int             opt_mem_fir;                           /* "mem_fir": with "chain_mem", a DSP_FIR in a trunk or a branch on the chain kernels, formats 4 and 6 (default 0) */
+    int             opt_shard_trees;                       /* "shard_trees": with "chain_mem", a sharded core keeps its memory words: it is cut at tree boundaries (default 0) */
     int             opt_chain_copy;                        /* "chain_copy": DSP_LOAD_STORE lists lowered to the chain kernels' side as one copy launch (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
@@ -316,7 +318,7 @@ static const option_row g_options[] = {
     /* what the chain lowering takes (lower_gates); 0: such cores on the interpreter.  DESIGN.md 4.2f (SAT0DB_TPDF / _GAIN / _TPDF_GAIN
      * and a head TPDF_CALC), 4.2g (one DSP_DELAY behind a chain's banks), 4.2h (both behind a DSP_FIR), 4.2i (all of it in cores with
      * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call),
-     * 4.2l (a DSP_FIR in a trunk or a branch) */
+     * 4.2l (a DSP_FIR in a trunk or a branch), 5d (memory words in a sharded core, which is then cut at tree boundaries) */
     { "chain_finish", OPT_REPLAN, .off = SLOT(opt_chain_finish), ZERO_OR_ONE("chain_finish") },
     { "chain_delay",  OPT_REPLAN, .off = SLOT(opt_chain_delay),  ZERO_OR_ONE("chain_delay") },
     { "fir_tail",     OPT_REPLAN, .off = SLOT(opt_fir_tail),     ZERO_OR_ONE("fir_tail") },
@@ -324,6 +326,7 @@ static const option_row g_options[] = {
     { "chain_mem",    OPT_REPLAN, .off = SLOT(opt_chain_mem),    ZERO_OR_ONE("chain_mem") },
     { "chain_copy",   OPT_REPLAN, .off = SLOT(opt_chain_copy),   ZERO_OR_ONE("chain_copy") },
     { "mem_fir",      OPT_REPLAN, .off = SLOT(opt_mem_fir),      ZERO_OR_ONE("mem_fir") },
+    { "shard_trees",  OPT_REPLAN, .off = SLOT(opt_shard_trees),  ZERO_OR_ONE("shard_trees") },
     /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it: what
      * dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
     { "rate_count_static", OPT_HOST, .hook = HOOK_RATE_STATIC, .flags = OF_WRITE_ONLY },
@@ -464,12 +467,7 @@ int dspRuntimeGetOption(const char *key)
  * The chains of a core are independent (lower_core proves it per core), so N processes -- one per GPU -- may each
  * run a contiguous range of them with no exchange at all.  Contiguous and balanced: the first (total % world)
  * ranks take one chain more, i.e. avdsp_amd/sharding.py shard_range().                                        */
-static void shard_range(int total, int world, int rank, int *lo, int *hi)
-{
-    const int q = total / world, r = total % world;
-    *lo = rank * q + (rank < r ? rank : r);
-    *hi = *lo + q + (rank < r ? 1 : 0);
-}
+#define shard_range avdsp_shard_range                   /* (avdsp_shard_cut.h: the stand-alone layout driver cuts with the same function) */
 
 int dspRuntimeSetShard(int rank, int world)
 {
@@ -978,6 +976,7 @@ typedef struct {
     int      fir_tail;        /* "fir_tail": formats 4 and 6, the chain FIR's */
     int      mux_tail, mem, copy;      /* "mux_tail", "chain_mem", "chain_copy" */
     int      mem_fir;         /* "mem_fir": only with "chain_mem" */
+    int      shard_trees;     /* "shard_trees": only with "chain_mem" */
     unsigned delay_factor;
 } lower_gates;
 
@@ -991,6 +990,7 @@ static lower_gates gates_of(int format)
     g.mem = G.opt_chain_mem;
     g.copy = G.opt_chain_copy;
     g.mem_fir = G.opt_chain_mem && G.opt_mem_fir;             /* (formats 4 and 6 by what else refuses: lower_fir the int64 model, lower_mem formats 3 and 5) */
+    g.shard_trees = G.opt_chain_mem && G.opt_shard_trees;
     g.delay_factor = delay_line_factor();
     return g;
 }
@@ -1157,7 +1157,7 @@ static int lower_mem(lower_walk *W)
         return fail(-8, "word %d: LOAD_MEM_DATA is not lowered to the HIP path (of the memory opcodes only LOAD_MEM and STORE_MEM are)", at);
     if (!chain_kernel_format(W->format)) return fail(-8, "word %d: a memory word is not lowered to the HIP path in format %d", at, W->format);
     if (G.ninst > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the program has instances", at);
-    if (G.shard_world > 1) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the core is sharded", at);
+    if (G.shard_world > 1 && !W->g.shard_trees) return fail(-8, "word %d: a memory word is not lowered to the HIP path while the core is sharded", at);
     LC_NEED(1);
     LC_PROG(a[0], 2);
     if (!*W->smap && !(*W->smap = store_mem_map())) return fail(-9, "out of memory");
@@ -1397,6 +1397,144 @@ static int lower_sat_store(lower_walk *W)
 #undef LC_IO
 #undef LC_PREAD
 
+/* ---- "shard_trees"  ----
+ * The tree of every chain, for avdsp_tree_shard_bounds(): a chain whose memory word has a trunk in the core belongs to that trunk's
+ * tree (the trunk's chain index names it), every other chain -- ordinary, or a branch of a word nobody in the core writes -- is a tree
+ * of its own.  NULL: out of memory */
+static int *tree_of_chains(const lowered *L)
+{
+    const int n = L->nchains;
+    int *t = (int *)malloc((size_t)(n ? n : 1) * sizeof *t);
+    long long *trunk = (long long *)malloc((size_t)(n ? n : 1) * sizeof *trunk);      /* word << 32 | chain, sorted: a branch finds its trunk by its word */
+    if (!t || !trunk) { free(t); free(trunk); return 0; }
+    int nt = 0;
+    for (int i = 0; i < n; i++) {
+        t[i] = i;
+        if (L->chains[i].mem_store) trunk[nt++] = ((long long)L->chains[i].mem_word << 32) | (long long)i;
+    }
+    qsort(trunk, (size_t)nt, sizeof *trunk, cmp_ll);
+    for (int i = 0; i < n; i++) {
+        if (!L->chains[i].mem_word || L->chains[i].mem_store) continue;
+        const long long key = (long long)L->chains[i].mem_word << 32;
+        int a = 0, b = nt;                                   /* the first trunk at or above (word, chain 0) */
+        while (a < b) { const int m = (a + b) / 2; if (trunk[m] < key) a = m + 1; else b = m; }
+        if (a < nt && (int)(trunk[a] >> 32) == L->chains[i].mem_word) t[i] = (int)(trunk[a] & 0x7FFFFFFF);
+    }
+    free(trunk);
+    return t;
+}
+
+/* This process's contiguous slice [lo, hi) of a lowered core's chains (dspRuntimeSetShard): shard_range(), or -- a sharded core with
+ * memory words, which only "shard_trees" lowers -- the cut at tree boundaries.  0, or -9 (out of memory) */
+static int shard_cut(const lowered *L, int *lo, int *hi)
+{
+    shard_range(L->nchains, G.shard_world, G.shard_rank, lo, hi);
+    if (G.shard_world <= 1 || !L->nmem) return 0;
+    int *t = tree_of_chains(L);
+    int *b = (int *)malloc(((size_t)G.shard_world + 1 + 2 * (size_t)L->nchains + 1) * sizeof *b);
+    if (!t || !b) { free(t); free(b); return fail(-9, "out of memory"); }
+    avdsp_tree_shard_bounds(t, L->nchains, G.shard_world, b, b + G.shard_world + 1);
+    *lo = b[G.shard_rank]; *hi = b[G.shard_rank + 1];
+    free(t); free(b);
+    return 0;
+}
+
+/* Marks, in map[0 .. total), every program word an opcode outside [first, end) -- another core -- reads or writes: the targets of
+ * LOAD_MEM and STORE_MEM and every range an opcode reads as a parameter (what scan_generic's gs_param and the lowering's pread record),
+ * at every rate the program is encoded for -- a table kept by hand beside scan_generic's switch, which points here.  0, or -1: an opcode whose ranges cannot be enumerated (unknown, too short, or pointing
+ * outside the program) */
+static int mark_foreign_words(int first, int end, unsigned char *map)
+{
+    const int total = dspHeaderPtr->totalLength, nf = G.num_freq;
+    const int *w = (const int *)G.code;
+    for (int at = 0; at < total;) {
+        const int op = (int)((unsigned)w[at] >> 16), skip = w[at] & 0xFFFF;
+        if (skip == 0) break;
+        if (at + skip > total) return -1;
+        if (at >= first && at < end) { at += skip; continue; }
+        const int *a = w + at + 1;
+        int need = 0, nr = 0;
+        long long r[16][2];                                  /* [offset from `at`, words] */
+#define FW_RANGE(off, n) do { if (nr == 16) return -1; r[nr][0] = (off); r[nr][1] = (n); nr++; } while (0)
+        switch (op) {
+        case DSP_HEADER: case DSP_NOP: case DSP_CORE: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:
+        case DSP_SWAPXY: case DSP_COPYXY: case DSP_COPYYX: case DSP_CLRXY:
+        case DSP_ADDXY: case DSP_ADDYX: case DSP_SUBXY: case DSP_SUBYX: case DSP_NEGX: case DSP_NEGY:
+        case DSP_MULXY: case DSP_DIVXY: case DSP_DIVYX: case DSP_AVGXY: case DSP_AVGYX: case DSP_SQRTX:
+        case DSP_SAT0DB: case DSP_SAT0DB_TPDF: case DSP_WHITE:
+        case DSP_SHIFT: case DSP_MUL_VALUE: case DSP_DIV_VALUE: case DSP_MUL_VALUE_INT: case DSP_DIV_VALUE_INT: case DSP_AND_VALUE_INT: case DSP_CLIP:
+        case DSP_LOAD: case DSP_STORE: case DSP_LOAD_STORE: case DSP_TPDF_CALC: case DSP_TPDF: case DSP_DELAY_1: case DSP_LOAD_MEM_DATA:
+        case DSP_RMS: case DSP_DCBLOCK: case DSP_DITHER: case DSP_DISTRIB: case DSP_DIRAC: case DSP_SQUAREWAVE: case DSP_SINE:
+            break;                                           /* (immediates and words of the data area only) */
+        case DSP_LOAD_GAIN: need = 2; if (skip > need) FW_RANGE(a[1], 1); break;
+        case DSP_GAIN: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN: case DSP_VALUE: case DSP_VALUE_INT:
+            need = 1; if (skip > need) FW_RANGE(a[0], 1); break;
+        case DSP_LOAD_MEM: case DSP_STORE_MEM: need = 1; if (skip > need) FW_RANGE(a[0], 2); break;
+        case DSP_DELAY: case DSP_DELAY_DP: need = 3; if (skip > need && a[2]) FW_RANGE(a[2], 1); break;
+        case DSP_DATA_TABLE: need = 5; if (skip > need) { if (a[2] < 0) return -1; FW_RANGE(a[4], a[2]); } break;
+        case DSP_DITHER_NS2: need = 2; if (skip > need) FW_RANGE(a[1], 3ll * nf); break;
+        case DSP_BIQUADS: {
+            need = 2;
+            if (skip <= need) break;
+            const long long bank = (long long)at + a[1];
+            if (bank < 0 || bank + 2 > total) return -1;
+            const int num = (short)w[bank];
+            if (num < 1) return -1;
+            FW_RANGE(a[1], 5 + 6ll * nf + (long long)(num - 1) * dspBiquadFreqSkip);      /* the header and every rate's coefficients of every section */
+            break; }
+        case DSP_LOAD_MUX: {
+            need = 2;
+            if (skip <= need) break;
+            const long long t = (long long)at + a[0];
+            if (t < 0 || t >= total) return -1;
+            const int n = (short)w[t];
+            FW_RANGE(a[0], 1 + 2ll * (n > 0 ? n : 0));
+            break; }
+        case DSP_FIR:
+            need = nf + 1;
+            if (skip <= need || nf > 15) return -1;
+            for (int f = 0; f < nf; f++) {
+                if (!a[f]) continue;
+                const long long imp = (long long)at + a[f];
+                if (imp < 0 || imp >= total) return -1;
+                const int length = w[imp];
+                FW_RANGE(a[f], 1 + ((length >> 16) || length < 0 ? 0 : (long long)length));
+            }
+            break;
+        default: return -1;
+        }
+#undef FW_RANGE
+        if (skip <= need) return -1;
+        for (int k = 0; k < nr; k++) {
+            const long long lo = (long long)at + r[k][0], hi = lo + r[k][1];
+            if (lo < 0 || hi > total) return -1;
+            if (hi > lo) memset(map + lo, 1, (size_t)(hi - lo));
+        }
+        at += skip;
+    }
+    return 0;
+}
+
+/* A trunk's mem_stage writes its word into this rank's mirror alone, so a word another core reads -- as a constant branch, through the
+ * interpreter's LOAD_MEM, as a parameter -- or writes would be stale on every rank but the trunk's: a sharded core whose memory words
+ * (trunk targets and branch sources, both words of each) are touched by an opcode outside [first, end), the core, is not lowered */
+static int check_shared_words(const lowered *L, int first, int end)
+{
+    if (!L->nmem) return 0;
+    unsigned char *map = (unsigned char *)calloc((size_t)dspHeaderPtr->totalLength, 1);
+    if (!map) return fail(-9, "out of memory");
+    int rc = 0;
+    if (mark_foreign_words(first, end, map))
+        rc = fail(-8, "an opcode of another core whose parameter words cannot be told may share a memory word of this core: not lowered to the HIP path while the core is sharded");
+    for (int i = 0; i < L->nchains && !rc; i++) {
+        const int w = L->chains[i].mem_word;
+        if (w && (map[w] || map[w + 1]))
+            rc = fail(-8, "memory word %d is shared with another core: not lowered to the HIP path while the core is sharded", w);
+    }
+    free(map);
+    return rc;
+}
+
 /* The lowering of one core: the gates, the walk, the checks behind it.  -8: not lowered (the text says why), -9: out
  * of memory, or what ensure_encoding returns.  mux_damaged (may be NULL): set when the refusal is a LOAD_MUX whose table cannot be used.
  * lower_core_ex owns the STORE_MEM map the walk may build. */
@@ -1413,6 +1551,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     W.p = dspFindCoreBegin(core);
     W.g = gates_of(format);
     if (ensure_encoding(format)) return g_err_code;
+    const int first_word = (int)(W.p - G.code);
 
     for (;; W.p += W.skip) {
         const int op = W.op = W.p->op.opcode, at = W.at = (int)(W.p - G.code);
@@ -1450,6 +1589,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     if (!rc) rc = check_copies(L);
     if (!rc && L->nchains == 0 && L->ncopy == 0) rc = fail(-8, "core contains no LOAD..STORE chain");
     if (!rc) rc = check_mem_words(L, W.g.mem_fir);
+    if (!rc && G.shard_world > 1 && W.g.shard_trees) rc = check_shared_words(L, first_word, W.at);
     if (!rc) rc = check_mux_beside_tails(L, &W.g);
     if (!rc) rc = check_line_vs_mux_result(L, &W.g);
     if (!rc) rc = check_lines_apart(L, &W.g);
@@ -1720,6 +1860,8 @@ static int scan_generic(int format, opcode_t *core, int end_word, avdsp_generic_
         S.at = at; S.skip = skip;
         int rc = 0;
         if (op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) nreal++;
+        /* (an opcode added here, or a gs_param() added to one: mark_foreign_words() keeps the same ranges per opcode for the shared-word
+         * check of "shard_trees" -- an opcode it does not know refuses every sharded tree core of a program that holds it) */
         switch (op) {
         case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:
         case DSP_SWAPXY: case DSP_COPYXY: case DSP_COPYYX: case DSP_CLRXY:
@@ -2089,19 +2231,24 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
     cp->deps = deps;
     if (chains) {
         /* this process's contiguous slice of the core's chains (dspRuntimeSetShard; the whole core when unsharded):
-         * the plan, its FIR rings and the IO windows a block call must cover shrink to the slice */
+         * the plan, its FIR rings and the IO windows a block call must cover shrink to the slice.  ("shard_trees", DESIGN.md 5d: a
+         * core with memory words is cut between trees -- the slice holds every trunk with all its branches, so mem_trees sees no
+         * branch whose trunk runs elsewhere) */
         int lo, hi;
-        shard_range(L.nchains, G.shard_world, G.shard_rank, &lo, &hi);
+        if (shard_cut(&L, &lo, &hi)) { lowered_free(&L); return 0; }
         cp->total_chains = L.nchains; cp->first_chain = lo; cp->nchains = hi - lo;
         cp->ncopy = L.ncopy;                                /* ("chain_copy": never under a shard; a core of pairs alone has no chain and is no empty shard) */
-        if (hi == lo && !L.ncopy) {                         /* more ranks than chains: nothing to do here */
+        /* more ranks than chains (or than trees): nothing to do here -- but for a head TPDF_CALC, which every rank runs: the cores
+         * behind this one dither with what it leaves in the program's globals.  Such a rank gets a plan of no chains, as a core of
+         * pairs alone has one */
+        if (hi == lo && !L.ncopy && (!L.tpdf_calc || G.chain_inst_made)) {
             cp->empty = 1; cp->plan_id = -1;
             lowered_free(&L);
             G.nplans++;
             return cp;
         }
         const int sec0 = hi > lo ? L.chains[lo].sec_base : 0;
-        const int sec1 = hi < L.nchains ? L.chains[hi].sec_base : L.nsec;
+        const int sec1 = hi == lo ? sec0 : hi < L.nchains ? L.chains[hi].sec_base : L.nsec;
         for (int i = lo; i < hi; i++) L.chains[i].sec_base -= sec0;
         avdsp_plan_desc d;
         memset(&d, 0, sizeof d);
@@ -2218,8 +2365,8 @@ static int core_report_open(int format, opcode_t *core, int lower, core_report *
     const int rc = report_preamble(format, core);
     if (rc || G.opt_generic || !lower) return rc;
     R->lowered_rc = lower_core_ex(format, core, &R->L, &R->damaged);
-    if (R->lowered_rc == 0) shard_range(R->L.nchains, G.shard_world, G.shard_rank, &R->lo, &R->hi);
-    else lowered_free(&R->L);
+    if (R->lowered_rc == 0) R->lowered_rc = shard_cut(&R->L, &R->lo, &R->hi);
+    if (R->lowered_rc) lowered_free(&R->L);
     return R->lowered_rc == -8 ? 0 : R->lowered_rc;
 }
 
@@ -2375,7 +2522,7 @@ int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *
 
 /* What "chain_mem" makes of the core -- its trunks (chains that end in STORE_MEM), its branches (chains that start with LOAD_MEM) and,
  * of those, the ones whose word no chain of the core writes: they read what the mirror holds when a launch starts.
- * Counted over the whole core: a core with memory words is never sharded. */
+ * Counted over the whole core, under a shard too ("shard_trees": the rank's slice is dspRuntimeShardInfo's). */
 int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches)
 {
     core_report R;

@@ -316,7 +316,8 @@ class Runtime:
         self._check(self.L.dspRuntimeTagOutput(out.ctypes.data, out.shape[1], column, out.shape[0]))
 
     def set_shard(self, rank: int, world: int):
-        """dspRuntimeSetShard: this process runs chains shard_range(total, world, rank) of every chain core."""
+        """dspRuntimeSetShard: this process runs chains shard_range(total, world, rank) of every chain core (a core with memory words,
+        under set_option("shard_trees", 1): sharding.tree_shard_bounds() -- cut between trees)."""
         self._select()
         self._check(self.L.dspRuntimeSetShard(rank, world))
 

@@ -8,6 +8,8 @@ of each [B][C] input block and produces its slice of the output block.  RCCL (to
 all-gather of the output slices / an all-reduce of their checksums."""
 from __future__ import annotations
 
+from typing import Sequence
+
 import numpy as np
 
 from . import progbuilder as pb
@@ -18,6 +20,28 @@ def shard_range(total_channels: int, world: int, rank: int) -> tuple[int, int]:
     q, r = divmod(total_channels, world)
     lo = rank * q + min(rank, r)
     return lo, lo + q + (1 if rank < r else 0)
+
+
+def tree_shard_bounds(tree_of: Sequence[int], world: int) -> list[int]:
+    """Where dspRuntimeSetShard cuts a core of len(tree_of) chains under "shard_trees" (avdsp_shard_cut.h is the same
+    rule in C): rank k runs chains [b[k], b[k + 1]) of the returned b[0 .. world].  tree_of[i] names the tree of chain i -- chains with
+    the same value stay on one rank.  A position 0 < p < n is open if no tree has a member below p and a member at or above p; 0 and n
+    are open.  b[k] is the open position nearest to shard_range(n, world, k)'s lo, a tie goes to the lower one.  Without trees (all
+    values distinct) that is shard_range itself."""
+    n = len(tree_of)
+    first, last = {}, {}
+    for i, t in enumerate(tree_of):
+        first.setdefault(t, i)
+        last[t] = i
+    closed = [False] * (n + 1)
+    for t, a in first.items():
+        for p in range(a + 1, last[t] + 1):
+            closed[p] = True
+    bounds = []
+    for k in range(world):
+        want = shard_range(n, world, k)[0]
+        bounds.append(min((p for p in range(n + 1) if not closed[p]), key=lambda p: (abs(p - want), p)))
+    return bounds + [n]
 
 
 def shard_program(fmt: int, total_channels: int, nsections: int, ntaps: int, world: int, rank: int,

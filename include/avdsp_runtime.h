@@ -205,7 +205,27 @@ int dspRuntimeUploadParams(void);
  *     in  = x + in_io_min-th column,  in_io_base  = in_io_min,  in_stride  = whatever pitch the slice has
  * and receives its slice of the output columns; dspRuntimeShardInfo() reports those IO ranges (host-only, nothing
  * runs).  Cores that are not chain cores (interpreter) are not cut: every rank runs them whole (replicas).
- * dspRuntimeSyncState() returns this rank's view: its own chains' state advanced, the other chains' untouched. */
+ * dspRuntimeSyncState() returns this rank's view: its own chains' state advanced, the other chains' untouched.
+ * A rank whose range of a core is empty (more ranks than chains) launches nothing for that core and touches neither window -- unless
+ * the core begins with a lowered DSP_TPDF_CALC ("chain_finish"): every rank runs that, because the cores behind it dither with what
+ * it leaves in the program's globals.  Such a call stores no sample, but it is a block call like any other: hand it valid pointers
+ * and windows at least one column wide (the ones the rank uses for its other cores will do).
+ *
+ * "shard_trees" (dspRuntimeSetOption, 0 or 1, default 0): with 0 a core that holds memory words ("chain_mem") is not
+ * lowered while a shard is set -- a contiguous slice of chains may separate a STORE_MEM trunk from its LOAD_MEM branches -- and runs
+ * whole on every rank, on the interpreter.  With 1 (and "chain_mem" 1) it is lowered and cut at TREE boundaries.  The tree of a chain:
+ * a chain whose memory word has a trunk in the core belongs to that trunk's tree; every other chain (ordinary, or a branch of a word
+ * nobody in the core writes) is a tree of its own.  A position p, 0 < p < chains, is open if no tree has a chain below p and a chain at
+ * or above p (trees need not be adjacent: a tree closes everything between its first and its last chain); 0 and `chains` are open.
+ * Rank k's lower boundary is the open position nearest to the balanced lo above, a tie goes to the lower position; its upper boundary
+ * is rank k + 1's lower one.  The ranges stay contiguous, disjoint and cover the core, balanced by chain count as far as the trees let
+ * them; a rank may come out empty (see below); a core without trees is cut exactly as above.  avdsp_amd/sharding.py
+ * tree_shard_bounds() is the same rule.  Branches load no IO: a rank's input window is its trunks' and its ordinary chains'.
+ * A trunk writes its word into THIS rank's mirror only, so such a core is lowered only if no opcode of another core reads or writes
+ * one of its memory words -- as LOAD_MEM / STORE_MEM target or as a parameter (-8, "memory word %d is shared with another core: ...";
+ * both cores of such a pair then run whole on every rank as with 0).  LOAD_STORE lists and instances stay refused under a shard.
+ * After a block a rank's mirror holds its own trunks' words advanced and every other memory word as it was -- the same contract as
+ * for state. */
 int dspRuntimeSetShard(int rank, int world);
 int dspRuntimeShardInfo(int format, opcode_t *core, int *total_chains, int *first_chain, int *nchains,
                         int *in_io_min, int *in_io_max, int *out_io_min, int *out_io_max);
@@ -377,9 +397,9 @@ int dspRuntimeMuxTailInfo(int format, opcode_t *core, int *dressed_chains, int *
  * frame.  Refused with -8 and a text of its own, the core then on the interpreter as with 0: a STORE_MEM that is not its chain's last
  * opcode, two STORE_MEM of one word, words that overlap, a LOAD_MEM in front of the STORE_MEM of its word, a word that another opcode
  * reads as a parameter or that is no free PARAM word, a DSP_FIR or a LOAD_MUX head in or beside such chains, LOAD_MEM_DATA, formats 3
- * and 5, instances, a set shard.
+ * and 5, instances, a set shard (unless "shard_trees" is 1: dspRuntimeSetShard above).
  * dspRuntimeMemInfo is host-only, nothing runs on the GPU: the core's trunks, its branches, and the branches whose word no chain of
- * the core writes.  A core without memory words and a core the interpreter runs report zeros. */
+ * the core writes -- of the whole core, under a shard too.  A core without memory words and a core the interpreter runs report zeros. */
 int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, int *constant_branches);
 
 /* "mem_fir" (dspRuntimeSetOption, 0 or 1, default 0): a DSP_FIR in a trunk or a branch of a "chain_mem" core, formats 4

@@ -16,6 +16,10 @@ the median over all its timed calls; with --timers the kernel timers (dspRuntime
 lines as they come, one JSON line at the end.
 
     python tools/firtree_bench.py [--steps 20] [--rounds 3] [--formats 4,6] [--blocks 1024,256] [--trees 1024] [--ways 3] [--taps 4096] [--timers] [--ladder]
+
+--shard RANK WORLD ("shard_trees" 1): the tree programs alone, one shard on this GPU -- dspRuntimeSetShard(RANK, WORLD), the
+core cut at tree boundaries -- against the whole core on the same library, alternating in the same way; the windows stay the whole
+block's.  `linear` is whole / (WORLD x shard).
 """
 from __future__ import annotations
 
@@ -129,13 +133,15 @@ def main() -> None:
     ap.add_argument("--timers", action="store_true")
     ap.add_argument("--ladder", action="store_true", help="mem_fir 1 against mem_fir 0 from 16 trees x 128 taps up, one call per cell")
     ap.add_argument("--stop-ms", type=float, default=1000.0)
+    ap.add_argument("--shard", type=int, nargs=2, metavar=("RANK", "WORLD"), help="one shard of the tree programs (shard_trees 1) against the whole core")
     a = ap.parse_args()
     import torch
     from avdsp_amd import devmem as dm
     blocks = [int(v) for v in a.blocks.split(",")]
     st = torch.cuda.current_stream().cuda_stream
     lines = []
-    options = ("chain_mem", "mem_fir", "fir_tail", "chain_delay", "chain_finish")
+    options = ("chain_mem", "mem_fir", "fir_tail", "chain_delay", "chain_finish") + (("shard_trees",) if a.shard else ())
+    rank, world = a.shard or (0, 1)
 
     def loaded(fmt, kind, shared, T, taps, mem_fir=1):
         r = rt.Runtime(fmt, program(fmt, kind, shared, T, a.ways, a.sections, taps, a.us), fs=48000, random=1, dither=24)
@@ -146,6 +152,37 @@ def main() -> None:
     try:
         for fmt in [int(v) for v in a.formats.split(",")]:
             for kind in a.kinds.split(","):
+                if a.shard:
+                    T = a.trees
+                    nout = T * a.ways
+                    r = loaded(fmt, kind, True, T, a.taps)
+                    xd = dm.to_device(pb.lcg_input(max(blocks), T, fmt == 6, seed=3))
+                    yd = dm.to_device(pb.lcg_input(max(blocks), nout, fmt == 6, seed=4))
+                    settings = (("whole", (0, 1)), ("shard", (rank, world)))
+                    for B in blocks:
+                        args = (xd.data_ptr(), T, nout, yd.data_ptr(), nout, 0, B, st)
+                        us = {name: [] for name, _ in settings}
+                        cuts, chains = {}, {}
+                        for _ in range(a.rounds):
+                            for name, (k, n) in settings:
+                                r.set_shard(k, n)
+                                s = r.shard_info()
+                                cuts[name], chains[name] = (s["first_chain"], s["nchains"]), r.core_info()["chains"]
+                                r.run_block_device(*args)
+                                r.run_block_device(*args)
+                                torch.cuda.synchronize()
+                                us[name] += time_calls(r, args, a.steps)
+                                print(f"# format {fmt} {kind} block {B} {name}: {len(us[name])} calls, median {statistics.median(us[name]):.1f} us", flush=True)
+                        med = {name: statistics.median(v) for name, v in us.items()}
+                        lines.append(dict(format=fmt, kind=kind, trees=T, ways=a.ways, sections=a.sections, taps=a.taps, block=B, delay_us=a.us, shard=[rank, world],
+                                          **{f"{name}_us": round(m, 1) for name, m in med.items()}, **{f"{name}_min_us": round(min(v), 1) for name, v in us.items()},
+                                          linear=round(med["whole"] / (world * med["shard"]), 3), first_chain_and_chains=cuts, lowered_chains=chains,
+                                          calls={name: len(v) for name, v in us.items()}))
+                        print(lines[-1], flush=True)
+                    r.set_shard(0, 1)
+                    r.release()
+                    del xd, yd
+                    continue
                 if a.ladder:
                     T, taps = 16, 128
                     while True:
@@ -206,6 +243,7 @@ def main() -> None:
                 flat.release()
                 del xd, yd
     finally:
+        rt.lib().dspRuntimeSetShard(0, 1)
         for key in options:
             rt.Runtime.set_global_option(key, 0)
     print(json.dumps(dict(tool="firtree_bench", lines=lines)))

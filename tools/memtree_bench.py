@@ -15,6 +15,12 @@ call lasts more than `--slow-ms` is measured by that one call and left out of th
 frames in turn, one wave: seconds per block); every line says how many calls stand behind each figure.  One JSON line at the end.
 
     python tools/memtree_bench.py [--steps 20] [--rounds 3] [--formats 2,4,6] [--blocks 1024,256] [--trees 1024] [--ways 3] [--sections 8] [--us 1000]
+
+--shard RANK WORLD ("shard_trees" 1): the tree program alone, one shard of it on this GPU -- dspRuntimeSetShard(RANK, WORLD),
+the core cut at tree boundaries -- against the whole core on the same library, alternating in the same way; the windows stay the
+whole block's (they only have to cover the shard's IOs).  `linear` is whole / (WORLD x shard): 1.0 would be a shard that costs its
+share of the whole.  --with-off adds the same shard with "shard_trees" 0 -- the core whole on the interpreter, as every rank ran it
+before the option --, measured like the other slow settings; meant for a small --trees.
 """
 from __future__ import annotations
 
@@ -92,6 +98,73 @@ def unshared_program(fmt: int, trees: int, ways: int, sections: int, us: int):
     return enc.encode(build, 2 if fmt == 2 else 6, F48000, F48000, max_io=nout + trees, capacity=nout * (sections * 16 + 32) + 4096)
 
 
+def shard_mode(a) -> None:
+    """one shard of the tree program against the whole core"""
+    import torch
+    from avdsp_amd import devmem as dm
+    rank, world = a.shard
+    T, W = a.trees, a.ways
+    nout = T * W
+    blocks = [int(v) for v in a.blocks.split(",")]
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+    options = ("chain_mem", "chain_delay", "chain_finish", "shard_trees")
+    try:
+        for fmt in [int(v) for v in a.formats.split(",")]:
+            r = rt.Runtime(fmt, tree_program(fmt, T, W, a.sections, a.us), fs=48000, random=1, dither=24)
+            for key in options:
+                r.set_option(key, 1)
+            xd = dm.to_device(pb.lcg_input(max(blocks), T, fmt == 6, seed=3))
+            yd = dm.to_device(pb.lcg_input(max(blocks), nout, fmt == 6, seed=4))
+            settings = [("whole", (0, 1), 1), ("shard", (rank, world), 1)] + ([("shard_trees_0", (rank, world), 0)] if a.with_off else [])
+            for B in blocks:
+                args = (xd.data_ptr(), T, nout, yd.data_ptr(), nout, 0, B, st)
+                us = {name: [] for name, _, _ in settings}
+                slow, cuts, chains = set(), {}, {}
+                for _ in range(a.rounds):
+                    for name, (k, n), opt in settings:
+                        if name in slow:
+                            continue
+                        r.set_option("shard_trees", opt)
+                        r.set_shard(k, n)
+                        s = r.shard_info()
+                        cuts[name], chains[name] = (s["first_chain"], s["nchains"]), r.core_info()["chains"]
+                        r.run_block_device(*args)
+                        w0, w1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        w0.record()
+                        r.run_block_device(*args)
+                        w1.record()
+                        torch.cuda.synchronize()
+                        if w0.elapsed_time(w1) > a.slow_ms:
+                            slow.add(name)
+                            us[name].append(w0.elapsed_time(w1) * 1e3)
+                            print(f"# format {fmt} block {B} {name}: one call of {us[name][0] / 1e6:.3f} s", flush=True)
+                            continue
+                        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+                        for e0, e1 in ev:
+                            e0.record()
+                            r.run_block_device(*args)
+                            e1.record()
+                        torch.cuda.synchronize()
+                        us[name] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
+                        print(f"# format {fmt} block {B} {name}: {len(us[name])} calls, median {statistics.median(us[name]):.1f} us", flush=True)
+                med = {name: statistics.median(v) for name, v in us.items()}
+                lines.append(dict(format=fmt, trees=T, ways=W, sections=a.sections, block=B, delay_us=a.us, shard=[rank, world],
+                                  **{f"{name}_us": round(m, 1) for name, m in med.items()},
+                                  **{f"{name}_min_us": round(min(us[name]), 1) for name in us},
+                                  linear=round(med["whole"] / (world * med["shard"]), 3), first_chain_and_chains=cuts, lowered_chains=chains,
+                                  calls={name: len(v) for name, v in us.items()}))
+                print(lines[-1], flush=True)
+            r.set_shard(0, 1)
+            r.release()
+            del xd, yd
+    finally:
+        rt.lib().dspRuntimeSetShard(0, 1)
+        for key in options:
+            rt.Runtime.set_global_option(key, 0)
+    print(json.dumps(dict(tool="memtree_bench", mode="shard", lines=lines)))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -103,6 +176,8 @@ def main() -> None:
     ap.add_argument("--sections", type=int, default=8)
     ap.add_argument("--us", type=int, default=1000)
     ap.add_argument("--slow-ms", type=float, default=20.0)
+    ap.add_argument("--shard", type=int, nargs=2, metavar=("RANK", "WORLD"), help="one shard of the tree program (shard_trees 1) against the whole core")
+    ap.add_argument("--with-off", action="store_true", help="with --shard: the same shard with shard_trees 0 too (the interpreter)")
     a = ap.parse_args()
     import torch
     from avdsp_amd import devmem as dm
@@ -111,6 +186,8 @@ def main() -> None:
     L.dsp_SAT0DB_TPDF_GAIN_Fixed.argtypes = [c_float]
     L.dsp_LOAD_MEM.argtypes = [c_int]
     L.dsp_STORE_MEM.argtypes = [c_int]
+    if a.shard:
+        return shard_mode(a)
     T, W = a.trees, a.ways
     nout = T * W
     blocks = [int(v) for v in a.blocks.split(",")]
