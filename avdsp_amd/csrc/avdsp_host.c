@@ -124,6 +124,7 @@ typedef struct avdsp_ctx {
     int             opt_mem_fir;                           /* "mem_fir": with "chain_mem", a DSP_FIR in a trunk or a branch on the chain kernels, formats 4 and 6 (default 0) */
     int             opt_shard_trees;                       /* "shard_trees": with "chain_mem", a sharded core keeps its memory words: it is cut at tree boundaries (default 0) */
     int             opt_chain_copy;                        /* "chain_copy": DSP_LOAD_STORE lists lowered to the chain kernels' side as one copy launch (default 0) */
+    int             opt_chain_ways;                        /* "chain_ways": two-way COPYXY / SWAPXY forks as two chains, and runs of DSP_GAIN / DSP_NEGX behind a chain's banks on chain_tail (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
 
@@ -318,7 +319,8 @@ static const option_row g_options[] = {
     /* what the chain lowering takes (lower_gates); 0: such cores on the interpreter.  DESIGN.md 4.2f (SAT0DB_TPDF / _GAIN / _TPDF_GAIN
      * and a head TPDF_CALC), 4.2g (one DSP_DELAY behind a chain's banks), 4.2h (both behind a DSP_FIR), 4.2i (all of it in cores with
      * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call),
-     * 4.2l (a DSP_FIR in a trunk or a branch), 5d (memory words in a sharded core, which is then cut at tree boundaries) */
+     * 4.2l (a DSP_FIR in a trunk or a branch), 5d (memory words in a sharded core, which is then cut at tree boundaries), 4.2n (two-way
+     * COPYXY / SWAPXY forks, runs of GAIN and NEGX behind the banks) */
     { "chain_finish", OPT_REPLAN, .off = SLOT(opt_chain_finish), ZERO_OR_ONE("chain_finish") },
     { "chain_delay",  OPT_REPLAN, .off = SLOT(opt_chain_delay),  ZERO_OR_ONE("chain_delay") },
     { "fir_tail",     OPT_REPLAN, .off = SLOT(opt_fir_tail),     ZERO_OR_ONE("fir_tail") },
@@ -327,6 +329,7 @@ static const option_row g_options[] = {
     { "chain_copy",   OPT_REPLAN, .off = SLOT(opt_chain_copy),   ZERO_OR_ONE("chain_copy") },
     { "mem_fir",      OPT_REPLAN, .off = SLOT(opt_mem_fir),      ZERO_OR_ONE("mem_fir") },
     { "shard_trees",  OPT_REPLAN, .off = SLOT(opt_shard_trees),  ZERO_OR_ONE("shard_trees") },
+    { "chain_ways",   OPT_REPLAN, .off = SLOT(opt_chain_ways),   ZERO_OR_ONE("chain_ways") },
     /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it: what
      * dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
     { "rate_count_static", OPT_HOST, .hook = HOOK_RATE_STATIC, .flags = OF_WRITE_ONLY },
@@ -720,6 +723,7 @@ typedef struct {
     int tpdf_calc, tpdf_calc_arg, tpdf_calc_word;         /* "chain_finish": the core begins with a DSP_TPDF_CALC; its width word and result word */
     int ndressed;                                         /* ... chains with a dressed finish */
     int ndelayed;                                         /* "chain_delay": chains with a DSP_DELAY */
+    int *fork_a; int nforks, cap_forks;                   /* "chain_ways": way A's chain of every two-way fork (way B is the next chain) */
     int nmem;                                             /* "chain_mem": trunks and branches */
     int *pread; int npread, cap_pread;                    /* ... program words [lo, hi) the core's opcodes read as parameters (pairs; kept under "chain_mem" only) */
     /* "chain_copy" (DESIGN.md 4.2k): the DSP_LOAD_STORE pairs of the core.  While the core is walked, cp_sym[io] is the frame INPUT whose
@@ -732,7 +736,7 @@ typedef struct {
 
 static void lowered_free(lowered *L)
 {
-    free(L->chains); free(L->coef_word); free(L->state_word); free(L->pread);
+    free(L->chains); free(L->coef_word); free(L->state_word); free(L->pread); free(L->fork_a);
     free(L->cp_sym); free(L->cp_mark); free(L->cp_seen); free(L->cp_src); free(L->cp_dst);
     memset(L, 0, sizeof *L);
 }
@@ -977,6 +981,7 @@ typedef struct {
     int      mux_tail, mem, copy;      /* "mux_tail", "chain_mem", "chain_copy" */
     int      mem_fir;         /* "mem_fir": only with "chain_mem" */
     int      shard_trees;     /* "shard_trees": only with "chain_mem" */
+    int      ways;            /* "chain_ways" */
     unsigned delay_factor;
 } lower_gates;
 
@@ -991,6 +996,7 @@ static lower_gates gates_of(int format)
     g.copy = G.opt_chain_copy;
     g.mem_fir = G.opt_chain_mem && G.opt_mem_fir;             /* (formats 4 and 6 by what else refuses: lower_fir the int64 model, lower_mem formats 3 and 5) */
     g.shard_trees = G.opt_chain_mem && G.opt_shard_trees;
+    g.ways = G.opt_chain_ways;
     g.delay_factor = delay_line_factor();
     return g;
 }
@@ -1090,6 +1096,11 @@ typedef struct {
     avdsp_chain    cur;               /* the open chain */
     int            open, fir_op;      /* fir_op: the open chain holds a DSP_FIR opcode (with taps or bypassed) */
     int            after_mem;         /* the opcode before was a trunk's STORE_MEM: a chain head or the core's end must follow */
+    /* "chain_ways" (DESIGN.md 4.2n).  head_now: this opcode is a chain head; behind_head: the opcode before it was (NOP, PARAM, PARAM_NUM
+     * and SERIAL between them do not count).  fork: 0 no COPYXY in the open chain, 1 in way A (COPYXY seen, at fork_word), 2 in way B
+     * (SWAPXY seen).  fork_head: the head of the fork's chain, which way B loads again */
+    int            head_now, behind_head, fork, fork_word;
+    avdsp_chain    fork_head;
     opcode_t      *p;                 /* the opcode at hand: its word index, length and payload */
     int            op, at;
     unsigned       skip;
@@ -1108,11 +1119,12 @@ static int chain_kernel_format(int format) { return format == 2 || format == 4 |
 static int open_chain(lower_walk *W)
 {
     if (W->open) {
+        if (W->fork == 1) return fail(-8, "word %d: a COPYXY without a SWAPXY in its chain is not lowered to the HIP path", W->fork_word);
         if (W->cur.n_out == 0) return fail(-8, "word %d: value replaced before any STORE (X/Y tricks are not lowered)", W->at);
         if (push_chain(W->L, &W->cur)) return fail(-9, "out of memory");
     }
     memset(&W->cur, 0, sizeof W->cur);
-    W->open = 1; W->fir_op = 0;
+    W->open = 1; W->fir_op = 0; W->fork = 0; W->head_now = 1;
     W->cur.sec_base = W->L->nsec;
     return 0;
 }
@@ -1175,6 +1187,8 @@ static int lower_mem(lower_walk *W)
         return 0;
     }
     if (!W->open) return fail(-8, "word %d: STORE_MEM without a LOAD", at);
+    if (W->fork) return fail(-8, "word %d: a STORE_MEM in a way of a COPYXY / SWAPXY fork is not lowered to the HIP path", at);
+    if (W->cur.ways_n) return fail(-8, "word %d: a GAIN or NEGX in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
     if (W->cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a memory word in a chain with a LOAD_MUX head is not lowered to the HIP path", at);
     if (W->cur.load_mode == AVDSP_LOAD_MEM) return fail(-8, "word %d: a STORE_MEM in a chain that starts with LOAD_MEM is not lowered to the HIP path", at);
     if (W->fir_op && !W->g.mem_fir) return fail(-8, "word %d: a DSP_FIR in a trunk (a chain that ends in STORE_MEM) is not lowered to the HIP path", at);
@@ -1244,6 +1258,7 @@ static int lower_biquads(lower_walk *W)
     const int at = W->at;
     const int *a = W->a;
     avdsp_chain *cur = &W->cur;
+    if (W->open && cur->ways_n) return fail(-8, "word %d: a GAIN or NEGX in front of a BIQUADS is not lowered to the HIP path", at);
     if (W->open && cur->delay_slot) return fail(-8, "word %d: a DSP_DELAY in front of the banks is not lowered to the HIP path", at);
     if (!W->open || cur->n_out || cur->sat || cur->fir_taps)
         return fail(-8, "word %d: BIQUADS outside the supported LOAD->BIQUADS->FIR->SAT0DB->STORE order", at);
@@ -1271,6 +1286,7 @@ static int lower_fir(lower_walk *W)
     const int at = W->at;
     const int *a = W->a;
     avdsp_chain *cur = &W->cur;
+    if (W->open && cur->ways_n) return fail(-8, "word %d: a GAIN or NEGX in a chain with a DSP_FIR is not lowered to the HIP path", at);
     if (W->open && cur->delay_slot)
         return W->g.fir_tail ? fail(-8, "word %d: a DSP_DELAY in front of the chain's DSP_FIR is not lowered to the HIP path", at)
                              : fail(-8, "word %d: a DSP_DELAY in a chain with a DSP_FIR is not lowered to the HIP path", at);
@@ -1373,6 +1389,83 @@ static int lower_tpdf_calc(lower_walk *W)
         return fail(-8, "word %d: data offset %d (+2) outside the state area (%d words)", at, a[1], dspHeaderPtr->dataSize);
     L->tpdf_calc = 1; L->tpdf_calc_arg = a[0]; L->tpdf_calc_word = W->prog_words + a[1];
     return 0;
+}
+
+/* "chain_ways" (DESIGN.md 4.2n), the two-way fork  HEAD, COPYXY, <way A>, SWAPXY, <way B>:  way A stays the open chain, SWAPXY closes it
+ * and opens way B as a chain of its own that loads the head again.  COPYXY is Y = X (dsp_runtime.c:344-347), SWAPXY exchanges them
+ * (:337-342), so way B starts from the head's value -- which the load again gives, since no chain's input IO is stored inside the core
+ * (check_independent), a launch's input and output windows do not overlap, and a memory word has one trunk, in front of its branches.
+ *
+ * Y-liveness, enforced here: among lowered opcodes only SWAPXY reads Y.  It is taken only with the fork's COPYXY before it in its own
+ * chain (fork == 1), and between the two no opcode writes Y: only loads do, and a load is a chain head, which ends the chain (open_chain
+ * refuses a fork left at 1).  What SWAPXY leaves in Y -- way A's result -- is dead: way B takes no X/Y opcode (fork == 2 refuses a second
+ * COPYXY or SWAPXY, every other X/Y opcode is refused wherever it stands), and behind way B comes a chain head, which overwrites Y
+ * before anything could read it, or the core's end. */
+static int lower_fork(lower_walk *W)
+{
+    const int at = W->at;
+    if (!W->g.ways) return LC_NOT_LOWERED;
+    if (W->op == DSP_COPYXY) {
+        if (W->fork) return fail(-8, "word %d: a second COPYXY in one chain is not lowered to the HIP path", at);
+        if (!W->open || !W->behind_head) return fail(-8, "word %d: a COPYXY that is not directly behind a chain head is not lowered to the HIP path", at);
+        if (W->cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a COPYXY behind a LOAD_MUX head is not lowered to the HIP path", at);
+        W->fork = 1; W->fork_word = at;
+        W->fork_head = W->cur;
+        return 0;
+    }
+    if (W->fork == 2) return fail(-8, "word %d: a second SWAPXY in one chain is not lowered to the HIP path", at);
+    if (!W->open || W->fork != 1) return fail(-8, "word %d: a SWAPXY without a COPYXY behind its chain's head is not lowered to the HIP path", at);
+    if (W->cur.n_out == 0) return fail(-8, "word %d: a SWAPXY before way A's first STORE is not lowered to the HIP path", at);
+    lowered *L = W->L;
+    if (L->nforks == L->cap_forks) {
+        const int c = L->cap_forks ? 2 * L->cap_forks : 64;
+        int *q = (int *)realloc(L->fork_a, (size_t)c * sizeof *q);
+        if (!q) return fail(-9, "out of memory");
+        L->fork_a = q; L->cap_forks = c;
+    }
+    L->fork_a[L->nforks++] = L->nchains;
+    if (push_chain(L, &W->cur)) return fail(-9, "out of memory");
+    /* way B: the load again -- load_mode, in_io, gain_bits, mem_word (a LOAD_MEM head: a second branch of the same word) */
+    W->cur = W->fork_head;
+    W->cur.sec_base = L->nsec;
+    if (W->cur.load_mode == AVDSP_LOAD_MEM) L->nmem++;
+    W->fir_op = 0; W->fork = 2;
+    return 0;
+}
+
+/* "chain_ways": DSP_GAIN (dsp_runtime.c:636-640: ALU *= the parameter) and DSP_NEGX (:380-383), a run of at most AVDSP_MAX_WAY_OPS behind
+ * the chain's last BIQUADS -- or its head, COPYXY or SWAPXY -- and in front of its DSP_DELAY, SAT0DB slot and STOREs; chain_tail applies
+ * them in program order (two gains are two roundings: nothing is folded) */
+static int lower_way_op(lower_walk *W)
+{
+    const int at = W->at;
+    const char *name = W->op == DSP_GAIN ? "GAIN" : "NEGX";
+    avdsp_chain *cur = &W->cur;
+    if (!W->g.ways) return LC_NOT_LOWERED;
+    if (!W->open) return fail(-8, "word %d: a %s in front of the chain's LOAD is not lowered to the HIP path", at, name);
+    if (!chain_kernel_format(W->format)) return fail(-8, "word %d: a %s is not lowered to the HIP path in format %d", at, name, W->format);
+    if (G.ninst > 1) return fail(-8, "word %d: a %s is not lowered to the HIP path while the program has instances", at, name);
+    if (cur->load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a %s in a chain with a LOAD_MUX head is not lowered to the HIP path", at, name);
+    if (W->fir_op) return fail(-8, "word %d: a %s in a chain with a DSP_FIR is not lowered to the HIP path", at, name);
+    if (cur->n_out || cur->sat || cur->delay_slot) return fail(-8, "word %d: a %s behind a DSP_DELAY, a SAT0DB or a STORE is not lowered to the HIP path", at, name);
+    if (cur->ways_n == AVDSP_MAX_WAY_OPS) return fail(-8, "word %d: more than %d GAIN / NEGX in a run are not lowered to the HIP path", at, AVDSP_MAX_WAY_OPS);
+    if (W->op == DSP_GAIN) {
+        LC_NEED(1);
+        LC_PROG(W->a[0], 1);
+        cur->ways_op[cur->ways_n] = AVDSP_WAY_GAIN;
+        cur->ways_gain_bits[cur->ways_n] = W->p[W->a[0]].u32;
+        LC_PREAD(W->a[0], 1);
+    } else cur->ways_op[cur->ways_n] = AVDSP_WAY_NEG;
+    cur->ways_n++;
+    return 0;
+}
+
+/* "chain_ways": every other opcode that reads or writes Y.  (With the option off they get the generic text, as ever) */
+static int lower_other_xy(lower_walk *W)
+{
+    if (!W->g.ways) return LC_NOT_LOWERED;
+    return fail(-8, "word %d: X/Y opcode %d (%s) is not lowered to the HIP path (of the X/Y opcodes only the COPYXY and SWAPXY of a two-way fork are)", W->at, W->op,
+                dspOpcodeText[W->op] + (dspOpcodeText[W->op][0] == '\n'));
 }
 
 /* DSP_SAT0DB (dsp_runtime.c:464-475), DSP_STORE (:610-633) */
@@ -1561,6 +1654,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         if (W.skip == 0 || op == DSP_CORE) break;            /* dsp_runtime.c:321-331 */
         if ((long long)at + W.skip > W.prog_words) return fail(-8, "word %d: opcode longer than the program", at);
         if ((rc = lower_behind_trunk(&W)) != 0) return rc;
+        if (op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) { W.behind_head = W.head_now; W.head_now = 0; }
         switch (op) {
         case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:          break;
         case DSP_LOAD_STORE:                                                         rc = lower_load_store(&W); break;
@@ -1573,6 +1667,10 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         case DSP_SAT0DB_TPDF: case DSP_SAT0DB_GAIN: case DSP_SAT0DB_TPDF_GAIN:       rc = lower_finish(&W); break;
         case DSP_TPDF_CALC:                                                          rc = lower_tpdf_calc(&W); break;
         case DSP_SAT0DB: case DSP_STORE:                                             rc = lower_sat_store(&W); break;
+        case DSP_COPYXY: case DSP_SWAPXY:                                            rc = lower_fork(&W); break;
+        case DSP_GAIN: case DSP_NEGX:                                                rc = lower_way_op(&W); break;
+        case DSP_COPYYX: case DSP_CLRXY: case DSP_ADDXY: case DSP_ADDYX: case DSP_SUBXY: case DSP_SUBYX: case DSP_NEGY:
+        case DSP_MULXY: case DSP_DIVXY: case DSP_DIVYX: case DSP_AVGXY: case DSP_AVGYX:    rc = lower_other_xy(&W); break;
         default:                                                                     rc = LC_NOT_LOWERED; break;
         }
         if (rc == LC_NOT_LOWERED)
@@ -1581,6 +1679,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         if (rc) return rc;
     }
     if (W.open) {
+        if (W.fork == 1) return fail(-8, "word %d: a COPYXY without a SWAPXY in its chain is not lowered to the HIP path", W.fork_word);
         if (W.cur.n_out == 0) return fail(-8, "core ends with a chain that is never stored");
         if (push_chain(L, &W.cur)) return fail(-9, "out of memory");
     }
@@ -1590,6 +1689,9 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
     if (!rc && L->nchains == 0 && L->ncopy == 0) rc = fail(-8, "core contains no LOAD..STORE chain");
     if (!rc) rc = check_mem_words(L, W.g.mem_fir);
     if (!rc && G.shard_world > 1 && W.g.shard_trees) rc = check_shared_words(L, first_word, W.at);
+    if (!rc && W.g.ways && lowered_has_mux(L))              /* ("chain_ways": chain_tail beside the mux stage is "mux_tail"'s, which knows no way operations) */
+        for (int i = 0; i < L->nchains && !rc; i++)
+            if (L->chains[i].ways_n) rc = fail(-8, "a GAIN or NEGX in a core with LOAD_MUX heads is not lowered to the HIP path");
     if (!rc) rc = check_mux_beside_tails(L, &W.g);
     if (!rc) rc = check_line_vs_mux_result(L, &W.g);
     if (!rc) rc = check_lines_apart(L, &W.g);
@@ -2261,6 +2363,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.delay_line_factor = g.delay_factor;
         d.fir_tail = g.fir_tail; d.mux_tail = g.mux_tail; d.chain_mem = g.mem;
         d.mem_fir = g.mem_fir;
+        d.chain_ways = g.ways;
         d.chain_copy = g.copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
@@ -2574,6 +2677,24 @@ int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live)
     if (rc) return rc;
     put(pairs, R.L.ncopy_written); put(live, R.L.ncopy);
     core_report_close(&R);
+    return 0;
+}
+
+/* What "chain_ways" makes of the core -- the two-way COPYXY / SWAPXY forks of which this process runs a way (each way is
+ * a chain of its own: dspRuntimeCoreInfo counts both), and the chains this process runs that have a run of GAIN / NEGX for chain_tail. */
+int dspRuntimeWaysInfo(int format, opcode_t *core, int *forks, int *op_chains)
+{
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int nf = 0, no = 0;
+    for (int k = 0; k < R.L.nforks; k++) {               /* (way A is chain fork_a, way B the next: an empty shard runs neither) */
+        const int wa = R.L.fork_a[k], wb = wa + 1;
+        nf += (wa >= R.lo && wa < R.hi) || (wb >= R.lo && wb < R.hi);
+    }
+    for (int i = R.lo; i < R.hi; i++) no += R.L.chains[i].ways_n != 0;
+    core_report_close(&R);
+    put(forks, nf); put(op_chains, no);
     return 0;
 }
 

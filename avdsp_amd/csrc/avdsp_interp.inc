@@ -352,6 +352,11 @@ template <int FMT> __device__ __forceinline__ typename M<FMT>::alu fmacc(typenam
         return acc + FF(mul_ff(a, b));
     }
 }
+/* the int64 model's wrapping product, sum and difference (the reference's plain long long arithmetic, without the overflow C leaves
+ * undefined): one definition for the interpreter, strand_lanes and chain_tail's way operations */
+__device__ __forceinline__ long long wmul(long long x, long long y) { return (long long)((unsigned long long)x * (unsigned long long)y); }
+__device__ __forceinline__ long long wadd(long long x, long long y) { return (long long)((unsigned long long)x + (unsigned long long)y); }
+__device__ __forceinline__ long long wsub(long long x, long long y) { return (long long)((unsigned long long)x - (unsigned long long)y); }
 /* accumulator <-> 32-bit float, the way the reference's instructions do it */
 template <int FMT> __device__ __forceinline__ float to_sp(typename M<FMT>::alu X)
 {
@@ -795,9 +800,6 @@ __device__ __forceinline__ void run(const GenericArgs &a, int *prog, unsigned *s
     if (a.tpdf_role == 2 && lane < nb) { const int *q = wc.tpdf_seq + 2 * (wc.frame0 + lane); gv = q[0]; gr = q[1]; }
 
     auto to_alu_i = [](int v) -> alu_t { return (alu_t)v; };
-    auto wmul = [](long long x, long long y) { return (long long)((unsigned long long)x * (unsigned long long)y); };
-    auto wadd = [](long long x, long long y) { return (long long)((unsigned long long)x + (unsigned long long)y); };
-    auto wsub = [](long long x, long long y) { return (long long)((unsigned long long)x - (unsigned long long)y); };
     /* sums and products whose two operands can both be NaN (the float models' DSP_DITHER makes NaN, see fsub): the
      * first operand's NaN wins, as in the SSE instruction the source line compiles to -- hipcc is free to commute
      * a plain a + b, and does so differently in the two kernels */
@@ -1758,9 +1760,6 @@ __device__ __forceinline__ void strand_batch(const StrandArgs &a, int *tab, int 
     constexpr bool AI = M<FMT>::alu_int, A64 = M<FMT>::alu64, SI = M<FMT>::smp_int;
     constexpr bool WIDE = A64 && !AI;
     constexpr int AW = A64 ? 2 : 1;
-    auto wmul = [](long long x, long long y) { return (long long)((unsigned long long)x * (unsigned long long)y); };
-    auto wadd = [](long long x, long long y) { return (long long)((unsigned long long)x + (unsigned long long)y); };
-    auto wsub = [](long long x, long long y) { return (long long)((unsigned long long)x - (unsigned long long)y); };
     /* this frame's dither value: published per frame by the piece that holds the core's TPDF_CALC, else the program's current one.
      * One fetch for the batch (lane f takes frame f's), and what SAT0DB_TPDF adds (dsp_tpdf.h:133-156) worked out here, once per
      * frame and batch: the value is uniform, so its special cases would be scalar branches in front of every use */

@@ -3655,8 +3655,16 @@ struct TailArgs {
     unsigned delay_factor;
     BlockIO io;
 };
-template <int FMT>
-__global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a)
+/* chain_tail<FMT, true> ("chain_ways"): the run of DSP_GAIN (dsp_runtime.c:636-640) and DSP_NEGX (:380-383) that stands
+ * behind the chain's banks, applied to the accumulator right after it is read -- from the row or the sample -- in program order, with
+ * the interpreter's own arithmetic (AVDSP_SOP_GAIN, AVDSP_SOP_NEGX of strand_lanes), in front of the slot-B opcode and the line.  One
+ * WayRec per DelayRec, a table of its own: DelayRec and chain_tail<FMT> -- OPS false, under the name it had -- are as they were.
+ * Launched only for a plan that has such a chain. */
+struct WayRec { int n, op[AVDSP_MAX_WAY_OPS]; unsigned gain_bits[AVDSP_MAX_WAY_OPS]; };
+struct TailArgsOps : TailArgs { const WayRec *ways; };
+template <bool OPS> using TailArgsW = std::conditional_t<OPS, TailArgsOps, TailArgs>;
+template <int FMT, bool OPS>
+__device__ __forceinline__ void chain_tail_body(const TailArgsW<OPS> &a)
 {
     using namespace interp;
     using alu_t = typename Alu<FMT>::type;
@@ -3681,6 +3689,19 @@ __global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a)
             const unsigned long long bits = a.hand[(size_t)r.hand_row * kFirChunk + f];
             if constexpr (FMT == 2) X = (long long)bits; else X = __longlong_as_double((long long)bits);
         } else X = load_stage<FMT>(a.io.in[(size_t)f * a.io.in_stride + (c.in_io - a.io.in_base)], c.load_mode, c.gain_bits);
+    }
+    if constexpr (OPS) {
+        const WayRec w = a.ways[blockIdx.x];
+        /* (interp's wmul, wsub and to_alu; uniform over the workgroup; each operation rounds: none is folded.  Unrolled: the record stays in scalar registers) */
+#pragma unroll
+        for (int k = 0; k < AVDSP_MAX_WAY_OPS; k++) {
+            if (k >= w.n) break;
+            if (w.op[k] == AVDSP_WAY_GAIN) {
+                if constexpr (FMT == 2) X = wmul(X, (long long)(int)w.gain_bits[k]); else X *= to_alu<FMT>(__uint_as_float(w.gain_bits[k]));
+            } else {
+                if constexpr (FMT == 2) X = wsub(0, X); else X = -X;
+            }
+        }
     }
     auto slot_opcode = [&](alu_t v) __attribute__((always_inline)) -> alu_t {
         if (r.finish) return finish_alu<FMT>(v, r.finish, r.gain_bits, a.addend[f]);
@@ -3713,6 +3734,14 @@ __global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a)
         if (r.slot == AVDSP_DELAY_A) X = slot_opcode(X);
         emit_out(a.io, c, f, store_stage<FMT>(X, 0, a.io.store_mask));
     }
+}
+template <int FMT>
+__global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgs a) { chain_tail_body<FMT, false>(a); }
+template <int FMT, bool OPS>
+__global__ __launch_bounds__(kFirChunk) void chain_tail(const TailArgsOps a)
+{
+    static_assert(OPS, "the form without way operations is chain_tail<FMT>");
+    chain_tail_body<FMT, true>(a);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -4616,6 +4645,7 @@ struct Plan {
     int block_f0 = 0;                                    /* first frame, in the block call, of the launch being made (the addend table's index) */
     /* delay lines ("chain_delay"): chain_tail behind the cascades */
     int n_tail = 0; DevArr<DelayRec> d_tail;             /* chains with a DSP_DELAY */
+    int n_way_ops = 0; DevArr<WayRec> d_ways;            /* "chain_ways": of d_tail, the chains with way operations; [n_tail] their runs (made when n_way_ops) */
     DevArr<unsigned long long> d_hand;                   /* [those with sections][kFirChunk]: the accumulators their cascades hand over */
     DevArr<int> d_hand_row;                              /* [record of d_chains]: the chain's row there (-1: none) */
     unsigned delay_factor = 0;
@@ -5900,6 +5930,14 @@ int enqueue_finishers(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t st
         TailArgs a{};
         a.buf = prog->d_buf; a.chains = pl.d_chains; a.recs = pl.d_tail; a.hand = pl.d_hand; a.addend = prog->d_addend + pl.block_f0;
         a.delay_factor = pl.delay_factor; a.io = io;
+        if (pl.n_way_ops) {
+            /* ("chain_ways": a plan with way operations -- the OPS form for all its tail chains, the others with a run of none) */
+            if (!pl.d_ways) return set_err("a launch of chains with way operations without their table");
+            TailArgsOps w{};
+            static_cast<TailArgs &>(w) = a;
+            w.ways = pl.d_ways;
+            hipLaunchKernelGGL((chain_tail<FMT, true>), dim3((unsigned)pl.n_tail), dim3((unsigned)((io.nframes + 63) / 64 * 64)), 0, stream, w);
+        } else
         hipLaunchKernelGGL(chain_tail<FMT>, dim3((unsigned)pl.n_tail), dim3((unsigned)((io.nframes + 63) / 64 * 64)), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
@@ -6305,6 +6343,18 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
             else tail.push_back(DelayRec{i, AVDSP_DELAY_A, 0, 0, 0, row, c.sat, c.finish, c.finish_gain_bits});
         }
         if (pl.d_tail.upload(tail)) return -1;
+        if (t.n_way_ops) {
+            std::vector<WayRec> ways(tail.size());
+            for (size_t k = 0; k < tail.size(); k++) {
+                const avdsp_chain &c = t.chains[tail[k].cid];
+                WayRec w{};
+                w.n = c.ways_n;
+                for (int q = 0; q < c.ways_n; q++) { w.op[q] = c.ways_op[q]; w.gain_bits[q] = c.ways_gain_bits[q]; }
+                ways[k] = w;
+            }
+            if (pl.d_ways.upload(ways)) return -1;
+            pl.n_way_ops = t.n_way_ops;
+        }
         pl.n_tail = (int)tail.size(); pl.delay_factor = d->delay_line_factor;
         if (rows) {
             if (pl.d_hand_row.upload(hand_row)) return -1;

@@ -136,7 +136,8 @@ struct ChainTables {
     std::vector<int> fir, pass;          /* chains with a FIR; chains with neither sections nor FIR */
     std::vector<int> pass_dressed;       /* ... of the latter, those with a dressed finish (they are not in `pass`) */
     int n_dressed = 0;                   /* chains with a dressed finish */
-    std::vector<int> tail;               /* chains with a DSP_DELAY ("chain_delay") and the handed FIR chains: chain_tail finishes and stores them (they are in neither pass list) */
+    std::vector<int> tail;               /* chains with a DSP_DELAY ("chain_delay"), the handed FIR chains and ("chain_ways") chains with way operations: chain_tail finishes and stores them (they are in neither pass list) */
+    int n_way_ops = 0;                   /* "chain_ways": of those, the chains with way operations -- a plan with one launches chain_tail's OPS form */
     /* "fir_tail": the handed FIR chains -- a FIR, and a dressed finish and / or a delay behind it.  Their FIR launch (a HAND form) leaves
      * the accumulators in the hand-over block for chain_tail.  `fir` holds every chain with a FIR, they among them (rings, taps, history);
      * `fir_plain` those that store themselves */
@@ -296,7 +297,7 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (!c.mem_store) continue;
-        if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || (c.fir_taps && !mem_fir) || c.in_io < 0) return text("chain %d: not a trunk", i);
+        if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || c.ways_n || (c.fir_taps && !mem_fir) || c.in_io < 0) return text("chain %d: not a trunk", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
         int exact;
         if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
@@ -341,7 +342,8 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
             /* ("mem_fir": a FIR alone -- no column, no record of the stage's own, no row of the tree's: the stage feeds its ring, its FIR
              * stores it or hands it over like any FIR chain's) */
             else if (c.fir_taps) { c.load_mode = kLoadFed; t.mem_feed.push_back(MemFeed{(int)k, i}); }
-            else if (c.delay_slot) { if (tr.row < 0) tr.row = t.n_hand_rows++; t.mem_row[i] = tr.row; }
+            /* ("chain_ways": a branch with way operations is chain_tail's like a delayed one -- the stage fills its tree's row, and does not finish it) */
+            else if (c.delay_slot || c.ways_n) { if (tr.row < 0) tr.row = t.n_hand_rows++; t.mem_row[i] = tr.row; }
             else {
                 MemOwn o{};
                 o.tree = (int)k; o.cid = i; o.sat = c.sat; o.finish = c.finish; o.gain_bits = c.finish_gain_bits; o.n_out = c.n_out;
@@ -404,9 +406,20 @@ inline std::string check_chains(const avdsp_plan_desc *d, long long buf_words, C
             if (c.delay_max < 0 || c.delay_word < 0 || (long long)c.delay_word + 1 + nline > buf_words || c.delay_us_word < 0 || c.delay_us_word >= buf_words)
                 return text("chain %d: delay line outside the loaded buffer", i);
         }
+        if (c.ways_n) {
+            /* way operations (avdsp_chain::ways_n, "chain_ways"): chain_tail's OPS form of formats 2, 4 and 6; no FIR, no LOAD_MUX plan, no instances */
+            if (c.ways_n < 0 || c.ways_n > AVDSP_MAX_WAY_OPS) return text("chain %d: %d way operations", i, c.ways_n);
+            for (int k = 0; k < c.ways_n; k++)
+                if (c.ways_op[k] != AVDSP_WAY_GAIN && c.ways_op[k] != AVDSP_WAY_NEG) return text("chain %d: way operation %d", i, c.ways_op[k]);
+            if (!d->chain_ways || (d->format != 2 && d->format != 4 && d->format != 6) || c.fir_taps || t.has_mux || d->instances > 1)
+                return text("chain %d: way operations have no kernel here", i);
+            t.n_way_ops++;
+        }
         const bool handed = c.fir_taps && (c.finish || c.delay_slot);
         if (handed) t.fir_hand.push_back(i); else if (c.fir_taps) t.fir_plain.push_back(i);
-        if (c.delay_slot || handed) {
+        /* ("chain_ways": a chain with way operations is a tail chain exactly as a delayed one is -- without a DSP_DELAY it gets the record of a
+         * line of 0 samples, as a handed FIR chain without one) */
+        if (c.delay_slot || handed || c.ways_n) {
             t.tail.push_back(i);
             if (c.nsec || c.fir_taps || t.mux_handed[i]) t.hand_row[i] = t.n_hand_rows++;
             else if (t.mem_row[i] >= 0) t.hand_row[i] = t.mem_row[i];      /* (a branch without sections: its tree's row, shared with its siblings) */
@@ -478,7 +491,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
         /* ("chain_mem": a trunk hands over like a delayed chain -- "mem_fir": unless a FIR stands behind its cascade, which then feeds
          * the ring like any; branches are groups of their own, of the second phase) */
         const int kind = t.has_mem ? t.mem_kind[i] : 0, phase = kind == 2 ? 1 : 0;
-        const bool hand = !fir && (t.chains[i].delay_slot != 0 || kind == 1), wide = hand || (!fir && t.chains[i].finish != 0);
+        const bool hand = !fir && (t.chains[i].delay_slot != 0 || t.chains[i].ways_n != 0 || kind == 1), wide = hand || (!fir && t.chains[i].finish != 0);
         auto it = std::find_if(L.groups.begin(), L.groups.end(), [&](const GroupLayout &g) { return g.nsec == nsec && g.wide == wide && g.hand == hand && g.phase == phase; });
         if (it == L.groups.end()) { L.groups.emplace_back(); it = L.groups.end() - 1; it->nsec = nsec; it->wide = wide; it->hand = hand; it->phase = phase; }
         it->ids.push_back(i);
@@ -512,7 +525,7 @@ inline CascadeLayout cascade_groups(int format, const ChainTables &t)
                     pc.sec_base = c.sec_base + at; pc.nsec = pg.nsec;
                     if (k > 0) { pc.in_io = j; pc.load_mode = kLoadRaw; }
                     if (k + 1 < np) {
-                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j; pc.finish = 0; pc.delay_slot = 0;
+                        pc.fir_taps = 0; pc.sat = kStoreRaw; pc.n_out = 1; pc.out_io[0] = j; pc.finish = 0; pc.delay_slot = 0; pc.ways_n = 0;
                         pg.ids[j] = (int)L.dev_chains.size(); L.dev_chains.push_back(pc);
                     } else { pg.ids[j] = g.ids[j]; L.dev_chains[g.ids[j]] = pc; }
                 }

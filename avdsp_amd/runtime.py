@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeMemFirInfo", "dspRuntimeCopyInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeMemFirInfo", "dspRuntimeCopyInfo", "dspRuntimeWaysInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -144,6 +144,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "dspRuntimeCopyInfo"):             # (tools/copy_bench.py --parent loads a library from before the call)
             L.dspRuntimeCopyInfo.restype = i32
             L.dspRuntimeCopyInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "dspRuntimeWaysInfo"):             # (AVDSP_LIB may name a library from before the call: bench.py's A/B against the parent)
+            L.dspRuntimeWaysInfo.restype = i32
+            L.dspRuntimeWaysInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -307,6 +310,14 @@ class Runtime:
         the live pairs the plan copies -- forwarding, the last writer and self-copies resolved)."""
         a, b = C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeCopyInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
+
+    def ways_info(self, core_index: int = 0):
+        """dspRuntimeWaysInfo (host-only): in a core that "chain_ways" puts on the chain kernels, (the two-way COPYXY / SWAPXY forks of which
+        this process runs a way -- each way is a chain of its own --, the chains with a run of GAIN / NEGX for chain_tail), at the current
+        shard."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeWaysInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
         return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):

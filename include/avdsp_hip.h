@@ -15,6 +15,7 @@
  * and ("chain_delay") chains without FIR and LOAD_MUX with one DSP_DELAY (:769-794) on either side of the SAT0DB slot
  * and ("fir_tail", formats 4 and 6) both of them behind a chain's DSP_FIR
  * and ("mux_tail") all of that behind a LOAD_MUX head and beside LOAD_MUX chains
+ * and ("chain_ways", formats 2, 4 and 6) a run of DSP_GAIN (:636-640) and DSP_NEGX (:380-383) behind the banks, in front of delay, SAT0DB and STORE
  *
  * for every chain of the core over a block of frame-interleaved samples.
  */
@@ -66,7 +67,15 @@ typedef struct avdsp_chain {
      * "mem_fir" either may have fir_taps: a trunk's FIR stands in front of its STORE_MEM, a branch's behind its sections */
     int32_t  mem_word;
     int32_t  mem_store;
+    /* way operations ("chain_ways"): a run of DSP_GAIN (dsp_runtime.c:636-640) and DSP_NEGX (:380-383) behind the chain's
+     * last BIQUADS -- or behind its head -- and in front of its DSP_DELAY, its SAT0DB slot and its STOREs, applied in this order by
+     * chain_tail.  No FIR, no LOAD_MUX head, no trunk, no instances */
+    int32_t  ways_n;                 /* 0: none */
+    int32_t  ways_op[4];             /* AVDSP_WAY_*            (AVDSP_MAX_WAY_OPS entries) */
+    uint32_t ways_gain_bits[4];      /* AVDSP_WAY_GAIN: Q4.28 int or float bits of the DSP_GAIN parameter */
 } avdsp_chain;
+#define AVDSP_MAX_WAY_OPS 4
+enum { AVDSP_WAY_GAIN = 1, AVDSP_WAY_NEG = 2 };
 enum { AVDSP_DELAY_NONE = 0, AVDSP_DELAY_A = 1, AVDSP_DELAY_B = 2 };      /* A: in front of the SAT0DB slot, B: behind it */
 enum { AVDSP_FINISH_NONE = 0, AVDSP_FINISH_TPDF = 1, AVDSP_FINISH_GAIN = 2, AVDSP_FINISH_TPDF_GAIN = 3 };      /* bit 0: dither, bit 1: gain */
 
@@ -113,6 +122,8 @@ typedef struct avdsp_plan_desc {
     const int32_t *copy_dst;         /* [ncopy]: ... IO written in the output window */
     int32_t  mem_fir;                /* 1 ("mem_fir", with chain_mem, formats 4 and 6): a trunk or a branch may have fir_taps -- a trunk's FIR
                                         hands its sums to mem_stage, a branch's FIR takes the word the stage forms; 0: such a chain is refused */
+    int32_t  chain_ways;             /* 1 ("chain_ways", formats 2, 4 and 6): a chain may have way operations (ways_n), which make it a chain of chain_tail's;
+                                        0: such a chain is refused */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

@@ -434,6 +434,21 @@ int dspRuntimeMemFirInfo(int format, opcode_t *core, int *fir_trunks, int *fir_b
  * core the interpreter runs report zeros. */
 int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live);
 
+/* "chain_ways" (dspRuntimeSetOption, 0 or 1, default 0): X/Y forks and way operations in a core of chains.
+ * Two-way forks, formats 2 to 6:  HEAD, COPYXY, <way A>, SWAPXY, <way B>  with HEAD a LOAD, a LOAD_GAIN or (under "chain_mem") a LOAD_MEM
+ * and COPYXY the opcode directly behind it.  Each way is whatever an ordinary chain may be behind its head under the options that are
+ * on, and ends in at least one STORE; way B becomes a chain of its own that loads the head again (a LOAD_MEM head: a second branch of
+ * the word).  Way operations, formats 2, 4 and 6: a run of at most 4 DSP_GAIN / DSP_NEGX behind a chain's last BIQUADS -- or, without
+ * banks, behind its head, COPYXY or SWAPXY -- and in front of its DSP_DELAY, SAT0DB slot and STOREs, applied in program order.
+ * Refused with -8 and a text of its own, the core then on the interpreter as with 0: a COPYXY that is not directly behind a head or has
+ * no SWAPXY in its chain, a SWAPXY without that COPYXY or before way A's first STORE, a second COPYXY or SWAPXY in a chain, a STORE_MEM
+ * in a way, a fork behind a LOAD_MUX head, every other X/Y opcode; a GAIN or NEGX in front of a BIQUADS, behind a DSP_DELAY, a SAT0DB
+ * or a STORE, a fifth one in a run, one in a chain with a DSP_FIR, in a trunk, in a core with LOAD_MUX heads, in formats 3 and 5, or
+ * while the program has instances.  With 0 every core takes the path and the refusal text it had before the option existed.
+ * dspRuntimeWaysInfo is host-only, nothing runs on the GPU: the forks of which this process runs a way (dspRuntimeCoreInfo counts each
+ * way as a chain) and the chains this process runs that have way operations.  A core the interpreter runs reports zeros. */
+int dspRuntimeWaysInfo(int format, opcode_t *core, int *forks, int *op_chains);
+
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
 /* Several programs in one process.  dspRuntimeInit(codePtr, ...) loads a program into a context of its own, keyed by the
