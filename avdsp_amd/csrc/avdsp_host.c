@@ -125,6 +125,7 @@ typedef struct avdsp_ctx {
     int             opt_shard_trees;                       /* "shard_trees": with "chain_mem", a sharded core keeps its memory words: it is cut at tree boundaries (default 0) */
     int             opt_chain_copy;                        /* "chain_copy": DSP_LOAD_STORE lists lowered to the chain kernels' side as one copy launch (default 0) */
     int             opt_chain_ways;                        /* "chain_ways": two-way COPYXY / SWAPXY forks as two chains, and runs of DSP_GAIN / DSP_NEGX behind a chain's banks on chain_tail (default 0) */
+    int             opt_chain_sum;                         /* "chain_sum": with "chain_mem", a sum head  LOAD_MEM, (LOAD_MEM, ADDXY | SUBXY)+  in front of a branch, a tree of its own on mem_stage's SUM form, formats 2, 4 and 6 (default 0) */
     int             opt_mux_tail;                          /* "mux_tail": what "chain_finish", "chain_delay" and "fir_tail" lower, also in a core with LOAD_MUX chain heads (default 0) */
 } avdsp_ctx;
 
@@ -320,7 +321,7 @@ static const option_row g_options[] = {
      * and a head TPDF_CALC), 4.2g (one DSP_DELAY behind a chain's banks), 4.2h (both behind a DSP_FIR), 4.2i (all of it in cores with
      * LOAD_MUX heads), 4.2j (STORE_MEM trunks, LOAD_MEM branches), 4.2k (DSP_LOAD_STORE lists, one copy_pairs launch per block call),
      * 4.2l (a DSP_FIR in a trunk or a branch), 5d (memory words in a sharded core, which is then cut at tree boundaries), 4.2n (two-way
-     * COPYXY / SWAPXY forks, runs of GAIN and NEGX behind the banks) */
+     * COPYXY / SWAPXY forks, runs of GAIN and NEGX behind the banks), 4.2o (sum heads: a bus of memory words in front of a branch) */
     { "chain_finish", OPT_REPLAN, .off = SLOT(opt_chain_finish), ZERO_OR_ONE("chain_finish") },
     { "chain_delay",  OPT_REPLAN, .off = SLOT(opt_chain_delay),  ZERO_OR_ONE("chain_delay") },
     { "fir_tail",     OPT_REPLAN, .off = SLOT(opt_fir_tail),     ZERO_OR_ONE("fir_tail") },
@@ -330,6 +331,7 @@ static const option_row g_options[] = {
     { "mem_fir",      OPT_REPLAN, .off = SLOT(opt_mem_fir),      ZERO_OR_ONE("mem_fir") },
     { "shard_trees",  OPT_REPLAN, .off = SLOT(opt_shard_trees),  ZERO_OR_ONE("shard_trees") },
     { "chain_ways",   OPT_REPLAN, .off = SLOT(opt_chain_ways),   ZERO_OR_ONE("chain_ways") },
+    { "chain_sum",    OPT_REPLAN, .off = SLOT(opt_chain_sum),    ZERO_OR_ONE("chain_sum") },
     /* the reference's dspNumSamplingFreq static as a fresh process would have it (0), or as an earlier program left it: what
      * dspChangeFormat converts depends on it (dspRuntimeInit); a test hook, a process restart does the same */
     { "rate_count_static", OPT_HOST, .hook = HOOK_RATE_STATIC, .flags = OF_WRITE_ONLY },
@@ -725,6 +727,7 @@ typedef struct {
     int ndelayed;                                         /* "chain_delay": chains with a DSP_DELAY */
     int *fork_a; int nforks, cap_forks;                   /* "chain_ways": way A's chain of every two-way fork (way B is the next chain) */
     int nmem;                                             /* "chain_mem": trunks and branches */
+    int nterms;                                           /* "chain_sum": the words the sum heads load behind their first */
     int *pread; int npread, cap_pread;                    /* ... program words [lo, hi) the core's opcodes read as parameters (pairs; kept under "chain_mem" only) */
     /* "chain_copy" (DESIGN.md 4.2k): the DSP_LOAD_STORE pairs of the core.  While the core is walked, cp_sym[io] is the frame INPUT whose
      * word slot `io` holds by now (-1: its own), cp_seen[] the slots a pair has ever given another word; at the end cp_src / cp_dst are
@@ -935,7 +938,8 @@ static int dither_width_constant(void)
 static int check_mem_words(const lowered *L, int mem_fir)
 {
     if (!L->nmem) return 0;
-    long long *w = (long long *)malloc((size_t)L->nmem * sizeof *w);      /* word << 32 | trunk << 31 ... sorted by word, trunks first */
+    /* ("chain_sum": every word a sum head loads behind its first is held to the same rules, as a read of the head's chain) */
+    long long *w = (long long *)malloc((size_t)(L->nmem + L->nterms) * sizeof *w);      /* word << 32 | branch << 31 | term << 30 | chain ... sorted by word, trunks first */
     if (!w) return fail(-9, "out of memory");
     int k = 0, rc = 0;
     for (int i = 0; i < L->nchains; i++) {
@@ -943,15 +947,18 @@ static int check_mem_words(const lowered *L, int mem_fir)
         if (c->load_mode == AVDSP_LOAD_MUX) { free(w); return fail(-8, "memory words beside LOAD_MUX heads are not lowered to the HIP path"); }
         if (c->fir_taps && !mem_fir) { free(w); return fail(-8, "memory words beside a chain with a DSP_FIR are not lowered to the HIP path"); }
         if (c->mem_word) w[k++] = ((long long)c->mem_word << 32) | (c->mem_store ? 0 : 1ll << 31) | (long long)i;
+        for (int q = 0; q < c->sum_n; q++) w[k++] = ((long long)c->sum_word[q] << 32) | 3ll << 30 | (long long)i;
     }
     qsort(w, (size_t)k, sizeof *w, cmp_ll);
     int trunk = -1, trunk_word = -1;
     for (int j = 0; j < k && !rc; j++) {
-        const int word = (int)(w[j] >> 32), is_branch = (int)(w[j] >> 31) & 1, chain = (int)(w[j] & 0x7FFFFFFF);
+        const int word = (int)(w[j] >> 32), is_branch = (int)(w[j] >> 31) & 1, is_term = (int)(w[j] >> 30) & 1, chain = (int)(w[j] & 0x3FFFFFFF);
         if (j && word == (int)(w[j - 1] >> 32) + 1)
             rc = fail(-8, "memory words %d and %d of the core overlap without being the same word", word - 1, word);
         else if (!is_branch && word == trunk_word) rc = fail(-8, "memory word %d is written by two STORE_MEM of the core", word);
         else if (!is_branch) { trunk = chain; trunk_word = word; }
+        else if (word == trunk_word && chain < trunk && is_term)
+            rc = fail(-8, "memory word %d: a term of a sum head in front of the STORE_MEM of its word (the one-frame-lag form) is not lowered to the HIP path", word);
         else if (word == trunk_word && chain < trunk)
             rc = fail(-8, "memory word %d: a LOAD_MEM in front of the STORE_MEM of its word (the one-frame-lag form) is not lowered to the HIP path", word);
         for (int q = 0; q < L->npread && !rc; q++)
@@ -982,6 +989,7 @@ typedef struct {
     int      mem_fir;         /* "mem_fir": only with "chain_mem" */
     int      shard_trees;     /* "shard_trees": only with "chain_mem" */
     int      ways;            /* "chain_ways" */
+    int      sum;             /* "chain_sum": only with "chain_mem", formats 2, 4 and 6 */
     unsigned delay_factor;
 } lower_gates;
 
@@ -997,6 +1005,7 @@ static lower_gates gates_of(int format)
     g.mem_fir = G.opt_chain_mem && G.opt_mem_fir;             /* (formats 4 and 6 by what else refuses: lower_fir the int64 model, lower_mem formats 3 and 5) */
     g.shard_trees = G.opt_chain_mem && G.opt_shard_trees;
     g.ways = G.opt_chain_ways;
+    g.sum = G.opt_chain_mem && G.opt_chain_sum && (format == 2 || format == 4 || format == 6);
     g.delay_factor = delay_line_factor();
     return g;
 }
@@ -1101,6 +1110,10 @@ typedef struct {
      * (SWAPXY seen).  fork_head: the head of the fork's chain, which way B loads again */
     int            head_now, behind_head, fork, fork_word;
     avdsp_chain    fork_head;
+    /* "chain_sum" (DESIGN.md 4.2o).  term_now: this opcode is a LOAD_MEM taken as a term of the open chain's sum head (at term_at, its
+     * word term_word); behind_term: the opcode before it was -- an ADDXY or SUBXY must stand here.  sumop_now / behind_sumop: the same
+     * for that ADDXY / SUBXY, behind which the next term may stand */
+    int            term_now, behind_term, sumop_now, behind_sumop, term_at, term_word;
     opcode_t      *p;                 /* the opcode at hand: its word index, length and payload */
     int            op, at;
     unsigned       skip;
@@ -1178,6 +1191,16 @@ static int lower_mem(lower_walk *W)
             return fail(-8, "word %d: %s target (word %d) is not a free word of a PARAM section: it would "
                             "rewrite %s", at, op == DSP_STORE_MEM ? "STORE_MEM" : "LOAD_MEM", at + a[0] + k,
                         (*W->smap)[at + a[0] + k] ? "a count, IO number or length other opcodes rely on" : "the opcode stream");
+    if (op == DSP_LOAD_MEM && W->g.sum && W->open && W->cur.load_mode == AVDSP_LOAD_MEM && !W->fork &&
+        ((W->behind_head && !W->cur.sum_n) || W->behind_sumop)) {
+        /* "chain_sum": a LOAD_MEM directly behind a LOAD_MEM head, or behind the ADDXY / SUBXY of the term before, is the next term of
+         * the sum head -- the load moves the running value to Y, lower_sum_op takes it from there */
+        if (G.shard_world > 1) return fail(-8, "word %d: a sum head (LOAD_MEM, LOAD_MEM of word %d) is not lowered to the HIP path while the core is sharded", at, at + a[0]);
+        if (W->cur.sum_n == AVDSP_MAX_SUM_TERMS - 1)
+            return fail(-8, "word %d: a sum head of more than %d memory words (word %d would be the next) is not lowered to the HIP path", at, AVDSP_MAX_SUM_TERMS, at + a[0]);
+        W->term_now = 1; W->term_at = at; W->term_word = at + a[0];
+        return 0;
+    }
     if (op == DSP_LOAD_MEM) {
         const int rc = open_chain(W);
         if (rc) return rc;
@@ -1406,6 +1429,10 @@ static int lower_fork(lower_walk *W)
     const int at = W->at;
     if (!W->g.ways) return LC_NOT_LOWERED;
     if (W->op == DSP_COPYXY) {
+        /* ("chain_sum", Y-liveness behind a sum head: Y holds the previous running value -- the last term's LOAD_MEM moved it there, and
+         * ADDXY / SUBXY write X alone.  Among lowered opcodes only a fork's SWAPXY reads Y.  A fork behind a sum head is refused here
+         * (its way B would load the head again, and a sum head is no single load), so that value is dead) */
+        if (W->open && W->cur.sum_n) return fail(-8, "word %d: a COPYXY behind a sum head (LOAD_MEM of word %d and %d more) is not lowered to the HIP path", at, W->cur.mem_word, W->cur.sum_n);
         if (W->fork) return fail(-8, "word %d: a second COPYXY in one chain is not lowered to the HIP path", at);
         if (!W->open || !W->behind_head) return fail(-8, "word %d: a COPYXY that is not directly behind a chain head is not lowered to the HIP path", at);
         if (W->cur.load_mode == AVDSP_LOAD_MUX) return fail(-8, "word %d: a COPYXY behind a LOAD_MUX head is not lowered to the HIP path", at);
@@ -1457,6 +1484,26 @@ static int lower_way_op(lower_walk *W)
         LC_PREAD(W->a[0], 1);
     } else cur->ways_op[cur->ways_n] = AVDSP_WAY_NEG;
     cur->ways_n++;
+    return 0;
+}
+
+/* "chain_sum" (DESIGN.md 4.2o): the ADDXY (dsp_runtime.c:360-363, ALU += ALU2) or SUBXY (:370-373, ALU -= ALU2) of a sum head's term.
+ * It stands directly behind the term's LOAD_MEM (behind_term), which has moved the running value to Y and put the term's word in X: the
+ * running value becomes newest + running or newest - running, in this order, nothing reassociated (mem_stage's SUM form).  Anywhere
+ * else -- behind a LOAD or LOAD_GAIN head, behind banks, in a way of a fork -- it is refused */
+static int lower_other_xy(lower_walk *W);
+static int lower_sum_op(lower_walk *W)
+{
+    const int at = W->at;
+    const char *name = W->op == DSP_ADDXY ? "ADDXY" : "SUBXY";
+    avdsp_chain *cur = &W->cur;
+    if (!W->g.sum) return lower_other_xy(W);
+    if (!W->behind_term)
+        return fail(-8, "word %d: an %s that does not stand directly behind a LOAD_MEM behind a LOAD_MEM head (a sum head) is not lowered to the HIP path", at, name);
+    cur->sum_word[cur->sum_n] = W->term_word;
+    cur->sum_op[cur->sum_n] = W->op == DSP_ADDXY ? AVDSP_SUM_ADD : AVDSP_SUM_SUB;
+    cur->sum_n++; W->L->nterms++;
+    W->sumop_now = 1;
     return 0;
 }
 
@@ -1654,7 +1701,12 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         if (W.skip == 0 || op == DSP_CORE) break;            /* dsp_runtime.c:321-331 */
         if ((long long)at + W.skip > W.prog_words) return fail(-8, "word %d: opcode longer than the program", at);
         if ((rc = lower_behind_trunk(&W)) != 0) return rc;
-        if (op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) { W.behind_head = W.head_now; W.head_now = 0; }
+        if (op != DSP_NOP && op != DSP_PARAM && op != DSP_PARAM_NUM && op != DSP_SERIAL) {
+            W.behind_head = W.head_now; W.head_now = 0;
+            W.behind_term = W.term_now; W.term_now = 0; W.behind_sumop = W.sumop_now; W.sumop_now = 0;
+            if (W.behind_term && op != DSP_ADDXY && op != DSP_SUBXY)
+                return fail(-8, "word %d: a LOAD_MEM (of word %d) behind a LOAD_MEM head without its ADDXY or SUBXY is not lowered to the HIP path", W.term_at, W.term_word);
+        }
         switch (op) {
         case DSP_NOP: case DSP_PARAM: case DSP_PARAM_NUM: case DSP_SERIAL:          break;
         case DSP_LOAD_STORE:                                                         rc = lower_load_store(&W); break;
@@ -1669,7 +1721,8 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
         case DSP_SAT0DB: case DSP_STORE:                                             rc = lower_sat_store(&W); break;
         case DSP_COPYXY: case DSP_SWAPXY:                                            rc = lower_fork(&W); break;
         case DSP_GAIN: case DSP_NEGX:                                                rc = lower_way_op(&W); break;
-        case DSP_COPYYX: case DSP_CLRXY: case DSP_ADDXY: case DSP_ADDYX: case DSP_SUBXY: case DSP_SUBYX: case DSP_NEGY:
+        case DSP_ADDXY: case DSP_SUBXY:                                              rc = lower_sum_op(&W); break;
+        case DSP_COPYYX: case DSP_CLRXY: case DSP_ADDYX: case DSP_SUBYX: case DSP_NEGY:
         case DSP_MULXY: case DSP_DIVXY: case DSP_DIVYX: case DSP_AVGXY: case DSP_AVGYX:    rc = lower_other_xy(&W); break;
         default:                                                                     rc = LC_NOT_LOWERED; break;
         }
@@ -1678,6 +1731,7 @@ static int lower_core_body(int format, opcode_t *core, lowered *L, int *mux_dama
                         (op >= 0 && op < DSP_MAX_OPCODE) ? dspOpcodeText[op] + (dspOpcodeText[op][0] == '\n') : "?");
         if (rc) return rc;
     }
+    if (W.term_now) return fail(-8, "word %d: a LOAD_MEM (of word %d) behind a LOAD_MEM head without its ADDXY or SUBXY is not lowered to the HIP path", W.term_at, W.term_word);
     if (W.open) {
         if (W.fork == 1) return fail(-8, "word %d: a COPYXY without a SWAPXY in its chain is not lowered to the HIP path", W.fork_word);
         if (W.cur.n_out == 0) return fail(-8, "core ends with a chain that is never stored");
@@ -2364,6 +2418,7 @@ static core_plan *get_plan_range(int format, opcode_t *core, int end_word)
         d.fir_tail = g.fir_tail; d.mux_tail = g.mux_tail; d.chain_mem = g.mem;
         d.mem_fir = g.mem_fir;
         d.chain_ways = g.ways;
+        d.chain_sum = g.sum;
         d.chain_copy = g.copy; d.ncopy = L.ncopy; d.copy_src = L.cp_src; d.copy_dst = L.cp_dst;
         int32_t *fg_start = 0, *fg_chains = 0;
         if (!G.chain_inst_made) {                           /* (chain instances keep every chain on fir_tile: no groups) */
@@ -2637,6 +2692,7 @@ int dspRuntimeMemInfo(int format, opcode_t *core, int *trunks, int *branches, in
         if (c->mem_store) nt++;
         if (c->load_mode != AVDSP_LOAD_MEM) continue;
         nb++;
+        if (c->sum_n) continue;                              /* ("chain_sum": a sum head is one branch, and no constant one: dspRuntimeSumInfo) */
         int written = 0;
         for (int j = 0; j < R.L.nchains && !written; j++) written = R.L.chains[j].mem_store && R.L.chains[j].mem_word == c->mem_word;
         nc += !written;
@@ -2695,6 +2751,21 @@ int dspRuntimeWaysInfo(int format, opcode_t *core, int *forks, int *op_chains)
     for (int i = R.lo; i < R.hi; i++) no += R.L.chains[i].ways_n != 0;
     core_report_close(&R);
     put(forks, nf); put(op_chains, no);
+    return 0;
+}
+
+/* What "chain_sum" makes of the core -- its sum heads (each one chain for dspRuntimeCoreInfo and one branch for
+ * dspRuntimeMemInfo) and the memory words they load in all, the first of each head included.  (A sharded core has none.) */
+int dspRuntimeSumInfo(int format, opcode_t *core, int *heads, int *terms)
+{
+    core_report R;
+    const int rc = core_report_open(format, core, 1, &R);
+    if (rc) return rc;
+    int nh = 0, nt = 0;
+    for (int i = 0; i < R.L.nchains; i++)
+        if (R.L.chains[i].sum_n) { nh++; nt += 1 + R.L.chains[i].sum_n; }
+    core_report_close(&R);
+    put(heads, nh); put(terms, nt);
     return 0;
 }
 

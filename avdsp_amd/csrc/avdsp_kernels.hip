@@ -3778,8 +3778,41 @@ struct MemArgsFeed : MemArgs {
     const int *feed_start; const MemFeed *feed;      /* the feeds of tree k: feed[feed_start[k] .. feed_start[k + 1]) */
 };
 template <bool FEED> using MemArgsF = std::conditional_t<FEED, MemArgsFeed, MemArgs>;
-template <int FMT, bool FEED = false>
-__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsF<FEED> a)
+/* SUM ("chain_sum"): the plan has sum trees (kMemSrcSum) -- a sum head  LOAD_MEM, (LOAD_MEM, ADDXY | SUBXY)+  is a tree
+ * without word and trunk whose accumulator the tree's wave forms from its MemTerms in program order, a lane per frame: each term as a
+ * LOAD_MEM of its word sees it in that frame (mem_term), then, the load having moved the running value to Y, X = X + Y (dsp_runtime.c:
+ * 360-363) or X = X - Y (:370-373) with the interpreter's own wadd / wsub, xy_add / fsub and its operand order (avdsp_interp.inc, case
+ * DSP_ADDXY) -- the newest word first, nothing reassociated.  A row read is 512 consecutive bytes per wave and term.  From there the
+ * tree goes on as any: narrow_stage into LDS, feeds, the row for chain_tail, the stage's own stores; it writes no memory word.  SUM
+ * false is the kernel as it was, under the names it had. */
+template <bool FEED> struct MemArgsSum : MemArgsF<FEED> {
+    const int *sum_start; const MemTerm *terms;      /* the terms of tree k: terms[sum_start[k] .. sum_start[k + 1]) */
+};
+template <bool FEED, bool SUM> using MemArgsFS = std::conditional_t<SUM, MemArgsSum<FEED>, MemArgsF<FEED>>;
+template <int FMT>
+__device__ __forceinline__ typename Alu<FMT>::type mem_term(const MemArgs &a, const MemTerm &m, int f)
+{
+    if (m.src == kMemSrcSample) return load_stage<FMT>(a.io.in[(size_t)f * a.io.in_stride + (m.in_io - a.io.in_base)], m.load_mode, m.gain_bits);
+    unsigned long long u;
+    if (m.src == kMemSrcRow) u = a.hand[(size_t)m.row * kFirChunk + f];
+    else u = (unsigned long long)(unsigned)a.buf[m.word] | ((unsigned long long)(unsigned)a.buf[m.word + 1] << 32);
+    if constexpr (FMT == 2) return (long long)u; else return __longlong_as_double((long long)u);
+}
+template <int FMT>
+__device__ __forceinline__ typename Alu<FMT>::type mem_sum(const MemArgs &a, const MemTerm *first, const MemTerm *end, int f)
+{
+    using namespace interp;
+    using alu_t = typename Alu<FMT>::type;
+    alu_t Y = mem_term<FMT>(a, *first, f);                   /* the running value */
+    for (const MemTerm *m = first + 1; m < end; m++) {
+        const alu_t X = mem_term<FMT>(a, *m, f);             /* the newest word */
+        if (m->op == AVDSP_SUM_ADD) { if constexpr (FMT == 2) Y = wadd(X, Y); else Y = xy_add(X, Y); }
+        else { if constexpr (FMT == 2) Y = wsub(X, Y); else Y = fsub(X, Y); }
+    }
+    return Y;
+}
+template <int FMT, bool FEED, bool SUM>
+__device__ __forceinline__ void mem_stage_body(const MemArgsFS<FEED, SUM> &a)
 {
     static_assert(!FEED || FMT == 4 || FMT == 6, "the chain FIR's formats");
     using alu_t = typename Alu<FMT>::type;
@@ -3794,7 +3827,10 @@ __global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsF<FEED> a)
         const int f = f0 + lane;
         unsigned long long u;
         alu_t X;
-        if (tr.src == kMemSrcSample) {
+        if (SUM && tr.src == kMemSrcSum) {
+            if constexpr (SUM) X = mem_sum<FMT>(a, a.terms + a.sum_start[tile.tree0 + tl], a.terms + a.sum_start[tile.tree0 + tl + 1], f);
+            if constexpr (FMT == 2) u = (unsigned long long)X; else u = (unsigned long long)__double_as_longlong(X);
+        } else if (tr.src == kMemSrcSample) {
             X = load_stage<FMT>(a.io.in[(size_t)f * a.io.in_stride + (tr.in_io - a.io.in_base)], tr.load_mode, tr.gain_bits);
             if constexpr (FMT == 2) u = (unsigned long long)X; else u = (unsigned long long)__double_as_longlong(X);
         } else {
@@ -3824,6 +3860,14 @@ __global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsF<FEED> a)
         const int f = i / tile.ncol, c = i - f * tile.ncol;
         a.scratch[(size_t)(f0 + f) * a.scratch_stride + tile.col0 + c] = s_word[a.col_tree[tile.col0 + c] - tile.tree0][f];
     }
+}
+template <int FMT, bool FEED = false>
+__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsF<FEED> a) { mem_stage_body<FMT, FEED, false>(a); }
+template <int FMT, bool FEED, bool SUM>
+__global__ __launch_bounds__(kBlock) void mem_stage(const MemArgsSum<FEED> a)
+{
+    static_assert(SUM, "the forms without sum trees are mem_stage<FMT> and mem_stage<FMT, true>");
+    mem_stage_body<FMT, FEED, true>(a);
 }
 
 /* One wave per block call, on the call's stream ahead of the cascades: the core's DSP_TPDF_CALC over the whole block (has_calc: what
@@ -4691,6 +4735,9 @@ struct Plan {
     DevArr<int> d_fir_trunk; int n_fir_trunk = 0, n_fir_plain = 0;
     int n_append_trunk = 0, n_append_plain = 0, n_append_hand = 0;      /* per list: the chains that append their own input (FirLaunch::appends) */
     DevArr<MemFeed> d_mem_feed; DevArr<int> d_mem_feed_start; int n_mem_feed = 0;
+    /* "chain_sum" (DESIGN.md 4.2o): the terms of the sum trees, tree by tree, and where each tree's begin ([trees + 1]); a plan with a
+     * sum tree launches mem_stage's SUM form */
+    DevArr<MemTerm> d_mem_terms; DevArr<int> d_mem_sum_start; int n_mem_sums = 0;
     /* "chain_copy" (DESIGN.md 4.2k): the live pairs of the core's DSP_LOAD_STORE lists, by destination; copy_pairs once per block call */
     DevArr<CopyPair> d_copy; int n_copy = 0;
     bool lane_mode = false;                              /* formats 3 and 5: chain_lane, one lane per chain, state in the mirror */
@@ -5658,6 +5705,8 @@ int launch_mem(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
     a.hand = pl.d_hand; a.addend = prog->d_addend ? prog->d_addend + pl.block_f0 : nullptr;
     a.scratch = pl.d_mem_scratch; a.scratch_stride = pl.n_mem_cols; a.io = io;
     const dim3 grid((unsigned)pl.n_mem_tiles, (unsigned)((io.nframes + kMemFrames - 1) / kMemFrames));
+    /* ("chain_sum": a plan with sum trees -- the SUM form for all its trees) */
+    if (pl.n_mem_sums && (!pl.d_mem_terms || !pl.d_mem_sum_start)) return set_err("a memory-word stage with sum trees without their tables");
     if (pl.n_mem_feed) {
         /* ("mem_fir": branches that are a FIR alone -- the FEED form puts their input into their rings) */
         if constexpr (FMT == 4 || FMT == 6) {
@@ -5665,8 +5714,19 @@ int launch_mem(avdsp_hip_prog *prog, Plan &pl, BlockIO io, hipStream_t stream)
             MemArgsFeed fa{};
             static_cast<MemArgs &>(fa) = a;
             fa.ring = plan_ring(pl); fa.feed_start = pl.d_mem_feed_start; fa.feed = pl.d_mem_feed;
+            if (pl.n_mem_sums) {
+                MemArgsSum<true> sa{};
+                static_cast<MemArgsFeed &>(sa) = fa;
+                sa.sum_start = pl.d_mem_sum_start; sa.terms = pl.d_mem_terms;
+                hipLaunchKernelGGL((mem_stage<FMT, true, true>), grid, dim3(kBlock), 0, stream, sa);
+            } else
             hipLaunchKernelGGL((mem_stage<FMT, true>), grid, dim3(kBlock), 0, stream, fa);
         } else return set_err("a memory-word stage that feeds FIR rings: formats 4 and 6 only");
+    } else if (pl.n_mem_sums) {
+        MemArgsSum<false> sa{};
+        static_cast<MemArgs &>(sa) = a;
+        sa.sum_start = pl.d_mem_sum_start; sa.terms = pl.d_mem_terms;
+        hipLaunchKernelGGL((mem_stage<FMT, false, true>), grid, dim3(kBlock), 0, stream, sa);
     } else hipLaunchKernelGGL(mem_stage<FMT>, grid, dim3(kBlock), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -6436,6 +6496,8 @@ int avdsp_hip_prog_add_plan(avdsp_hip_prog *prog, const avdsp_plan_desc *d)
         if (t.n_mem_cols && pl.d_mem_scratch.alloc((size_t)kFirChunk * t.n_mem_cols) != hipSuccess) return set_err("hipMalloc(branch block of %d columns)", t.n_mem_cols);
         pl.n_mem_feed = (int)t.mem_feed.size();
         if (pl.n_mem_feed && (pl.d_mem_feed.upload(t.mem_feed) || pl.d_mem_feed_start.upload(t.mem_feed_start))) return -1;
+        pl.n_mem_sums = t.n_mem_sums;
+        if (pl.n_mem_sums && (pl.d_mem_terms.upload(t.mem_terms) || pl.d_mem_sum_start.upload(t.mem_sum_start))) return -1;
     }
     if (pl.overlap_ok) {                                  /* ready words, all at launch number 0 */
         if (pl.d_ready.alloc((size_t)d->nchains) != hipSuccess ||

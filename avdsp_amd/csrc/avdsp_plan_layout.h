@@ -75,11 +75,12 @@ struct MuxTile {
 constexpr int kMemFrames = 64;       /* frames per mem_stage workgroup */
 constexpr int kMemTileTrees = 16;    /* trees per mem_stage workgroup at most ... */
 constexpr int kMemTileCols = 64;     /* ... and a tile is closed once it holds this many columns (one tree may bring more) */
-enum { kMemSrcRow = 0, kMemSrcSample = 1, kMemSrcWord = 2 };
+enum { kMemSrcRow = 0, kMemSrcSample = 1, kMemSrcWord = 2, kMemSrcSum = 3 };
 struct MemTree {
     int word;                        /* the first of the two mirror words */
     int src;                         /* kMemSrcRow: the trunk's hand-over row; kMemSrcSample: a trunk without sections, load_stage of its sample;
-                                        kMemSrcWord: no trunk in this plan, the word as the mirror holds it when the launch starts */
+                                        kMemSrcWord: no trunk in this plan, the word as the mirror holds it when the launch starts;
+                                        kMemSrcSum ("chain_sum"): a sum tree -- no word (0), no trunk, the accumulator formed from its MemTerms */
     int trunk;                       /* the trunk's chain, -1: none */
     int row;                         /* kMemSrcRow: the row read.  Else: a row the stage FILLS for chain_tail (branches without sections but with a
                                         delay line), -1: no such branch */
@@ -93,6 +94,13 @@ struct MemTile { int tree0, ntree, col0, ncol; };
  * every frame's accumulator into the chain's ring.  The feeds tree by tree: those of tree k are mem_feed[mem_feed_start[k] ..
  * mem_feed_start[k + 1]) (a table beside MemTree, whose layout the stage without feeds keeps) */
 struct MemFeed { int tree, cid; };
+/* "chain_sum" (DESIGN.md 4.2o): a sum head is a tree of its own (kMemSrcSum), behind all word trees; its one branch is the head's chain.
+ * Its terms in program order: those of tree k are mem_terms[mem_sum_start[k] .. mem_sum_start[k + 1]) (again a table beside MemTree).
+ * A term takes the accumulator exactly as a LOAD_MEM of its word would see it in that frame: kMemSrcRow, the hand-over row of the
+ * word's trunk (sections or a FIR); kMemSrcSample, load_stage of the trunk's own sample (no sections -- never a row the stage itself
+ * fills in the same launch); kMemSrcWord, the mirror's word when the launch starts (no chain of the core writes it).  op: 0 for the
+ * first term, then AVDSP_SUM_ADD (newest + running) or AVDSP_SUM_SUB (newest - running) */
+struct MemTerm { int src, row, word, in_io, load_mode; unsigned gain_bits; int op; };
 
 /* "chain_copy" (DESIGN.md 4.2k): one live pair of the core's DSP_LOAD_STORE lists -- out[frame][dst] = in[frame][src], the raw word */
 struct CopyPair { int src, dst; };
@@ -160,6 +168,9 @@ struct ChainTables {
     int n_mem_cols = 0, n_mem_trunks = 0, n_mem_branches = 0, n_mem_constant = 0;
     std::vector<MemFeed> mem_feed;       /* "mem_fir": the branches that are a FIR alone, tree by tree ... */
     std::vector<int> mem_feed_start;     /* ... [trees + 1]: where each tree's begin (made when there is a feed) */
+    std::vector<MemTerm> mem_terms;      /* "chain_sum": the terms of the sum trees, tree by tree ... */
+    std::vector<int> mem_sum_start;      /* ... [trees + 1]: where each tree's begin (made when there is a sum tree) */
+    int n_mem_sums = 0;                  /* sum trees: a plan with one launches mem_stage's SUM form */
     /* "chain_copy" (DESIGN.md 4.2k), made by copy_list: the live pairs, sorted by destination (consecutive lanes of copy_pairs store
      * consecutive words where the IOs are).  They count in the IO spans and in stores_whole_window */
     std::vector<CopyPair> copy;
@@ -181,6 +192,7 @@ inline std::string check_heads(const avdsp_plan_desc *d, long long buf_words, Ch
         const bool mem = d->chain_mem && (m == AVDSP_LOAD_MEM || (t.chains[i].mem_store && (m == AVDSP_LOAD_PLAIN || m == AVDSP_LOAD_GAIN)));
         if (m != AVDSP_LOAD_PLAIN && m != AVDSP_LOAD_GAIN && m != AVDSP_LOAD_MUX && !mem) return text("chain %d: load mode %d", i, m);
         if (t.chains[i].mem_store && !mem) return text("chain %d: a memory word has no kernel here", i);
+        if (t.chains[i].sum_n && !mem) return text("chain %d: a sum head that is no branch", i);
         t.has_mux = t.has_mux || m == AVDSP_LOAD_MUX;
         t.has_mem = t.has_mem || mem;
     }
@@ -285,6 +297,8 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     auto find_tree = [&](int w, int *exact) {
         *exact = -1;
         for (size_t k = 0; k < t.mem_tree_list.size(); k++) {
+            /* ("chain_sum": a sum tree has no word -- its 0 would collide with word 1's overlap test) */
+            if (t.mem_tree_list[k].src == kMemSrcSum) continue;
             const int o = t.mem_tree_list[k].word;
             if (o == w) *exact = (int)k; else if (o == w - 1 || o == w + 1) return false;
         }
@@ -297,6 +311,7 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (!c.mem_store) continue;
+        if (c.sum_n) return text("chain %d: a sum head that is a trunk", i);
         if (c.load_mode == AVDSP_LOAD_MEM || c.n_out || c.sat || c.finish || c.delay_slot || c.ways_n || (c.fir_taps && !mem_fir) || c.in_io < 0) return text("chain %d: not a trunk", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
         int exact;
@@ -314,8 +329,13 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
     for (int i = 0; i < n; i++) {
         const avdsp_chain &c = t.chains[i];
         if (c.load_mode != AVDSP_LOAD_MEM) continue;
+        if (c.sum_n < 0 || c.sum_n > AVDSP_MAX_SUM_TERMS - 1) return text("chain %d: %d sum terms", i, c.sum_n);
+        for (int q = 0; q < c.sum_n; q++)
+            if (c.sum_op[q] != AVDSP_SUM_ADD && c.sum_op[q] != AVDSP_SUM_SUB) return text("chain %d: sum operation %d", i, c.sum_op[q]);
+        if (c.sum_n && !d->chain_sum) return text("chain %d: a sum head has no kernel here", i);
         if (c.mem_store || (c.fir_taps && !mem_fir) || (c.n_out < 1 && !(d->chain_copy && c.delay_slot))) return text("chain %d: not a branch", i);
         if (!word_ok(c.mem_word)) return text("chain %d: memory word outside the loaded buffer", i);
+        if (c.sum_n) continue;                               /* (below, behind all word trees) */
         int exact;
         if (!find_tree(c.mem_word, &exact)) return text("chain %d: its memory word overlaps another", i);
         if (exact >= 0 && t.mem_tree_list[exact].trunk > i) return text("chain %d: a branch in front of its trunk", i);
@@ -328,6 +348,34 @@ inline std::string mem_trees(const avdsp_plan_desc *d, long long buf_words, Chai
         tree_of[i] = exact; t.mem_kind[i] = 2; t.n_mem_branches++;
         t.n_mem_constant += t.mem_tree_list[exact].trunk < 0;
     }
+    /* ("chain_sum") the sum heads: a tree each, behind all word trees, and its terms -- the head's own word first -- each from where a
+     * LOAD_MEM of that word takes it.  A word with a trunk must have it in front of the head */
+    const size_t n_word_trees = t.mem_tree_list.size();
+    for (int i = 0; i < n; i++) {
+        const avdsp_chain &c = t.chains[i];
+        if (c.load_mode != AVDSP_LOAD_MEM || !c.sum_n) continue;
+        if (t.mem_sum_start.empty()) t.mem_sum_start.assign(n_word_trees, 0);
+        t.mem_sum_start.push_back((int)t.mem_terms.size());
+        for (int q = 0; q <= c.sum_n; q++) {
+            const int w = q ? c.sum_word[q - 1] : c.mem_word;
+            if (!word_ok(w)) return text("chain %d: memory word of a sum term outside the loaded buffer", i);
+            int exact;
+            if (!find_tree(w, &exact)) return text("chain %d: the memory word of a sum term overlaps another", i);
+            MemTerm m{};
+            m.src = kMemSrcWord; m.row = -1; m.word = w; m.op = q ? c.sum_op[q - 1] : 0;
+            if (exact >= 0 && t.mem_tree_list[exact].trunk >= 0) {
+                const MemTree &o = t.mem_tree_list[exact];
+                if (o.trunk > i) return text("chain %d: a sum term in front of its trunk", i);
+                m.src = o.src; m.row = o.src == kMemSrcRow ? o.row : -1; m.in_io = o.in_io; m.load_mode = o.load_mode; m.gain_bits = o.gain_bits;
+            }
+            t.mem_terms.push_back(m);
+        }
+        MemTree tr{};
+        tr.word = 0; tr.trunk = -1; tr.src = kMemSrcSum; tr.row = -1;
+        tree_of[i] = (int)t.mem_tree_list.size(); t.mem_kind[i] = 2; t.n_mem_branches++; t.n_mem_sums++;
+        t.mem_tree_list.push_back(tr);
+    }
+    if (t.n_mem_sums) t.mem_sum_start.push_back((int)t.mem_terms.size());
     /* the branches tree by tree: columns, the stage's own stores, the rows it fills */
     std::vector<std::vector<int>> members(t.mem_tree_list.size());
     for (int i = 0; i < n; i++) if (tree_of[i] >= 0) members[tree_of[i]].push_back(i);

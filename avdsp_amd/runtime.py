@@ -29,7 +29,7 @@ EXPORTED = [
     "dspRuntimeBlock_2", "dspRuntimeBlock_3", "dspRuntimeBlock_4", "dspRuntimeBlock_5", "dspRuntimeBlock_6",
     "dspRuntimeStrandInfo", "dspRuntimeBlockSubmit", "dspRuntimeBlockWait", "dspRuntimeBlockDevice", "dspRuntimeBlockPcm", "dspRuntimeUnpackPcmDevice", "dspRuntimeBlockAll", "dspRuntimeBlockAllDevice", "dspRuntimeBlockAllPcm",
     "dspRuntimeSyncState", "dspRuntimeUploadState", "dspRuntimeUploadParams", "dspRuntimeSetOption", "dspRuntimeGetOption",
-    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeMemFirInfo", "dspRuntimeCopyInfo", "dspRuntimeWaysInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
+    "dspRuntimeCoreInfo", "dspRuntimeFirGroupInfo", "dspRuntimeMuxInfo", "dspRuntimeFinishInfo", "dspRuntimeDelayInfo", "dspRuntimeFirTailInfo", "dspRuntimeMuxTailInfo", "dspRuntimeMemInfo", "dspRuntimeMemFirInfo", "dspRuntimeCopyInfo", "dspRuntimeWaysInfo", "dspRuntimeSumInfo", "dspRuntimeKernelTime", "dspRuntimeLastError", "dspRuntimeRelease", "dspRuntimeReleaseProgram", "dspRuntimeSelect",
     "dspRuntimeSetShard", "dspRuntimeShardInfo", "dspRuntimeTagOutput", "dspRuntimeTagOutputDevice", "dspRuntimeTagOutputReset",
     "dspRuntimeSetInstances", "dspRuntimeBlockAllInstancesDevice", "dspRuntimeInstanceState",
     # thin HIP ABI (include/avdsp_hip.h)
@@ -147,6 +147,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "dspRuntimeWaysInfo"):             # (AVDSP_LIB may name a library from before the call: bench.py's A/B against the parent)
             L.dspRuntimeWaysInfo.restype = i32
             L.dspRuntimeWaysInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "dspRuntimeSumInfo"):              # (as above)
+            L.dspRuntimeSumInfo.restype = i32
+            L.dspRuntimeSumInfo.argtypes = [i32, vp, C.POINTER(i32), C.POINTER(i32)]
         L.dspRuntimeTagOutput.restype = i32; L.dspRuntimeTagOutput.argtypes = [vp, i32, i32, i32]
         L.dspRuntimeTagOutputDevice.restype = i32; L.dspRuntimeTagOutputDevice.argtypes = [vp, i32, i32, i32, vp]
         L.dspRuntimeTagOutputReset.restype = i32; L.dspRuntimeTagOutputReset.argtypes = [i32]
@@ -318,6 +321,13 @@ class Runtime:
         shard."""
         a, b = C.c_int(), C.c_int()
         self._check(self.L.dspRuntimeWaysInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
+        return (a.value, b.value)
+
+    def sum_info(self, core_index: int = 0):
+        """dspRuntimeSumInfo (host-only): in a core that "chain_sum" puts on the chain kernels, (its sum heads -- each one chain and one
+        branch --, the memory words they load in all)."""
+        a, b = C.c_int(), C.c_int()
+        self._check(self.L.dspRuntimeSumInfo(self.fmt, self.cores[core_index], C.byref(a), C.byref(b)))
         return (a.value, b.value)
 
     def tag_output(self, out: np.ndarray, column: int):

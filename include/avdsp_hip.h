@@ -16,6 +16,7 @@
  * and ("fir_tail", formats 4 and 6) both of them behind a chain's DSP_FIR
  * and ("mux_tail") all of that behind a LOAD_MUX head and beside LOAD_MUX chains
  * and ("chain_ways", formats 2, 4 and 6) a run of DSP_GAIN (:636-640) and DSP_NEGX (:380-383) behind the banks, in front of delay, SAT0DB and STORE
+ * and ("chain_sum", with "chain_mem", formats 2, 4 and 6) a sum head: LOAD_MEM, (LOAD_MEM, ADDXY | SUBXY)+ (:360-363, :370-373) in front of a branch
  *
  * for every chain of the core over a block of frame-interleaved samples.
  */
@@ -73,8 +74,17 @@ typedef struct avdsp_chain {
     int32_t  ways_n;                 /* 0: none */
     int32_t  ways_op[4];             /* AVDSP_WAY_*            (AVDSP_MAX_WAY_OPS entries) */
     uint32_t ways_gain_bits[4];      /* AVDSP_WAY_GAIN: Q4.28 int or float bits of the DSP_GAIN parameter */
+    /* a sum head ("chain_sum"): load_mode AVDSP_LOAD_MEM and  LOAD_MEM mem_word, (LOAD_MEM sum_word[k], ADDXY | SUBXY) x
+     * sum_n.  A load moves X to Y (dsp_runtime.c:750-757), so at step k X is the newest word and Y the running value, which becomes
+     * newest + running (ADDXY, :360-363) or newest - running (SUBXY, :370-373).  Behind it whatever a branch may be.  mem_stage's SUM
+     * form makes it a tree of its own */
+    int32_t  sum_n;                  /* 0: none; terms behind the first word (AVDSP_MAX_SUM_TERMS - 1 at most) */
+    int32_t  sum_word[7];            /* the first of the two program words of term k + 1 */
+    int32_t  sum_op[7];              /* AVDSP_SUM_* */
 } avdsp_chain;
 #define AVDSP_MAX_WAY_OPS 4
+#define AVDSP_MAX_SUM_TERMS 8
+enum { AVDSP_SUM_ADD = 1, AVDSP_SUM_SUB = 2 };
 enum { AVDSP_WAY_GAIN = 1, AVDSP_WAY_NEG = 2 };
 enum { AVDSP_DELAY_NONE = 0, AVDSP_DELAY_A = 1, AVDSP_DELAY_B = 2 };      /* A: in front of the SAT0DB slot, B: behind it */
 enum { AVDSP_FINISH_NONE = 0, AVDSP_FINISH_TPDF = 1, AVDSP_FINISH_GAIN = 2, AVDSP_FINISH_TPDF_GAIN = 3 };      /* bit 0: dither, bit 1: gain */
@@ -124,6 +134,8 @@ typedef struct avdsp_plan_desc {
                                         hands its sums to mem_stage, a branch's FIR takes the word the stage forms; 0: such a chain is refused */
     int32_t  chain_ways;             /* 1 ("chain_ways", formats 2, 4 and 6): a chain may have way operations (ways_n), which make it a chain of chain_tail's;
                                         0: such a chain is refused */
+    int32_t  chain_sum;              /* 1 ("chain_sum", with chain_mem, formats 2, 4 and 6): an AVDSP_LOAD_MEM chain may be a sum head (sum_n), a tree of its own
+                                        in mem_stage's SUM form; 0: such a chain is refused */
 } avdsp_plan_desc;
 #define AVDSP_FIR_GROUP_MIN 16
 #define AVDSP_MUX_GROUP_MIN 16

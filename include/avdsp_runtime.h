@@ -449,6 +449,23 @@ int dspRuntimeCopyInfo(int format, opcode_t *core, int *pairs, int *live);
  * way as a chain) and the chains this process runs that have way operations.  A core the interpreter runs reports zeros. */
 int dspRuntimeWaysInfo(int format, opcode_t *core, int *forks, int *op_chains);
 
+/* "chain_sum" (dspRuntimeSetOption, 0 or 1, default 0; effective only with "chain_mem" 1 and in formats 2, 4 and 6):
+ * sum heads, a bus formed from memory words in front of a branch:
+ *     LOAD_MEM(w0), ( LOAD_MEM(wk), ADDXY | SUBXY ){1 .. AVDSP_MAX_SUM_TERMS - 1}
+ * Each later LOAD_MEM stands directly behind the head or behind the ADDXY / SUBXY before it, its ADDXY / SUBXY directly behind it (NOP,
+ * PARAM, PARAM_NUM and SERIAL do not count).  A load moves X to Y, so at each step X is the newest word and Y the running value, which
+ * becomes newest + running (ADDXY) or newest - running (SUBXY): nothing is reassociated, a word may occur twice.  Behind the head comes
+ * whatever a LOAD_MEM branch may be under the options that are on, except a COPYXY fork.  Every term word is held to the rules of a
+ * branch's word: a free word of a PARAM section, not overlapping another, not read as a parameter, its STORE_MEM -- if the core has
+ * one -- in front of the head.
+ * Refused with -8 and a text of its own, the core then on the interpreter as with 0: a LOAD_MEM behind a LOAD_MEM head without its
+ * ADDXY / SUBXY, an ADDXY / SUBXY anywhere else, a ninth word, a COPYXY behind a sum head, a term in front of its word's STORE_MEM, a
+ * sum head in a sharded core (also under "shard_trees").  A STORE_MEM in such a chain, instances and formats 3 and 5 keep the texts
+ * they have.  With 0 every core takes the path and the refusal text it had before the option existed.
+ * dspRuntimeSumInfo is host-only, nothing runs on the GPU: the sum heads of the core (dspRuntimeCoreInfo counts each as one chain,
+ * dspRuntimeMemInfo as one branch) and the words they load in all.  A core the interpreter runs reports zeros. */
+int dspRuntimeSumInfo(int format, opcode_t *core, int *heads, int *terms);
+
 const char *dspRuntimeLastError(void);
 void        dspRuntimeRelease(void);        /* frees device memory of every loaded program; the next Init starts clean */
 /* Several programs in one process.  dspRuntimeInit(codePtr, ...) loads a program into a context of its own, keyed by the
